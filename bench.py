@@ -21,7 +21,13 @@ iterate sent whole from rank 0) and `no_exchange` (x in place), and the per-rank
 `value`: weak scaling = shard evaluations all ranks completed per second; strong scaling = evaluations of the whole
 transcription per second; both over the max-over-ranks wall time of the K timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--x-mode peer|halo]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--x-mode peer|halo] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step handed its caller -- the constraint vector c and the Jacobian values, float64
+-- as DIR/constraints.npy and DIR/jacobian_values.npy (N > 1: each rank's full-length buffers as DIR/<name>_rank<r>.npy;
+entries the rank does not compute stay zero).  The inputs are closed-form, so two builds run with the same arguments can be
+compared output for output.  Above 64 MB in all, the larger arrays are cut to a fixed, seeded sample of their entries (sorted
+positions); the result line lists what was written.  (`bench_outputs/` in the repository root is ignored by git for this.)
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is one rank;
 started plainly (`python bench.py --gpus N`) it spawns the N rank processes itself -- fresh interpreters, nothing in the
@@ -96,6 +102,31 @@ def cpu_baseline(problem, scheme, N, x, budget_s=10.0):
                                         f"duals), OpenMP over the time steps, {avail} threads (oracle/ctd_oracle.cpp "
                                         f"orc_cons_jac_block)"}
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array of `arrays` (name -> array) as out_dir/<name>.npy in float64, at most `limit` bytes in all.
+    Over the limit, the smaller arrays are kept whole while they fit and the larger ones share what is left, each cut to a fixed,
+    seeded sample of its positions (sorted; the same positions for the same lengths).  Returns name -> {"entries", "of"}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    room = (limit - 4096 * len(arrays)) // 8          # float64 entries (4 KiB per file left for the .npy header)
+    written = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].size)):
+        a = arrays[name]
+        n = a.size
+        keep = min(n, room // (len(arrays) - i))
+        if keep < n:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))]
+        room -= keep
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"entries": int(keep), "of": int(n)}
+    return written
 
 
 def self_launch(argv, gpus, script=None):
@@ -188,6 +219,8 @@ def _main(real_stdout):
     ap.add_argument("--two-streams", action="store_true",
                     help="also time independent evaluations on two streams (overlapping kernels: keeps it out of the default run, whose rocprofv3 "
                          "kernel statistics are the timed region's)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (c and the Jacobian values, float64, at most 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     PROBLEM, SCHEME = cfg["problem"], cfg["scheme"]
@@ -285,8 +318,9 @@ def _main(real_stdout):
             el = float(t[0])
         return el
 
-    def measure(name, steps, warmup, ksec):
+    def measure(name, steps, warmup, ksec, keep_outputs=False):
         """One workload of CONFIGS on this job's ranks: the timed step + its secondary figures + per-rank kernel times.
+        keep_outputs: copy c and the Jacobian values as the last timed step left them (out.outputs).
         N = 1: one fused evaluation, pointers pre-bound.  N > 1: the rank's evaluation on the SHARDED iterate -- x_mode "peer":
         the neighbours' entries read in place by the kernel, outputs row-sharded, no collective before or
         after the kernel; x_mode "halo": one all-gather of the few entries first."""
@@ -323,9 +357,12 @@ def _main(real_stdout):
                 peer_error = repr(e)[:300]
                 x_mode = "halo"
         el = timed(sh.bind_cons_jac(x, c, vals, stitch=False, x_mode=x_mode), warmup, steps)
+        outputs = None
+        if keep_outputs:          # (before any secondary figure writes into c and vals again)
+            outputs = {"constraints": c.cpu().numpy(), "jacobian_values": vals.cpu().numpy()}
         out = SimpleNamespace(name=name, cfg=cf, N=N, sh=sh, docp=docp, x_host=x_host, x_full=x_full, x=x, c=c, vals=vals, el=el,
                               steps=steps, x_mode=x_mode, peer_error=peer_error, region_ms=region["ms_per_launch"],
-                              per_step_value=(world if cf["scaling"] == "weak" else 1), secondary={})
+                              per_step_value=(world if cf["scaling"] == "weak" else 1), secondary={}, outputs=outputs)
         secondary = out.secondary
         if dist_on:
             # the rank's outputs from the sharded iterate (NaN outside what it owns) equal those from the whole iterate, bit for bit
@@ -431,11 +468,16 @@ def _main(real_stdout):
                             for r in range(world)]
         return out
 
-    m = measure(args.config, args.steps, args.warmup, 500)
+    m = measure(args.config, args.steps, args.warmup, 500, keep_outputs=bool(args.dump_outputs))
     sh, docp, x_host, x_full, x, c, vals = m.sh, m.docp, m.x_host, m.x_full, m.x, m.c, m.vals
     N, el, x_mode, one, alg_bytes = m.N, m.el, m.x_mode, m.one, m.alg_bytes
     region_ms, per_step_value, secondary, per_dispatch, per_rank = m.region_ms, m.per_step_value, m.secondary, m.per_dispatch, m.per_rank
     b, e = sh.steps
+    dumped = None
+    if args.dump_outputs:         # every rank its own buffers; the 64 MB are shared among the ranks
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dumped = dump_outputs(args.dump_outputs, {k + sfx: v for k, v in m.outputs.items()}, limit=DUMP_LIMIT_BYTES // world)
+        m.outputs = None
 
     # N > 1, default line: the strong-scaling workloads north_star names ("a 10k-step Goddard transcription at 1/2/4/8" =
     # cfg2_strong; BASELINE configs[3] / [4] sharded), each with its stitched-c variant -- `value` stays the weak-scaling figure
@@ -718,6 +760,8 @@ def _main(real_stdout):
         if dist_on:
             out["config"]["x_mode"] = x_mode
         out.update(separately)
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if dist_on:
