@@ -33,6 +33,21 @@ typedef unsigned long uintptr_t;
 
 namespace ctd {
 
+// ---- batched launches: member b of a batch of iterates is the grid's second dimension -----------------------------------
+// (0 in single launches, in the fused iteration kernel and in the host builds of the kernel bodies -- tests/emu)
+CTD_HD int64_t batch_member() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int64_t)blockIdx.y;
+#else
+    return 0;
+#endif
+}
+// the batch member's copy of an output (p may be null: that output is skipped); B = false: p itself, no arithmetic
+template <bool B> CTD_HD double* member_out(double* p, int64_t ld) {
+    if constexpr (B) return p ? p + batch_member() * ld : p;
+    else return p;
+}
+
 // ---- forward-mode dual number with K directions, evaluated in registers ---------------------------------
 // The reference obtains Jacobian values by pushing ForwardDiff.Dual numbers through its generic callbacks
 // (ADNLPModels.SparseADJacobian, call site src/collocation.jl:116-120).  The engine differentiates the

@@ -97,7 +97,7 @@ struct ctd_handle {
     double* d_obj = nullptr;
     double* d_g = nullptr;          // staging for ctd_grad (host pointers)
     double* d_gpartial = nullptr;   // per-workgroup partial sums of dg/dv
-    int gblocks = 0;
+    int64_t gblocks = 0;            // rows of kMaxNV partial sums d_gpartial holds
     int obj_blocks = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // run-time defined OCP (ctd_register_ocp): kernels compiled with hiprtc and launched through the module API
@@ -130,6 +130,13 @@ struct ctd_handle {
     // ctd_stitch_c: padded send block and gathered blocks
     double *d_stitch_send = nullptr, *d_stitch_recv = nullptr;
     int64_t stitch_cap = 0;
+    // batched callbacks (ctd_*_batch_dev_async): capacity (doubles) of the objective's partial sums, doubles of Hessian partial
+    // sums per member and their capacity -- the buffers grow with the batch; the batched constraint / Jacobian kernel of a
+    // run-time OCP (compiled on first use)
+    int64_t partial_cap = 0, hpart_member = 0, hpart_cap = 0;
+    double out_mb = 0.0;            // megabytes of constraint / Jacobian outputs of one evaluation (the write-through rule, ctd_create)
+    hipModule_t jit_bmod = nullptr;
+    hipFunction_t f_cons_jac_batch = nullptr;
     std::string err;
 };
 
@@ -192,6 +199,7 @@ static void free_device(ctd_handle* h) {
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
     if (h->jit_hmod) (void)hipModuleUnload(h->jit_hmod);
+    if (h->jit_bmod) (void)hipModuleUnload(h->jit_bmod);
 }
 
 // ---- run-time compilation of the kernel templates for a registered OCP -------------------------------------------------
@@ -280,11 +288,12 @@ std::vector<std::string> jit_hess_exprs(int sc, int s) {
     return {"ctd::hess_kernel<" + P + ", " + a + ", " + b + ", false>", "ctd::hess_finish_kernel<" + P + ">"};
 }
 
+// batch: the grid's second dimension (members of a batched launch)
 hipError_t jit_launch(hipFunction_t f, int grid, int block, size_t lds, hipStream_t st, void** args, hipEvent_t e0 = nullptr,
-                      hipEvent_t e1 = nullptr) {
+                      hipEvent_t e1 = nullptr, int batch = 1) {
     if (e0 || e1)
-        return hipExtModuleLaunchKernel(f, (uint32_t)grid * (uint32_t)block, 1, 1, (uint32_t)block, 1, 1, lds, st, args, nullptr, e0, e1, 0);
-    return hipModuleLaunchKernel(f, (uint32_t)grid, 1, 1, (uint32_t)block, 1, 1, (uint32_t)lds, st, args, nullptr);
+        return hipExtModuleLaunchKernel(f, (uint32_t)grid * (uint32_t)block, (uint32_t)batch, 1, (uint32_t)block, 1, 1, lds, st, args, nullptr, e0, e1, 0);
+    return hipModuleLaunchKernel(f, (uint32_t)grid, (uint32_t)batch, 1, (uint32_t)block, 1, 1, (uint32_t)lds, st, args, nullptr);
 }
 }  // namespace
 
@@ -297,6 +306,20 @@ static int32_t jit_load_first(ctd_handle* h) {
     HIP_TRY(nullptr, hipModuleLoadData(&h->jit_mod, code.data()));
     hipFunction_t* f[] = {&h->f_cons_jac, &h->f_obj_partial, &h->f_obj_finish, &h->f_grad_units, &h->f_grad_finish};
     for (int i = 0; i < 5; ++i) HIP_TRY(nullptr, hipModuleGetFunction(f[i], h->jit_mod, names[i].c_str()));
+    return CTD_OK;
+}
+// the batched constraint / Jacobian kernel (cons_jac_batch_kernel) of a run-time OCP: compiled at the first batched call
+static int32_t jit_load_batch(ctd_handle* h) {
+    std::string code, err;
+    std::vector<std::string> names;
+    const Layout& Lj = h->model.L;
+    const int s = Lj.sc == SC_MIDPOINT ? Lj.cs : Lj.s;
+    const std::string b = std::to_string((Lj.sc == SC_IRK || Lj.sc == SC_MIDPOINT) && s > 0 ? s : 1);
+    const std::vector<std::string> exprs = {"ctd::cons_jac_batch_kernel<ctd::UserOCP, " + std::to_string(Lj.sc) + ", " + b + ">"};
+    int32_t st = jit_compile(*h->rt, "ctd_kernels.hpp", exprs, "off", code, names, err);
+    if (st) return fail(h, st, err);
+    HIP_TRY(h, hipModuleLoadData(&h->jit_bmod, code.data()));
+    HIP_TRY(h, hipModuleGetFunction(&h->f_cons_jac_batch, h->jit_bmod, names[0].c_str()));
     return CTD_OK;
 }
 static int32_t jit_load_hess(ctd_handle* h) {
@@ -449,6 +472,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
         const int wt = env_int("CTD_WT_STORE", -1);
         const double out_mb = 8.0 * ((double)(h->step_end - h->step_begin) * (mo.L.cb + mo.Lseg + (double)mo.L.nv * mo.vr)) / 1.0e6;
         h->kp.wt_store = wt >= 0 ? (wt ? 1 : 0) : (out_mb <= (double)env_int("CTD_WT_MB", 64) ? 1 : 0);
+        h->out_mb = out_mb;
     }
     h->kp.xcd_remap = env_int("CTD_XCD", 0);          // 1: every XCD walks one contiguous run of tiles (measured neutral)
     h->device = desc->device;
@@ -496,6 +520,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
         hp->kp.edge_code = hp->d_edge_code;
         hp->obj_blocks = 256;
         HIP_TRY(nullptr, hipMalloc((void**)&hp->d_partial, sizeof(double) * hp->obj_blocks));
+        hp->partial_cap = hp->obj_blocks;
         HIP_TRY(nullptr, hipMalloc((void**)&hp->d_obj, sizeof(double)));
         HIP_TRY(nullptr, hipEventCreate(&hp->ev0));
         HIP_TRY(nullptr, hipEventCreate(&hp->ev1));
@@ -923,8 +948,14 @@ int32_t ctd_launch_info(const ctd_handle* h, int64_t* o) {
 
 // ---- hot path ------------------------------------------------------------------------------------------------
 
+// A batched call (ctd_*_batch_dev_async): n members, member b at x + b ldx, ... (leading dimensions in doubles, already checked)
+struct Batch {
+    int32_t n;
+    int64_t ldx, ldy, ldc, ldv, ldg, ldh;
+};
+
 static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_dev, double* vals_dev, hipEvent_t te0 = nullptr,
-                                hipEvent_t te1 = nullptr) {
+                                hipEvent_t te1 = nullptr, const Batch* bt = nullptr) {
     if (!h) return CTD_EINVAL;
     if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
     if (!x_dev) return fail(h, CTD_EINVAL, "x is null");
@@ -934,6 +965,22 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     kp.vals = vals_dev;
     hipError_t e = hipErrorInvalidValue;
     const int sc = h->model.L.sc;
+    if (bt) {      // the batched instantiation of the kernel: grid (tiles, members)
+        BatchLd bl{bt->ldx, bt->ldc, bt->ldv};
+        // write-through stores by the rule of ctd_create, applied to what the whole LAUNCH writes (all members)
+        if (env_int("CTD_WT_STORE", -1) < 0) kp.wt_store = h->out_mb * bt->n <= (double)env_int("CTD_WT_MB", 64) ? 1 : 0;
+        if (h->rt) {
+            if (!h->f_cons_jac_batch) { const int32_t jst = jit_load_batch(h); if (jst) return jst; }
+            void* args[] = {&kp, &x_dev, &bl};
+            e = jit_launch(h->f_cons_jac_batch, h->grid, h->block, h->lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
+        }
+        for_problem(h->model.problem, [&](auto tag) {
+            using P = typename decltype(tag)::type;
+            e = launch_cons_jac_batch<P>(sc, kp, x_dev, bl, h->grid, h->block, h->lds_bytes, h->stream, bt->n);
+        });
+        if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
+        return CTD_OK;
+    }
     if (h->rt) {
         void* args[] = {&kp, &x_dev};
         e = jit_launch(h->f_cons_jac, h->grid, h->block, h->lds_bytes, h->stream, args, te0, te1);
@@ -1027,7 +1074,26 @@ int32_t ctd_cons_jac(ctd_handle* h, const double* x, double* c, double* vals) {
 // kernel parameters of the objective pass; returns the quadrature workgroups (0 for a Mayer-only cost)
 static int fill_obj_params(ctd_handle* h, double* f_dev, ObjParams& op);
 
-static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev) {
+// Grows a partial-sum buffer of the handle to `need` doubles (batched calls: one set of partial sums per member).  The buffer
+// may still be read by launches in flight, so the handle's stream is drained first -- which a capturing stream cannot do, and
+// nothing may be allocated inside a capture either: the call is refused there.
+static int32_t grow_scratch(ctd_handle* h, double** buf, int64_t& cap, int64_t need, const char* fn) {
+    if (need <= cap && *buf) return CTD_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this batch needs larger partial-sum buffers, which cannot be allocated while the "
+                                   "stream is capturing; make one call with the same batch size before the capture");
+    (void)hipGetLastError();
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    cap = 0;
+    HIP_TRY(h, hipMalloc((void**)buf, sizeof(double) * (size_t)need));
+    cap = need;
+    return CTD_OK;
+}
+
+static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev, const Batch* bt = nullptr) {
     if (!h) return CTD_EINVAL;
     if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
     if (!x_dev || !f_dev) return fail(h, CTD_EINVAL, "null argument");
@@ -1036,15 +1102,22 @@ static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev) {
     ObjParams op;
     const int blocks = fill_obj_params(h, f_dev, op);
     const bool lagrange = h->model.info.lagrange;
+    const int nb = bt ? bt->n : 1;
+    if (bt) {
+        const int32_t st = grow_scratch(h, &h->d_partial, h->partial_cap, (int64_t)nb * (blocks > 0 ? blocks : 1), "ctd_obj_batch_dev_async");
+        if (st) return st;
+        op.partial = h->d_partial;
+        op.ldx = bt->ldx;
+    }
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&op, &x_dev};
-        e = lagrange ? jit_launch(h->f_obj_partial, blocks, 256, 0, h->stream, args) : hipSuccess;
-        if (e == hipSuccess) e = jit_launch(h->f_obj_finish, 1, 64, 0, h->stream, args);
+        e = lagrange ? jit_launch(h->f_obj_partial, blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
+        if (e == hipSuccess) e = jit_launch(h->f_obj_finish, 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_obj<P>(L.sc, op, x_dev, lagrange ? blocks : 0, 256, h->stream);
+        e = launch_obj<P>(L.sc, op, x_dev, lagrange ? blocks : 0, 256, h->stream, nb);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;
@@ -1084,7 +1157,8 @@ int32_t ctd_obj_dev(ctd_handle* h, const double* x_dev, double* f_host) {
     return CTD_OK;
 }
 
-static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, GradParams* only_params = nullptr, bool shard = false);
+static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, GradParams* only_params = nullptr, bool shard = false,
+                            const Batch* bt = nullptr);
 int32_t ctd_grad_dev_async(ctd_handle* h, const double* x_dev, double* g_dev) { return enqueue_grad(h, x_dev, g_dev); }
 // the shard's own entries of the gradient from a sharded iterate read in place (see include/ctdirect_hip.h)
 int32_t ctd_grad_shard_dev_async(ctd_handle* h, const double* x_dev, double* g_dev) { return enqueue_grad(h, x_dev, g_dev, nullptr, true); }
@@ -1095,7 +1169,13 @@ int32_t ctd_grad_dev(ctd_handle* h, const double* x_dev, double* g_dev) {
     return CTD_OK;
 }
 
-static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, GradParams* only_params, bool shard) {
+// zeroes entries [0, len) of `rows` rows with leading dimension ld (the batched gradient's tails: one launch for all members)
+__global__ void zero_rows_kernel(double* __restrict__ p, int64_t ld, int64_t len) {
+    double* row = p + (int64_t)blockIdx.y * ld;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < len; e += (int64_t)gridDim.x * blockDim.x) row[e] = 0.0;
+}
+
+static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, GradParams* only_params, bool shard, const Batch* bt) {
     if (!h) return CTD_EINVAL;
     if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
     if (!x_dev || !g_dev) return fail(h, CTD_EINVAL, "null argument");
@@ -1109,7 +1189,13 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     const int64_t ub = shard ? h->step_begin : 0, ue = shard ? ((L.sc != SC_IRK && last) ? L.N + 1 : h->step_end) : all_units;
     const int64_t units = ue - ub;
     const int blocks = (int)((units + 255) / 256);
-    if (!h->d_gpartial || h->gblocks < blocks) {
+    const int nb = bt ? bt->n : 1;
+    if (bt) {
+        int64_t cap = h->d_gpartial ? h->gblocks * kMaxNV : 0;
+        const int32_t st = grow_scratch(h, &h->d_gpartial, cap, (int64_t)nb * blocks * kMaxNV, "ctd_grad_batch_dev_async");
+        if (st) return st;
+        h->gblocks = cap / kMaxNV;
+    } else if (!h->d_gpartial || h->gblocks < blocks) {
         if (h->d_gpartial) (void)hipFree(h->d_gpartial);
         h->d_gpartial = nullptr;
         HIP_TRY(h, hipMalloc((void**)&h->d_gpartial, sizeof(double) * (size_t)blocks * kMaxNV));
@@ -1131,7 +1217,16 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     // (final state, variables) needs zeroing before the finish kernel adds the Mayer part; a Mayer-only gradient is zero
     // except at x_0, x_f, v: one memset and the finish kernel
     const bool lagrange = h->model.info.lagrange;
-    if (shard) {
+    if (bt) {
+        // every member's g: the same entries as below (the tail, or all of g for a Mayer-only cost), zeroed by one launch
+        gp.ldx = bt->ldx;
+        gp.ldg = bt->ldg;
+        const int64_t z0 = lagrange ? L.N * (int64_t)L.blk : 0, len = L.nvar - z0;
+        if (len > 0) {
+            zero_rows_kernel<<<dim3((unsigned)std::min<int64_t>(64, (len + 255) / 256), (unsigned)nb), 256, 0, h->stream>>>(g_dev + z0, bt->ldg, len);
+            HIP_TRY(h, hipGetLastError());
+        }
+    } else if (shard) {
         // a shard touches its own entries only: zero what the unit kernel does not write (everything, for a Mayer-only cost), the
         // final-state entries on the last shard, and the nv variable entries (the finish kernel assigns them)
         const int64_t lo = h->step_begin * (int64_t)L.blk, hi = h->step_end * (int64_t)L.blk;
@@ -1144,12 +1239,12 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&gp, &x_dev};
-        e = lagrange ? jit_launch(h->f_grad_units, blocks, 256, 0, h->stream, args) : hipSuccess;
-        if (e == hipSuccess) e = jit_launch(h->f_grad_finish, 1, 64, 0, h->stream, args);
+        e = lagrange ? jit_launch(h->f_grad_units, blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
+        if (e == hipSuccess) e = jit_launch(h->f_grad_finish, 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_grad<P>(L.sc, L.s, gp, x_dev, lagrange ? blocks : 0, h->stream);
+        e = launch_grad<P>(L.sc, L.s, gp, x_dev, lagrange ? blocks : 0, h->stream, nb);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;
@@ -1329,8 +1424,9 @@ static int32_t ensure_hess(ctd_handle* h) {
     const int step_wgs = h->hess_step ? (int)((h->hp.step_end - h->hp.step_begin + kStepBlock - 1) / kStepBlock) : 0;
     const int edge_step = 32;      // (upper bound of the edge workgroups of the step launch)
     if (h->d_hpartials) { (void)hipFree(h->d_hpartials); h->d_hpartials = nullptr; }
-    HIP_TRY(h, hipMalloc((void**)&h->d_hpartials, sizeof(double) * (size_t)(std::max(h->hp.ntiles, step_wgs) + std::max(h->hp.n_edge_blocks, edge_step)) *
-                                                       (H.nvv > 0 ? H.nvv : 1)));
+    h->hpart_member = (int64_t)(std::max(h->hp.ntiles, step_wgs) + std::max(h->hp.n_edge_blocks, edge_step)) * (H.nvv > 0 ? H.nvv : 1);
+    HIP_TRY(h, hipMalloc((void**)&h->d_hpartials, sizeof(double) * (size_t)h->hpart_member));
+    h->hpart_cap = h->hpart_member;
     HParams& hp = h->hp;
     hp.tau = h->d_tau;
     hp.tptr = h->d_htptr; hp.terms = h->d_hterms; hp.pair_c = h->d_hpair_c;
@@ -1392,14 +1488,21 @@ static int32_t ensure_hess(ctd_handle* h) {
 }
 
 static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* vals_dev,
-                            hipEvent_t te0 = nullptr, hipEvent_t te1 = nullptr) {
+                            hipEvent_t te0 = nullptr, hipEvent_t te1 = nullptr, const Batch* bt = nullptr) {
     if (!h) return CTD_EINVAL;
     if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
     if (!x_dev || !y_dev || !vals_dev) return fail(h, CTD_EINVAL, "null argument");
     int32_t st = ensure_hess(h);
     if (st) return st;
     DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
+    const int nb = bt ? bt->n : 1;
+    if (bt) {      // one set of V x V partial sums per member
+        st = grow_scratch(h, &h->d_hpartials, h->hpart_cap, (int64_t)nb * h->hpart_member, "ctd_hess_coord_batch_dev_async");
+        if (st) return st;
+        h->hp.partials = h->hp_step.partials = h->sp.partials = h->d_hpartials;
+    }
     HParams hp = h->hp;
+    if (bt) { hp.ldx = bt->ldx; hp.ldy = bt->ldy; hp.ldh = bt->ldh; hp.part_stride = h->hpart_member; }
     hp.obj_weight = obj_weight;
     hp.vals = vals_dev;
     hp.halo = h->kp.halo;
@@ -1408,8 +1511,8 @@ static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&hp, &x_dev, &y_dev};
-        e = jit_launch(h->f_hess, hp.ntiles + hp.n_edge_blocks, kHessBlock, h->hess_lds_bytes, h->stream, args, te0, te1);
-        if (e == hipSuccess && hp.nvv > 0) e = jit_launch(h->f_hess_finish, 1, kHessBlock, 0, h->stream, args);
+        e = jit_launch(h->f_hess, hp.ntiles + hp.n_edge_blocks, kHessBlock, h->hess_lds_bytes, h->stream, args, te0, te1, nb);
+        if (e == hipSuccess && hp.nvv > 0) e = jit_launch(h->f_hess_finish, 1, kHessBlock, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1418,12 +1521,14 @@ static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_
             he.obj_weight = obj_weight;
             he.vals = vals_dev;
             he.halo = hp.halo; he.near = hp.near; he.own_lo = hp.own_lo; he.own_hi = hp.own_hi;       // (its edge blocks; a step lane reads its own step only)
+            he.ldx = hp.ldx; he.ldy = hp.ldy; he.ldh = hp.ldh; he.part_stride = hp.part_stride;
             SParams sp = h->sp;
             sp.obj_weight = obj_weight;
             sp.vals = vals_dev;
-            e = launch_hess_step<P>(he, sp, x_dev, y_dev, h->hess_step_lds, h->stream, te0, te1);
+            sp.ldh = hp.ldh; sp.part_stride = hp.part_stride;
+            e = launch_hess_step<P>(he, sp, x_dev, y_dev, h->hess_step_lds, h->stream, te0, te1, nb);
         } else {
-            e = launch_hess<P>(hp, x_dev, y_dev, h->hess_lds_bytes, h->stream, te0, te1);
+            e = launch_hess<P>(hp, x_dev, y_dev, h->hess_lds_bytes, h->stream, te0, te1, nb);
         }
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -1456,6 +1561,68 @@ int32_t ctd_hess_coord(ctd_handle* h, const double* x, const double* y, double o
     HIP_TRY(h, hipMemcpyAsync(vals, h->d_hvals, sizeof(double) * mo.H.nnzh, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return CTD_OK;
+}
+
+// ---- batched callbacks: K iterates of one transcription per launch ---------------------------------------------------
+// The same kernels on a grid whose second dimension is the member (include/ctdirect_hip.h).  Checks in this order: handle,
+// device (CTD_ENODEVICE), batch size, whole-grid handle, then pointers and leading dimensions (CTD_EINVAL).
+constexpr int32_t kMaxBatch = 65535;       // the grid's y limit
+
+static int32_t batch_check(ctd_handle* h, const char* fn, int32_t batch, const double* x_dev, int64_t ldx) {
+    if (!h) return CTD_EINVAL;
+    if (h->device < 0) return fail(h, CTD_ENODEVICE, std::string(fn) + ": compute call on a host-only handle (device = -1); there is no CPU fallback");
+    if (batch < 1 || batch > kMaxBatch) return fail(h, CTD_EINVAL, std::string(fn) + ": batch must be in [1, 65535], got " + std::to_string(batch));
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": batched calls need a handle of the whole grid; a shard handle (step_begin / step_end, "
+                                   "ctd_set_x_shards) evaluates one iterate per call");
+    if (!x_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": x is null");
+    if (ldx < h->model.L.nvar) return fail(h, CTD_EINVAL, std::string(fn) + ": ldx = " + std::to_string(ldx) + " < nvar = " + std::to_string(h->model.L.nvar));
+    return CTD_OK;
+}
+static int32_t ld_check(ctd_handle* h, const char* fn, const char* name, int64_t ld, int64_t n) {
+    if (ld < n) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " = " + std::to_string(ld) + " is below the vector length " + std::to_string(n));
+    return CTD_OK;
+}
+
+int32_t ctd_cons_jac_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* c_dev, int64_t ldc,
+                                     double* vals_dev, int64_t ldv) {
+    static const char* fn = "ctd_cons_jac_batch_dev_async";
+    int32_t st = batch_check(h, fn, batch, x_dev, ldx);
+    if (!st && c_dev) st = ld_check(h, fn, "ldc", ldc, h->model.L.ncon);
+    if (!st && vals_dev) st = ld_check(h, fn, "ldv", ldv, h->model.nnzj);
+    if (st) return st;
+    const Batch bt{batch, ldx, 0, c_dev ? ldc : 0, vals_dev ? ldv : 0, 0, 0};
+    return enqueue_cons_jac(h, x_dev, c_dev, vals_dev, nullptr, nullptr, &bt);
+}
+
+int32_t ctd_obj_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* f_dev) {
+    int32_t st = batch_check(h, "ctd_obj_batch_dev_async", batch, x_dev, ldx);
+    if (st) return st;
+    if (!f_dev) return fail(h, CTD_EINVAL, "ctd_obj_batch_dev_async: f is null");
+    const Batch bt{batch, ldx, 0, 0, 0, 0, 0};
+    return enqueue_obj(h, x_dev, f_dev, &bt);
+}
+
+int32_t ctd_grad_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* g_dev, int64_t ldg) {
+    static const char* fn = "ctd_grad_batch_dev_async";
+    int32_t st = batch_check(h, fn, batch, x_dev, ldx);
+    if (st) return st;
+    if (!g_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": g is null");
+    if ((st = ld_check(h, fn, "ldg", ldg, h->model.L.nvar))) return st;
+    const Batch bt{batch, ldx, 0, 0, 0, ldg, 0};
+    return enqueue_grad(h, x_dev, g_dev, nullptr, false, &bt);
+}
+
+int32_t ctd_hess_coord_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, const double* y_dev, int64_t ldy,
+                                       double obj_weight, double* vals_dev, int64_t ldh) {
+    static const char* fn = "ctd_hess_coord_batch_dev_async";
+    int32_t st = batch_check(h, fn, batch, x_dev, ldx);
+    if (st) return st;
+    if (!y_dev || !vals_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": y or vals is null");
+    if ((st = ld_check(h, fn, "ldy", ldy, h->model.L.ncon))) return st;
+    if ((st = ld_check(h, fn, "ldh", ldh, h->model.H.nnzh))) return st;
+    const Batch bt{batch, ldx, ldy, 0, 0, 0, ldh};
+    return enqueue_hess(h, x_dev, y_dev, obj_weight, vals_dev, nullptr, nullptr, &bt);
 }
 
 // ---- one solver iteration in one call --------------------------------------------------------------------------------

@@ -196,6 +196,12 @@ struct HParams {
     int32_t debug_stop;
     // diagnostics only (ctd_hess_debug_stamps): lane 0 of every workgroup stores 5 x {100 MHz realtime, shader cycles}
     unsigned long long* stamps;
+    // batched launches (ctd_hess_coord_batch_dev_async): member b = blockIdx.y reads xu + b * ldx, y + b * ldy, writes vals + b * ldh
+    // and its partial sums at partials + b * part_stride (0 in single launches: every offset vanishes)
+    int64_t ldx, ldy, ldh, part_stride;
 };
+// member mb's value array / partial sums (the kernels pass batch_member(); the fused iteration kernel runs one iterate: 0)
+CTD_HD double* hess_vals(const HParams& hp, int64_t mb) { return hp.vals + mb * hp.ldh; }
+CTD_HD double* hess_partials(const HParams& hp, int64_t mb) { return hp.partials + mb * hp.part_stride; }
 
 }  // namespace ctd

@@ -676,25 +676,25 @@ CTD_HD void hess_eval_boundary(const HParams& hp, const double* x0p, const doubl
 // have terms -- by the waves the point evaluations leave idle, at the start of the eval phase: the stores have long been
 // acknowledged when the barrier after that phase (which waits for them) is reached, so the entries written again in the
 // emit phase are ordered after them.
-CTD_HD void hess_zero_fill(const HParams& hp, const HBlockCtx& cx, int tid, int nthr) {
+CTD_HD void hess_zero_fill(const HParams& hp, const HBlockCtx& cx, int tid, int nthr, int64_t mb = 0) {
     if (hp.compact != 1 || cx.is_edge) return;
     const int64_t i0 = cx.a > hp.reg_first ? cx.a : hp.reg_first;
     const int64_t i1 = cx.b < hp.reg_last ? cx.b : hp.reg_last;
     if (i1 <= i0) return;
-    double* out0 = hp.vals + hp.seg_base + (i0 - hp.reg_first) * (int64_t)hp.Lseg;
+    double* out0 = hess_vals(hp, mb) + hp.seg_base + (i0 - hp.reg_first) * (int64_t)hp.Lseg;
     const int n = (int)(i1 - i0) * hp.Lseg, z0 = nthr > 64 ? 64 : 0;
     if (tid >= z0)
         for (int j = tid - z0; j < n; j += nthr - z0) emit_store(&out0[j], 0.0, hp.wt_store);
 }
 
 template <class P, int SC, int S>
-CTD_HD void hess_phase_eval(const HParams& hp, const HBlockCtx& cx, int tid, int nthr) {
+CTD_HD void hess_phase_eval(const HParams& hp, const HBlockCtx& cx, int tid, int nthr, int64_t mb = 0) {
     constexpr int n = P::NX, np = P::NPATH;
     constexpr HessRecLayout R = HRL<P, SC, S>::R;
     constexpr bool PATH_PT = np > 0 && SC != SC_TRAPEZE;
     constexpr int PT = R.S + (PATH_PT ? 1 : 0);
     const Layout& L = hp.L;
-    hess_zero_fill(hp, cx, tid, nthr);
+    hess_zero_fill(hp, cx, tid, nthr, mb);
     // (the coefficient products start at the LAST lane: the waves the point evaluations below leave idle take them)
     for (int w = nthr - 1 - tid; w < cx.nslots * hp.npairs; w += nthr) {
         const int k = (int)fast_div((uint32_t)w, hp.div_npairs);
@@ -830,7 +830,7 @@ CTD_HD void hess_emit_steps(const double* pa, const double* pb, const uint32_t* 
 }
 
 template <class P, int SC, int S>
-CTD_HD void hess_phase_emit(const HParams& hp, const HBlockCtx& cx, int block, int tid, int nthr) {
+CTD_HD void hess_phase_emit(const HParams& hp, const HBlockCtx& cx, int block, int tid, int nthr, int64_t mb = 0) {
     constexpr HessRecLayout R = HRL<P, SC, S>::R;
     if (cx.is_edge) {
         // (the edge blocks share the entries: an entry is a chain of dependent global loads -- index, term range, codes)
@@ -844,7 +844,7 @@ CTD_HD void hess_phase_emit(const HParams& hp, const HBlockCtx& cx, int block, i
                 const uint32_t code = hp.eterms[t];
                 acc = acc + hess_term(cx.rec, R.stride, cx.cp, hp.npairs, code, term_slot(code));
             }
-            hp.vals[hp.edge_idx[e]] = acc;
+            hess_vals(hp, mb)[hp.edge_idx[e]] = acc;
         }
         for (int e = tid; e < hp.nvv; e += nthr) {
             double acc = 0.0;
@@ -853,7 +853,7 @@ CTD_HD void hess_phase_emit(const HParams& hp, const HBlockCtx& cx, int block, i
                     const uint32_t code = hp.eterms[t];
                     acc = acc + hess_term(cx.rec, R.stride, cx.cp, hp.npairs, code, term_slot(code));
                 }
-            hp.partials[(int64_t)cx.edge_part * hp.nvv + e] = acc;
+            hess_partials(hp, mb)[(int64_t)cx.edge_part * hp.nvv + e] = acc;
         }
         return;
     }
@@ -867,7 +867,7 @@ CTD_HD void hess_phase_emit(const HParams& hp, const HBlockCtx& cx, int block, i
     // entries that have terms are walked; the positions of the others (structural zeros of the pattern) are zero-filled.
     const int nreg = (int)(i1 - i0);
     if (nreg > 0 && hp.Lseg > 0) {
-        double* out0 = hp.vals + hp.seg_base + (i0 - hp.reg_first) * (int64_t)hp.Lseg;
+        double* out0 = hess_vals(hp, mb) + hp.seg_base + (i0 - hp.reg_first) * (int64_t)hp.Lseg;
         const int nc = hp.nc;
         const int G = (nc > 0 && nc < nthr) ? nthr / nc : 1;
         const int nu = (nreg + G - 1) / G;
@@ -926,7 +926,7 @@ CTD_HD void hess_phase_emit(const HParams& hp, const HBlockCtx& cx, int block, i
 }
 
 // the tile's share of the V x V entries: its steps in step order (fixed summation order)
-CTD_HD void hess_phase_vvsum(const HParams& hp, const HBlockCtx& cx, int block, int tid, int nthr) {
+CTD_HD void hess_phase_vvsum(const HParams& hp, const HBlockCtx& cx, int block, int tid, int nthr, int64_t mb = 0) {
     if (cx.is_edge) return;
     const int ns = (int)(cx.b - cx.a);
     for (int e = tid; e < hp.nvv; e += nthr) {
@@ -937,14 +937,14 @@ CTD_HD void hess_phase_vvsum(const HParams& hp, const HBlockCtx& cx, int block, 
             acc = (((acc + r0) + r1) + r2) + r3;
         }
         for (; si < ns; ++si) acc = acc + cx.red[e * hp.T + si];
-        hp.partials[(int64_t)block * hp.nvv + e] = acc;
+        hess_partials(hp, mb)[(int64_t)block * hp.nvv + e] = acc;
     }
 }
 
 // V x V entries: sum of the per-workgroup partials in a fixed order (lane t takes workgroups t, t + nthr, ...; then a tree)
-CTD_HD double hess_finish_partial(const HParams& hp, int e, int tid, int nthr) {
+CTD_HD double hess_finish_partial(const HParams& hp, int e, int tid, int nthr, int64_t mb = 0) {
     double acc = 0.0;
-    const volatile double* part = hp.partials;       // written by other workgroups of the same launch (last-workgroup finish)
+    const volatile double* part = hess_partials(hp, mb);       // written by other workgroups of the same launch (last-workgroup finish)
     for (int b = tid; b < hp.ntiles + hp.n_edge_blocks; b += nthr) acc = acc + part[(int64_t)b * hp.nvv + e];
     return acc;
 }

@@ -59,7 +59,7 @@ __device__ __forceinline__ void hess_pin_kernargs(const HParams& hp, const doubl
 // DBG = true: diagnostics instantiation (ctd_hess_debug_stamps, env CTD_HESS_STOP); the default one holds no stamp / stop code
 template <class P, int SC, int S, bool DBG>
 __device__ __forceinline__ void hess_body(const HParams& hp, const double* __restrict__ xu, const double* __restrict__ y, int block,
-                                          double* hess_lds) {
+                                          double* hess_lds, int64_t mb = 0) {      // mb: member of a batched launch (xu, y: its own)
     hess_pin_kernargs(hp, xu, y);
     const int tid = threadIdx.x, nthr = blockDim.x;
     hess_stamp<DBG>(hp, 0);
@@ -68,7 +68,7 @@ __device__ __forceinline__ void hess_body(const HParams& hp, const double* __res
     __syncthreads();
     hess_stamp<DBG>(hp, 1);
     if (DBG && hp.debug_stop == 1) return;
-    hess_phase_eval<P, SC, S>(hp, cx, tid, nthr);
+    hess_phase_eval<P, SC, S>(hp, cx, tid, nthr, mb);
     if constexpr (hess_sums_stages(SC, S)) {
         __syncthreads();
         hess_phase_stage_sum<P, SC, S>(hp, cx, tid, nthr);
@@ -76,10 +76,10 @@ __device__ __forceinline__ void hess_body(const HParams& hp, const double* __res
     __syncthreads();
     hess_stamp<DBG>(hp, 2);
     if (DBG && hp.debug_stop == 2) return;
-    hess_phase_emit<P, SC, S>(hp, cx, block, tid, nthr);
+    hess_phase_emit<P, SC, S>(hp, cx, block, tid, nthr, mb);
     if (hp.nvv > 0) {
         __syncthreads();
-        hess_phase_vvsum(hp, cx, block, tid, nthr);
+        hess_phase_vvsum(hp, cx, block, tid, nthr, mb);
     }
     hess_stamp<DBG>(hp, 3);
     if (DBG && hp.stamps) {      // diagnostics: time until this workgroup's stores have left the CU
@@ -93,71 +93,72 @@ template <class P, int SC, int S, bool DBG>
 __global__ __launch_bounds__(kHessBlock) CTD_HESS_CAP void hess_kernel(const HParams hp, const double* __restrict__ xu,
                                                           const double* __restrict__ y) {
     extern __shared__ double hess_lds[];
-    hess_body<P, SC, S, DBG>(hp, xu, y, (int)blockIdx.x, hess_lds);
+    const int64_t mb = batch_member();          // (batched launch: the member's iterate and multipliers)
+    hess_body<P, SC, S, DBG>(hp, xu + mb * hp.ldx, y + mb * hp.ldy, (int)blockIdx.x, hess_lds, mb);
 }
 
-// V x V entries: fixed-order sum of the per-workgroup partials (one workgroup)
-__device__ __forceinline__ void hess_finish_body(const HParams& hp, double* red) {
+// V x V entries: fixed-order sum of the per-workgroup partials (one workgroup; per member of a batched launch: grid (1, batch))
+__device__ __forceinline__ void hess_finish_body(const HParams& hp, double* red, int64_t mb = 0) {
     const int tid = threadIdx.x, nthr = blockDim.x;
     for (int e = 0; e < hp.nvv; ++e) {
-        red[tid] = hess_finish_partial(hp, e, tid, nthr);
+        red[tid] = hess_finish_partial(hp, e, tid, nthr, mb);
         __syncthreads();
         for (int off = nthr >> 1; off > 0; off >>= 1) {
             if (tid < off) red[tid] = red[tid] + red[tid + off];
             __syncthreads();
         }
-        if (tid == 0 && hp.vv_idx[e] >= 0) hp.vals[hp.vv_idx[e]] = red[0];
+        if (tid == 0 && hp.vv_idx[e] >= 0) hess_vals(hp, mb)[hp.vv_idx[e]] = red[0];
         __syncthreads();
     }
 }
 template <class P>
 __global__ __launch_bounds__(kHessBlock) void hess_finish_kernel(const HParams hp) {
     __shared__ double red[kHessBlock];
-    hess_finish_body(hp, red);
+    hess_finish_body(hp, red, batch_member());
 }
 
 #if !defined(__HIPCC_RTC__)
 template <class P, int SC, int S, bool DBG>
 hipError_t launch_hess_variant_dbg(const HParams& hp, const double* xu, const double* y, size_t lds_bytes, hipStream_t st,
-                                   hipEvent_t e0, hipEvent_t e1) {
+                                   hipEvent_t e0, hipEvent_t e1, int batch) {
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)hess_kernel<P, SC, S, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
     const int grid = hp.ntiles + hp.n_edge_blocks;
-    if (e0 || e1) hipExtLaunchKernelGGL((hess_kernel<P, SC, S, DBG>), dim3(grid), dim3(kHessBlock), lds_bytes, st, e0, e1, 0, hp, xu, y);
-    else hess_kernel<P, SC, S, DBG><<<grid, kHessBlock, lds_bytes, st>>>(hp, xu, y);
-    if (hp.nvv > 0) hess_finish_kernel<P><<<1, kHessBlock, 0, st>>>(hp);
+    if (e0 || e1) hipExtLaunchKernelGGL((hess_kernel<P, SC, S, DBG>), dim3(grid, batch), dim3(kHessBlock), lds_bytes, st, e0, e1, 0, hp, xu, y);
+    else hess_kernel<P, SC, S, DBG><<<dim3(grid, batch), kHessBlock, lds_bytes, st>>>(hp, xu, y);
+    if (hp.nvv > 0) hess_finish_kernel<P><<<dim3(1, batch), kHessBlock, 0, st>>>(hp);
     return hipGetLastError();
 }
 template <class P, int SC, int S>
 hipError_t launch_hess_variant(const HParams& hp, const double* xu, const double* y, size_t lds_bytes, hipStream_t st,
-                               hipEvent_t e0, hipEvent_t e1) {
-    if (hp.stamps || hp.debug_stop) return launch_hess_variant_dbg<P, SC, S, true>(hp, xu, y, lds_bytes, st, e0, e1);
-    return launch_hess_variant_dbg<P, SC, S, false>(hp, xu, y, lds_bytes, st, e0, e1);
+                               hipEvent_t e0, hipEvent_t e1, int batch) {
+    if (hp.stamps || hp.debug_stop) return launch_hess_variant_dbg<P, SC, S, true>(hp, xu, y, lds_bytes, st, e0, e1, batch);
+    return launch_hess_variant_dbg<P, SC, S, false>(hp, xu, y, lds_bytes, st, e0, e1, batch);
 }
 
 template <class P>
 hipError_t launch_hess(const HParams& hp, const double* xu, const double* y, size_t lds_bytes, hipStream_t st, hipEvent_t e0,
-                       hipEvent_t e1) {
+                       hipEvent_t e1, int batch) {
     const int sc = hp.L.sc;
-    if (sc == SC_TRAPEZE) return launch_hess_variant<P, SC_TRAPEZE, 1>(hp, xu, y, lds_bytes, st, e0, e1);
+    if (sc == SC_TRAPEZE) return launch_hess_variant<P, SC_TRAPEZE, 1>(hp, xu, y, lds_bytes, st, e0, e1, batch);
     if (sc == SC_MIDPOINT) {      // S: controls per step (registry problems 1 - 3, as the constraint / Jacobian kernels)
-        if (hp.L.cs == 2) return launch_hess_variant<P, SC_MIDPOINT, 2>(hp, xu, y, lds_bytes, st, e0, e1);
-        if (hp.L.cs == 3) return launch_hess_variant<P, SC_MIDPOINT, 3>(hp, xu, y, lds_bytes, st, e0, e1);
+        if (hp.L.cs == 2) return launch_hess_variant<P, SC_MIDPOINT, 2>(hp, xu, y, lds_bytes, st, e0, e1, batch);
+        if (hp.L.cs == 3) return launch_hess_variant<P, SC_MIDPOINT, 3>(hp, xu, y, lds_bytes, st, e0, e1, batch);
         if (hp.L.cs > 3) return hipErrorInvalidValue;
-        return launch_hess_variant<P, SC_MIDPOINT, 1>(hp, xu, y, lds_bytes, st, e0, e1);
+        return launch_hess_variant<P, SC_MIDPOINT, 1>(hp, xu, y, lds_bytes, st, e0, e1, batch);
     }
-    if (hp.L.s == 1) return launch_hess_variant<P, SC_IRK, 1>(hp, xu, y, lds_bytes, st, e0, e1);
-    if (hp.L.s == 2) return launch_hess_variant<P, SC_IRK, 2>(hp, xu, y, lds_bytes, st, e0, e1);
-    return launch_hess_variant<P, SC_IRK, 3>(hp, xu, y, lds_bytes, st, e0, e1);
+    if (hp.L.s == 1) return launch_hess_variant<P, SC_IRK, 1>(hp, xu, y, lds_bytes, st, e0, e1, batch);
+    if (hp.L.s == 2) return launch_hess_variant<P, SC_IRK, 2>(hp, xu, y, lds_bytes, st, e0, e1, batch);
+    return launch_hess_variant<P, SC_IRK, 3>(hp, xu, y, lds_bytes, st, e0, e1, batch);
 }
 
 #define CTD_INSTANTIATE_HESS(P) \
-    template hipError_t launch_hess<P>(const HParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t);
+    template hipError_t launch_hess<P>(const HParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t, int);
 #define CTD_EXTERN_HESS(P) \
-    extern template hipError_t launch_hess<P>(const HParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t);
+    extern template hipError_t launch_hess<P>(const HParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t, int);
 
 #endif  // !__HIPCC_RTC__
 

@@ -79,6 +79,8 @@ struct SParams {
     double* partials;               // V x V partial sums per workgroup: this launch writes rows part_base + blockIdx
     int32_t part_base;
     int32_t wt_store;               // write-through value stores (HParams::wt_store)
+    // batched launches: member b = blockIdx.y writes vals + b * ldh and partials + b * part_stride (HParams::ldx / ldy: its inputs)
+    int64_t ldh, part_stride;
 };
 
 // The workgroup is ONE wave: its LDS operations execute in program order, so the transposition through LDS needs no workgroup
@@ -108,8 +110,11 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(CTD_
     constexpr int nvv = nv * (nv + 1) / 2;
     constexpr int kStepBufStride = step_buf_stride(StepFn<P, S, SW>::nout);
     extern __shared__ double lds[];       // max(edge block of the tile kernel, kStepBlock * (kStepBufStride + nvv) doubles)
+    const int64_t mb = batch_member();    // (batched launch: the member's iterate and multipliers)
+    xu += mb * hp.ldx;
+    y += mb * hp.ldy;
     if ((int)blockIdx.x < hp.n_edge_blocks) {
-        hess_body<P, SC_IRK, S, false>(hp, xu, y, (int)blockIdx.x, lds);
+        hess_body<P, SC_IRK, S, false>(hp, xu, y, (int)blockIdx.x, lds, mb);
         return;
     }
     const int wg = (int)blockIdx.x - hp.n_edge_blocks;
@@ -201,7 +206,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(CTD_
     // its latency once per window and batch of steps)
     int* lsrc = reinterpret_cast<int*>(lds + kStepBlock * kStepBufStride + kStepBlock * (nvv > 0 ? nvv : 1));
     for (int e = lane; e < sp.Lseg; e += kStepBlock) lsrc[e] = sp.src[e];
-    double* out0 = sp.vals + sp.seg_base + (i0 - sp.reg_first) * (int64_t)sp.Lseg;
+    double* out0 = sp.vals + mb * sp.ldh + sp.seg_base + (i0 - sp.reg_first) * (int64_t)sp.Lseg;
     // steps of this wave that write their segment (the regular ones)
     const int st_lo = (int)(sp.reg_lo > i0 ? (sp.reg_lo - i0 < nsw ? sp.reg_lo - i0 : nsw) : 0);
     const int st_hi = (int)(sp.reg_hi < i0 + nsw ? (sp.reg_hi > i0 ? sp.reg_hi - i0 : 0) : nsw);
@@ -253,7 +258,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(CTD_
         if (lane < nvv) {
             double acc = 0.0;
             for (int st = 0; st < nsw; ++st) acc = acc + vb[st * nvv + lane];      // step order: fixed summation order
-            sp.partials[((int64_t)sp.part_base + wg) * nvv + lane] = acc;
+            sp.partials[mb * sp.part_stride + ((int64_t)sp.part_base + wg) * nvv + lane] = acc;
         }
     }
 }
@@ -266,26 +271,26 @@ inline size_t hess_step_lds_bytes(int nout, int nv, int Lseg) {
 
 template <class P, int S, bool SW>
 hipError_t launch_hess_step_variant(const HParams& hp, const SParams& sp, const double* xu, const double* y, size_t lds_bytes, hipStream_t st,
-                                    hipEvent_t e0, hipEvent_t e1) {
+                                    hipEvent_t e0, hipEvent_t e1, int batch) {
     const int grid = hp.n_edge_blocks + (int)((sp.step_end - sp.step_begin + kStepBlock - 1) / kStepBlock);
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)hess_step_kernel<P, S, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-    if (e0 || e1) hipExtLaunchKernelGGL((hess_step_kernel<P, S, SW>), dim3(grid), dim3(kStepBlock), lds_bytes, st, e0, e1, 0, hp, sp, xu, y);
-    else hess_step_kernel<P, S, SW><<<grid, kStepBlock, lds_bytes, st>>>(hp, sp, xu, y);
-    if (hp.nvv > 0) hess_finish_kernel<P><<<1, kHessBlock, 0, st>>>(hp);
+    if (e0 || e1) hipExtLaunchKernelGGL((hess_step_kernel<P, S, SW>), dim3(grid, batch), dim3(kStepBlock), lds_bytes, st, e0, e1, 0, hp, sp, xu, y);
+    else hess_step_kernel<P, S, SW><<<dim3(grid, batch), kStepBlock, lds_bytes, st>>>(hp, sp, xu, y);
+    if (hp.nvv > 0) hess_finish_kernel<P><<<dim3(1, batch), kHessBlock, 0, st>>>(hp);
     return hipGetLastError();
 }
 // hp: the tile kernel's parameters with n_edge_blocks edge workgroups of kStepBlock lanes and ntiles = the number of step
 // workgroups (the finish kernel adds that many partials)
 template <class P>
 hipError_t launch_hess_step(const HParams& hp, const SParams& sp, const double* xu, const double* y, size_t lds_bytes, hipStream_t st,
-                            hipEvent_t e0, hipEvent_t e1) {
+                            hipEvent_t e0, hipEvent_t e1, int batch) {
     if constexpr (StepOK<P>::value) {
         const bool sw = sp.L.stagewise != 0;
-        if (sp.L.s == 2) return sw ? launch_hess_step_variant<P, 2, true>(hp, sp, xu, y, lds_bytes, st, e0, e1) : launch_hess_step_variant<P, 2, false>(hp, sp, xu, y, lds_bytes, st, e0, e1);
-        if (sp.L.s == 3) return sw ? launch_hess_step_variant<P, 3, true>(hp, sp, xu, y, lds_bytes, st, e0, e1) : launch_hess_step_variant<P, 3, false>(hp, sp, xu, y, lds_bytes, st, e0, e1);
+        if (sp.L.s == 2) return sw ? launch_hess_step_variant<P, 2, true>(hp, sp, xu, y, lds_bytes, st, e0, e1, batch) : launch_hess_step_variant<P, 2, false>(hp, sp, xu, y, lds_bytes, st, e0, e1, batch);
+        if (sp.L.s == 3) return sw ? launch_hess_step_variant<P, 3, true>(hp, sp, xu, y, lds_bytes, st, e0, e1, batch) : launch_hess_step_variant<P, 3, false>(hp, sp, xu, y, lds_bytes, st, e0, e1, batch);
     }
     return hipErrorInvalidValue;
 }
@@ -299,10 +304,10 @@ template <class P> const short* hess_step_pairs(int s, bool stagewise, int* nout
     return nullptr;
 }
 #define CTD_INSTANTIATE_HESS_STEP(P) \
-    template hipError_t launch_hess_step<P>(const HParams&, const SParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t); \
+    template hipError_t launch_hess_step<P>(const HParams&, const SParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t, int); \
     template const short* hess_step_pairs<P>(int, bool, int*);
 #define CTD_EXTERN_HESS_STEP(P) \
-    extern template hipError_t launch_hess_step<P>(const HParams&, const SParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t); \
+    extern template hipError_t launch_hess_step<P>(const HParams&, const SParams&, const double*, const double*, size_t, hipStream_t, hipEvent_t, hipEvent_t, int); \
     extern template const short* hess_step_pairs<P>(int, bool, int*);
 #endif
 

@@ -1151,6 +1151,12 @@ CTD_HD void emit_store(double* p, double v, int wt = 0) {
     *p = v;
 }
 
+// the outputs a workgroup writes: kp.c / kp.vals, or (B: batched launch) its member's rows of them (null when the output is skipped).
+// Read at each use like the plain field: a local copy made once per phase moved the loads and changed the registers of the
+// single-iterate kernels.
+template <bool B> CTD_HD double* out_c(const KParams& kp, const BatchLd& bl) { return member_out<B>(kp.c, bl.ldc); }
+template <bool B> CTD_HD double* out_vals(const KParams& kp, const BatchLd& bl) { return member_out<B>(kp.vals, bl.ldv); }
+
 // NB > 1 (long periods, e.g. 2904 codes per step for the 12-state quadrotor on Gauss-Legendre 3): more[q] = the code of position
 // tid + (q + 1) nthr -- ALL the positions a lane walks, fetched before the evaluation.  Read one position ahead inside the emit
 // loop instead, every code load queued behind the workgroups' own stores (microseconds under a full store queue): the emit phase
@@ -1163,8 +1169,8 @@ template <int NB> struct EmitPreT { uint32_t b; uint32_t v[kMaxNV]; int64_t eidx
 using EmitPre = EmitPreT<1>;     // edge block: b = the code of edge entry `tid`, eidx its index
 // Early emission (KParams::pos): the lead wave of a Gauss-Legendre tile stores the outputs that only read what its own lead tasks
 // wrote -- lane l owns one early output of every step of the tile -- while the other waves still evaluate the dynamics
-template <class P, int SC, int S, int NB>
-CTD_HD void early_emit(const KParams& kp, const BlockCtx& cx, int l, const EmitPreT<NB>& pre) {
+template <class P, int SC, int S, int NB, bool B = false>
+CTD_HD void early_emit(const KParams& kp, const BlockCtx& cx, int l, const EmitPreT<NB>& pre, const BatchLd bl = BatchLd{}) {
     constexpr RecLayout R = RL<P, SC, S>::R;
     const int stride = R.stride;
     const int nsteps = (int)(cx.b - cx.a), slot0 = (int)(cx.a - cx.lo);
@@ -1180,7 +1186,7 @@ CTD_HD void early_emit(const KParams& kp, const BlockCtx& cx, int l, const EmitP
         const int sl0 = (int)(ra - cx.lo);
         const double* pc = cx.rec + sl0 * stride + R.oC + code_ci(code);
         const double* pd = cx.rec + sl0 * stride + code_di(code);
-        double* out = kp.vals + kp.seg_base + (ra - kp.reg_first) * (int64_t)kp.Lseg + pre.ek;
+        double* out = out_vals<B>(kp, bl) + kp.seg_base + (ra - kp.reg_first) * (int64_t)kp.Lseg + pre.ek;
         const int last = nreg - 1;
         for (int s0 = 0; s0 < nreg; s0 += 4) {
             double a[4], b[4];
@@ -1197,7 +1203,7 @@ CTD_HD void early_emit(const KParams& kp, const BlockCtx& cx, int l, const EmitP
     } else if (l < ne + nc) {                       // a state row of c
         if (!kp.c) return;
         const int r = l - ne;
-        double* out = kp.c + cx.a * (int64_t)kp.L.cb + r;
+        double* out = out_c<B>(kp, bl) + cx.a * (int64_t)kp.L.cb + r;
         const double* src = cx.rec + slot0 * stride + R.oR + r;
         for (int s = 0; s < nsteps; ++s) emit_store(&out[s * kp.L.cb], src[s * stride], kp.wt_store);
     } else if (l < ne + nc + P::NV * vre) {         // d(state row) / dv of a V column
@@ -1206,7 +1212,7 @@ CTD_HD void early_emit(const KParams& kp, const BlockCtx& cx, int l, const EmitP
         const uint32_t code = pre.eb;
         const double* pc = cx.rec + slot0 * stride + R.oC + code_ci(code);
         const double* pd = cx.rec + slot0 * stride + code_di(code);
-        double* out = kp.vals + kp.vcol_base[kk] + cx.a * (int64_t)kp.vr + pre.ek;
+        double* out = out_vals<B>(kp, bl) + kp.vcol_base[kk] + cx.a * (int64_t)kp.vr + pre.ek;
         for (int s = 0; s < nsteps; ++s) emit_store(&out[s * kp.vr], pc[s * stride] * pd[s * stride], kp.wt_store);
     }
 }
@@ -1219,8 +1225,9 @@ template <class P, int SC, int S> CTD_HD int early_leadbase(const KParams& kp) {
     return (((r_dyn + r_path) << lgT) + 63) & ~63;
 }
 
-template <class P, int SC, int S, bool REG = false, int NB = 1>
-CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* epre = nullptr) {
+template <class P, int SC, int S, bool REG = false, int NB = 1, bool B = false>
+CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* epre = nullptr,
+                       const BatchLd bl = BatchLd{}) {
     constexpr bool FUSED = Dirs<P>::FUSED;
     constexpr RecLayout R = RL<P, SC, S>::R;
     const int ns = cx.nslots;
@@ -1411,7 +1418,7 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the wave's LDS writes before its LDS reads below
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                early_emit<P, SC, S, NB>(kp, cx, tid & 63, *epre);
+                early_emit<P, SC, S, NB, B>(kp, cx, tid & 63, *epre, bl);
 #endif
                 // (the serial emulator of tests/emu steps the lanes one after the other: it calls early_emit for the lead wave
                 // once every lane has run this phase)
@@ -1609,8 +1616,9 @@ CTD_HD EmitPreT<NB> emit_prefetch(const KParams& kp, const BlockCtx& cx, int tid
     return pre;
 }
 
-template <class P, int SC, int S, int NB = 1>
-CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB> pre_v, const bool hp) {
+template <class P, int SC, int S, int NB = 1, bool B = false>
+CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB> pre_v, const bool hp,
+                            const BatchLd bl = BatchLd{}) {
     const Layout& L = kp.L;
     constexpr RecLayout R = RL<P, SC, S>::R;
     const EmitPreT<NB>* pre_ = &pre_v;                     // hp: the lane's codes were prefetched (pre_v holds them)
@@ -1634,8 +1642,8 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
             for (int u = 0; u < 4; ++u) {
                 if (w0 + u * nthr >= ntot) break;
                 const double val = eval_code(R.oC, cx.rec + code_crec(code[u]) * R.stride, cx.rec + code_drec_raw(code[u]) * R.stride, code[u]);
-                if (idx[u] & kEdgeCBit) { if (kp.c) kp.c[idx[u] & ~kEdgeCBit] = val; }
-                else if (kp.vals) kp.vals[idx[u]] = val;
+                if (idx[u] & kEdgeCBit) { if (kp.c) out_c<B>(kp, bl)[idx[u] & ~kEdgeCBit] = val; }
+                else if (kp.vals) out_vals<B>(kp, bl)[idx[u]] = val;
             }
         }
         return;
@@ -1651,7 +1659,7 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
     // (A) constraint rows of the tile: c[a*cb .. b*cb)
     if (kp.c) {
         const int cb = L.cb;
-        double* out = kp.c + cx.a * (int64_t)cb;
+        double* out = out_c<B>(kp, bl) + cx.a * (int64_t)cb;
         const int par = (int)fast_div((uint32_t)nthr, kp.div_cb);
         if (par >= 1) {
             if (tid < par * cb) {
@@ -1676,7 +1684,7 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
         if (rb > ra) {
             const int Ls = kp.Lseg;
             const int nreg = (int)(rb - ra);
-            double* out = kp.vals + kp.seg_base + (ra - kp.reg_first) * (int64_t)Ls;
+            double* out = out_vals<B>(kp, bl) + kp.seg_base + (ra - kp.reg_first) * (int64_t)Ls;
             const int sl0 = (int)(ra - cx.lo);
             // early emission: only the late positions are left (kp.pos[0 .. n_late)), more steps in flight per pass
             const bool late_only = kp.n_early > 0;
@@ -1756,7 +1764,7 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
         const int par = (int)fast_div((uint32_t)nthr, kp.div_vr);
 #pragma unroll
         for (int kk = 0; kk < P::NV; ++kk) {
-            double* out = kp.vals + kp.vcol_base[kk] + cx.a * (int64_t)vr;
+            double* out = out_vals<B>(kp, bl) + kp.vcol_base[kk] + cx.a * (int64_t)vr;
             const uint32_t* codes = cx.vcodes + kk * vr;
             if (par >= 1) {
                 if (tid < par * vr) {
@@ -1781,10 +1789,11 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
     CTD_SUBE(kp, 3);
 }
 // (pointer form: the drivers that always prefetch, and the emulator)
-template <class P, int SC, int S, int NB = 1>
-CTD_HD void phase_emit(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* pre = nullptr) {
-    if (pre != nullptr) phase_emit_impl<P, SC, S, NB>(kp, cx, tid, nthr, *pre, pre->have != 0);
-    else phase_emit_impl<P, SC, S, NB>(kp, cx, tid, nthr, EmitPreT<NB>{}, false);
+template <class P, int SC, int S, int NB = 1, bool B = false>
+CTD_HD void phase_emit(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* pre = nullptr,
+                       const BatchLd bl = BatchLd{}) {
+    if (pre != nullptr) phase_emit_impl<P, SC, S, NB, B>(kp, cx, tid, nthr, *pre, pre->have != 0, bl);
+    else phase_emit_impl<P, SC, S, NB, B>(kp, cx, tid, nthr, EmitPreT<NB>{}, false, bl);
 }
 
 }  // namespace ctd

@@ -68,9 +68,14 @@ __device__ __forceinline__ void ctd_pin_emit_kernargs(const KParams& kp) {
 #endif
 }
 
-// workgroup `block` of the evaluation (the kernel below; also a branch of the fused iteration kernel, ctd_iter_kernels.hpp)
-template <class P, int SC, int S, bool DBG>
-__device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* __restrict__ xu, int block, double* ctd_lds) {
+// workgroup `block` of the evaluation (the kernel below; also a branch of the fused iteration kernel, ctd_iter_kernels.hpp).
+// B = true: the batched kernel (cons_jac_batch_kernel) -- the workgroup evaluates member blockIdx.y of the batch: its iterate at
+// xu + blockIdx.y * ldx, its outputs at c + blockIdx.y * ldc, vals + blockIdx.y * ldv (BatchLd, member_out); the tiles, edge
+// blocks and every table are the handle's, shared by the members.  B = false compiles none of it.
+template <class P, int SC, int S, bool DBG, bool B = false>
+__device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* __restrict__ xu, int block, double* ctd_lds,
+                                              const BatchLd bl = BatchLd{}) {
+    if constexpr (B) xu += batch_member() * bl.ldx;
     ctd_pin_kernargs<SC == SC_IRK ? S : 0>(kp, xu);
     ctd_stamp<DBG>(kp, 0);
     if (DBG && kp.debug_stop == 1) return;
@@ -80,13 +85,13 @@ __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* _
         const BlockCtx cx = make_direct_ctx(kp, block, ctd_lds, xu);
         const EmitPre pre = emit_prefetch<P>(kp, cx, tid, nthr);
         ctd_stamp<DBG>(kp, 1);
-        phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1>(kp, cx, tid, nthr, &pre);
+        phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1, B>(kp, cx, tid, nthr, &pre, bl);
         ctd_pin_emit_kernargs(kp);
         __syncthreads();
         ctd_stamp<DBG>(kp, 2);
         ctd_stamp<DBG>(kp, 3);
         if (DBG && kp.debug_stop >= 2 && kp.debug_stop <= 4) return;
-        phase_emit<P, SC, S>(kp, cx, tid, nthr, &pre);
+        phase_emit<P, SC, S, 1, B>(kp, cx, tid, nthr, &pre, bl);
         ctd_stamp<DBG>(kp, 4);
         if (DBG && kp.stamps) {
             __builtin_amdgcn_s_waitcnt(0);
@@ -115,7 +120,7 @@ __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* _
         __syncthreads();
         ctd_stamp<DBG>(kp, 1);
         if (DBG && kp.debug_stop == 2) return;
-        phase_eval<P, SC, S>(kp, cx, tid, nthr);
+        phase_eval<P, SC, S, false, 1, B>(kp, cx, tid, nthr, nullptr, bl);
         ctd_pin_emit_kernargs(kp);
         __syncthreads();
         ctd_stamp<DBG>(kp, 2);
@@ -138,7 +143,7 @@ __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* _
             nx = make_ctx(kp, block, ctd_lds);
             tin = load_issue<P>(kp, nx, xu, tid, nthr);
         }
-        phase_emit_impl<P, SC, S, NB>(kp, cx, tid, nthr, pre, use_pre);
+        phase_emit_impl<P, SC, S, NB, B>(kp, cx, tid, nthr, pre, use_pre, bl);
         ctd_stamp<DBG>(kp, 4);
         if (!more) break;
         load_commit<P, SC, S>(kp, nx, xu, tin, tid, nthr);
@@ -163,6 +168,13 @@ template <class P, int SC, int S, bool DBG>
 __global__ void __launch_bounds__(P::MAXB, (MinWaves<P, SC, S>::value)) cons_jac_kernel(const KParams kp, const double* __restrict__ xu) {
     extern __shared__ double ctd_lds[];
     cons_jac_body<P, SC, S, DBG>(kp, xu, (int)blockIdx.x, ctd_lds);
+}
+// K iterates per launch (ctd_cons_jac_batch_dev_async): grid (tiles, members), the same bodies with B = true
+template <class P, int SC, int S>
+__global__ void __launch_bounds__(P::MAXB, (MinWaves<P, SC, S>::value)) cons_jac_batch_kernel(const KParams kp, const double* __restrict__ xu,
+                                                                                          const BatchLd bl) {
+    extern __shared__ double ctd_lds[];
+    cons_jac_body<P, SC, S, false, true>(kp, xu, (int)blockIdx.x, ctd_lds, bl);
 }
 
 // EXPERIMENT build only (make EXTRA=-DCTD_KP_INDIRECT; VERDICT r03 item 7 ii): the 640-byte parameter block lives in device memory
@@ -193,6 +205,8 @@ struct ObjParams {
     // and X_1 / X_{N+1} of the Mayer term come from the owners' buffers; null: xu holds everything
     const XHalo* halo;
     XNear near;             // (the same buffers in the kernel arguments: one memory round trip per remote entry)
+    // batched launches (ctd_obj_batch_dev_async): member b = blockIdx.y reads xu + b * ldx, writes partial[b * nblocks ..] and out[b]
+    int64_t ldx;
 };
 
 template <class P> __device__ double obj_time(const ObjParams& op, const double* v, int64_t i) {
@@ -260,9 +274,10 @@ __device__ double lagrange_unit(const ObjParams& op, const double* __restrict__ 
 }
 
 // body of the quadrature pass for workgroup `block` of `nblocks` (wsum: 4+ doubles of LDS); also a branch of the fused
-// iteration kernel (iter_main_kernel)
+// iteration kernel (iter_main_kernel).  mb: member of a batched launch (xu is already the member's iterate)
 template <class P, int SC>
-__device__ __forceinline__ void obj_partial_body(const ObjParams& op, const double* __restrict__ xu, int block, int nblocks, double* wsum) {
+__device__ __forceinline__ void obj_partial_body(const ObjParams& op, const double* __restrict__ xu, int block, int nblocks, double* wsum,
+                                                 int64_t mb = 0) {
     double v[P::NV > 0 ? P::NV : 1];
     for (int k = 0; k < P::NV; ++k) v[k] = xu[op.L.v_off + k];
     double acc = 0.0;
@@ -278,22 +293,24 @@ __device__ __forceinline__ void obj_partial_body(const ObjParams& op, const doub
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += wsum[w];
-        op.partial[block] = s;
+        op.partial[mb * nblocks + block] = s;
     }
 }
 template <class P, int SC>
 __global__ void __launch_bounds__(256) obj_partial_kernel(const ObjParams op, const double* __restrict__ xu) {
     __shared__ double wsum[4];
-    obj_partial_body<P, SC>(op, xu, (int)blockIdx.x, (int)gridDim.x, wsum);
+    const int64_t mb = batch_member();
+    obj_partial_body<P, SC>(op, xu + mb * op.ldx, (int)blockIdx.x, (int)gridDim.x, wsum, mb);
 }
 
 template <class P>
-__device__ __forceinline__ void obj_finish_body(const ObjParams& op, const double* __restrict__ xu) {
+__device__ __forceinline__ void obj_finish_body(const ObjParams& op, const double* __restrict__ xu, int64_t mb = 0) {
     if (threadIdx.x >= 64) return;
     // one wave: lane l adds the partials l, l + 64, ... in index order, then a fixed shuffle tree (deterministic; the
     // loads of the 64 lanes are in flight together instead of one dependent chain of nblocks loads)
+    const double* part = op.partial + mb * op.nblocks;
     double s = 0.0;
-    for (int b = threadIdx.x; b < op.nblocks; b += 64) s += op.partial[b];
+    for (int b = threadIdx.x; b < op.nblocks; b += 64) s += part[b];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if (threadIdx.x != 0) return;
     double mayer = 0.0;
@@ -307,12 +324,14 @@ __device__ __forceinline__ void obj_finish_body(const ObjParams& op, const doubl
         for (int k = 0; k < nv; ++k) v[k] = xu[op.L.v_off + k];
         mayer = P::template mayer<double>(x0, xf, v);
     }
-    op.out[0] = mayer + s;
+    op.out[mb] = mayer + s;
 }
+// (one workgroup per member of a batched launch: grid (1, batch))
 template <class P>
 __global__ void obj_finish_kernel(const ObjParams op, const double* __restrict__ xu) {
     if (blockIdx.x != 0) return;
-    obj_finish_body<P>(op, xu);
+    const int64_t mb = batch_member();
+    obj_finish_body<P>(op, xu + mb * op.ldx, mb);
 }
 
 // ---- objective gradient: grad!(nlp, x, g) -----------------------------------------------------------------------------
@@ -334,6 +353,9 @@ struct GradParams {
     // sharded iterate read in place (ctd_set_x_shards): blocks of other shards come from their owners' buffers; null: xu holds everything
     const XHalo* halo;
     XNear near;
+    // batched launches (ctd_grad_batch_dev_async): member b = blockIdx.y reads xu + b * ldx, writes g + b * ldg and the partial
+    // rows [b * nblocks, (b + 1) * nblocks)
+    int64_t ldx, ldg;
 };
 // start of the variable block of step / node `st` in the buffer that owns it
 CTD_HD const double* grad_block(const GradParams& gp, const double* xu, int64_t st) {
@@ -451,9 +473,11 @@ template <class P> __device__ __forceinline__ double grad_time(const GradParams&
     return t0 + tau * (tf - t0);
 }
 
-// body of the gradient pass for workgroup `block` (wsum: 4 * kMaxNV doubles of LDS); also a branch of iter_main_kernel
+// body of the gradient pass for workgroup `block` (wsum: 4 * kMaxNV doubles of LDS); also a branch of iter_main_kernel.
+// mb: member of a batched launch (xu is already the member's iterate)
 template <class P, int SC, int S>
-__device__ __forceinline__ void grad_units_body(const GradParams& gp, const double* __restrict__ xu, int block, double (*wsum)[kMaxNV]) {
+__device__ __forceinline__ void grad_units_body(const GradParams& gp, const double* __restrict__ xu, int block, double (*wsum)[kMaxNV],
+                                                int64_t mb = 0) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV;
     constexpr bool FREE = (P::IT0 >= 0) || (P::ITF >= 0);
     const Layout& L = gp.L;
@@ -461,7 +485,7 @@ __device__ __forceinline__ void grad_units_body(const GradParams& gp, const doub
     for (int k = 0; k < nv; ++k) { v[k] = xu[L.v_off + k]; gv[k] = 0.0; }
     const int64_t i = gp.unit_begin + (int64_t)block * blockDim.x + threadIdx.x;      // step, or node for trapeze / midpoint
     if (P::HAS_LAGRANGE && i < gp.unit_end) {
-        double* g = gp.g;
+        double* g = gp.g + mb * gp.ldg;
         const double* base = grad_block(gp, xu, i);
         const double* nextb = (SC == SC_MIDPOINT && i < L.N) ? grad_block(gp, xu, i + 1) : base;      // X_{i+1}: the next shard's for a shard's last node
         double x[n > 0 ? n : 1], u[m > 0 ? m : 1], lx[n > 0 ? n : 1], lu[m > 0 ? m : 1], lv[nv > 0 ? nv : 1];
@@ -605,24 +629,27 @@ __device__ __forceinline__ void grad_units_body(const GradParams& gp, const doub
         for (int k = 0; k < nv; ++k) {
             double sacc = 0.0;
             for (int w = 0; w < (int)(blockDim.x >> 6); ++w) sacc += wsum[w][k];
-            gp.partial[(size_t)block * kMaxNV + k] = sacc;
+            gp.partial[((size_t)mb * gp.nblocks + block) * kMaxNV + k] = sacc;
         }
 }
 template <class P, int SC, int S>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) grad_units_kernel(const GradParams gp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    grad_units_body<P, SC, S>(gp, xu, (int)blockIdx.x, wsum);
+    const int64_t mb = batch_member();
+    grad_units_body<P, SC, S>(gp, xu + mb * gp.ldx, (int)blockIdx.x, wsum, mb);
 }
 
 template <class P>
-__device__ __forceinline__ void grad_finish_body(const GradParams& gp, const double* __restrict__ xu) {
+__device__ __forceinline__ void grad_finish_body(const GradParams& gp, const double* __restrict__ xu, int64_t mb = 0) {
     if (threadIdx.x >= 64) return;
     constexpr int n = P::NX, nv = P::NV;
     const Layout& L = gp.L;
+    const double* part = gp.partial + (size_t)mb * gp.nblocks * kMaxNV;
+    double* const g = gp.g + mb * gp.ldg;
     double gvs[nv > 0 ? nv : 1];
     for (int k = 0; k < nv; ++k) {          // one wave, fixed order (see obj_finish_kernel)
         double sacc = 0.0;
-        for (int b = threadIdx.x; b < gp.nblocks; b += 64) sacc += gp.partial[(size_t)b * kMaxNV + k];
+        for (int b = threadIdx.x; b < gp.nblocks; b += 64) sacc += part[(size_t)b * kMaxNV + k];
         for (int off = 32; off > 0; off >>= 1) sacc += __shfl_down(sacc, off, 64);
         gvs[k] = sacc;
     }
@@ -635,29 +662,33 @@ __device__ __forceinline__ void grad_finish_body(const GradParams& gp, const dou
         for (int k = 0; k < nv; ++k) { v[k] = xu[L.v_off + k]; gmv[k] = 0.0; }
         mayer_partials<P, 0>(x0, xf, v, g0x, gfx, gmv);
         for (int c = 0; c < n; ++c) {
-            if (gp.owns_first) gp.g[c] += g0x[c];
-            if (gp.owns_last) gp.g[L.N * (int64_t)L.blk + c] += gfx[c];
+            if (gp.owns_first) g[c] += g0x[c];
+            if (gp.owns_last) g[L.N * (int64_t)L.blk + c] += gfx[c];
         }
         if (gp.owns_last) for (int k = 0; k < nv; ++k) gvs[k] += gmv[k];
     }
-    for (int k = 0; k < nv; ++k) gp.g[L.v_off + k] = gvs[k];
+    for (int k = 0; k < nv; ++k) g[L.v_off + k] = gvs[k];
 }
+// (one workgroup per member of a batched launch: grid (1, batch))
 template <class P>
 __global__ void grad_finish_kernel(const GradParams gp, const double* __restrict__ xu) {
     if (blockIdx.x != 0) return;
-    grad_finish_body<P>(gp, xu);
+    const int64_t mb = batch_member();
+    grad_finish_body<P>(gp, xu + mb * gp.ldx, mb);
 }
 
 #if !defined(__HIPCC_RTC__)
+// batch: members of a batched launch (the grid's second dimension; 1 for one iterate)
 template <class P>
-hipError_t launch_grad(int sc, int s, const GradParams& gp, const double* xu, int grid, hipStream_t st) {
+hipError_t launch_grad(int sc, int s, const GradParams& gp, const double* xu, int grid, hipStream_t st, int batch) {
+    const dim3 g(grid > 0 ? grid : 1, batch);
     if (grid <= 0) {}      // Mayer-only cost: nothing to integrate
-    else if (sc == SC_TRAPEZE) grad_units_kernel<P, SC_TRAPEZE, 1><<<grid, 256, 0, st>>>(gp, xu);
-    else if (sc == SC_MIDPOINT) grad_units_kernel<P, SC_MIDPOINT, 1><<<grid, 256, 0, st>>>(gp, xu);
-    else if (s == 1) grad_units_kernel<P, SC_IRK, 1><<<grid, 256, 0, st>>>(gp, xu);
-    else if (s == 2) grad_units_kernel<P, SC_IRK, 2><<<grid, 256, 0, st>>>(gp, xu);
-    else grad_units_kernel<P, SC_IRK, 3><<<grid, 256, 0, st>>>(gp, xu);
-    grad_finish_kernel<P><<<1, 64, 0, st>>>(gp, xu);
+    else if (sc == SC_TRAPEZE) grad_units_kernel<P, SC_TRAPEZE, 1><<<g, 256, 0, st>>>(gp, xu);
+    else if (sc == SC_MIDPOINT) grad_units_kernel<P, SC_MIDPOINT, 1><<<g, 256, 0, st>>>(gp, xu);
+    else if (s == 1) grad_units_kernel<P, SC_IRK, 1><<<g, 256, 0, st>>>(gp, xu);
+    else if (s == 2) grad_units_kernel<P, SC_IRK, 2><<<g, 256, 0, st>>>(gp, xu);
+    else grad_units_kernel<P, SC_IRK, 3><<<g, 256, 0, st>>>(gp, xu);
+    grad_finish_kernel<P><<<dim3(1, batch), 64, 0, st>>>(gp, xu);
     return hipGetLastError();
 }
 
@@ -732,6 +763,32 @@ int occupancy_variant(int block, size_t lds_bytes) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cons_jac_kernel<P, SC, S, false>, block, lds_bytes) != hipSuccess) return 0;
     return nb;
 }
+// Batched launch (ctd_cons_jac_batch_dev_async): cons_jac_batch_kernel on grid (grid, batch)
+template <class P, int SC, int S>
+hipError_t launch_variant_batch(const KParams& kp, const double* xu, const BatchLd& bl, int grid, int block, size_t lds_bytes, hipStream_t st,
+                                int batch) {
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)cons_jac_batch_kernel<P, SC, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    cons_jac_batch_kernel<P, SC, S><<<dim3(grid, batch), block, lds_bytes, st>>>(kp, xu, bl);
+    return hipGetLastError();
+}
+template <class P>
+hipError_t launch_cons_jac_batch(int sc, const KParams& kp, const double* xu, const BatchLd& bl, int grid, int block, size_t lds_bytes,
+                                 hipStream_t st, int batch) {
+    if (sc == SC_TRAPEZE) return launch_variant_batch<P, SC_TRAPEZE, 1>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+    if (sc == SC_MIDPOINT) {
+        if (kp.L.cs == 2) return launch_variant_batch<P, SC_MIDPOINT, 2>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+        if (kp.L.cs == 3) return launch_variant_batch<P, SC_MIDPOINT, 3>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+        if (kp.L.cs > 3) return hipErrorInvalidValue;
+        return launch_variant_batch<P, SC_MIDPOINT, 1>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+    }
+    if (kp.L.s == 1) return launch_variant_batch<P, SC_IRK, 1>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+    if (kp.L.s == 2) return launch_variant_batch<P, SC_IRK, 2>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+    return launch_variant_batch<P, SC_IRK, 3>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+}
+
 template <class P>
 int occupancy_cons_jac(int sc, const KParams& kp, int block, size_t lds_bytes) {
     if (sc == SC_TRAPEZE) return occupancy_variant<P, SC_TRAPEZE, 1>(block, lds_bytes);
@@ -746,27 +803,31 @@ int occupancy_cons_jac(int sc, const KParams& kp, int block, size_t lds_bytes) {
 }
 
 template <class P>
-hipError_t launch_obj(int sc, const ObjParams& op, const double* xu, int grid, int block, hipStream_t st) {
+hipError_t launch_obj(int sc, const ObjParams& op, const double* xu, int grid, int block, hipStream_t st, int batch) {
+    const dim3 g(grid > 0 ? grid : 1, batch);
     if (grid <= 0) {}      // Mayer-only cost: nothing to integrate
-    else if (sc == SC_TRAPEZE) obj_partial_kernel<P, SC_TRAPEZE><<<grid, block, 0, st>>>(op, xu);
-    else if (sc == SC_MIDPOINT) obj_partial_kernel<P, SC_MIDPOINT><<<grid, block, 0, st>>>(op, xu);
-    else obj_partial_kernel<P, SC_IRK><<<grid, block, 0, st>>>(op, xu);
-    obj_finish_kernel<P><<<1, 64, 0, st>>>(op, xu);
+    else if (sc == SC_TRAPEZE) obj_partial_kernel<P, SC_TRAPEZE><<<g, block, 0, st>>>(op, xu);
+    else if (sc == SC_MIDPOINT) obj_partial_kernel<P, SC_MIDPOINT><<<g, block, 0, st>>>(op, xu);
+    else obj_partial_kernel<P, SC_IRK><<<g, block, 0, st>>>(op, xu);
+    obj_finish_kernel<P><<<dim3(1, batch), 64, 0, st>>>(op, xu);
     return hipGetLastError();
 }
 
 #define CTD_INSTANTIATE_LAUNCHERS(P)                                                                                       \
     template hipError_t launch_cons_jac<P>(int, const KParams&, const double*, int, int, size_t, hipStream_t, hipEvent_t, \
                                            hipEvent_t);                                                                    \
-    template hipError_t launch_obj<P>(int, const ObjParams&, const double*, int, int, hipStream_t);                       \
+    template hipError_t launch_cons_jac_batch<P>(int, const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, int); \
+    template hipError_t launch_obj<P>(int, const ObjParams&, const double*, int, int, hipStream_t, int);                  \
     template int occupancy_cons_jac<P>(int, const KParams&, int, size_t);                                                 \
-    template hipError_t launch_grad<P>(int, int, const GradParams&, const double*, int, hipStream_t);
+    template hipError_t launch_grad<P>(int, int, const GradParams&, const double*, int, hipStream_t, int);
 #define CTD_EXTERN_LAUNCHERS(P)                                                                                            \
     extern template hipError_t launch_cons_jac<P>(int, const KParams&, const double*, int, int, size_t, hipStream_t,      \
                                                   hipEvent_t, hipEvent_t);                                                 \
-    extern template hipError_t launch_obj<P>(int, const ObjParams&, const double*, int, int, hipStream_t);               \
+    extern template hipError_t launch_cons_jac_batch<P>(int, const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, \
+                                                        int);                                                                      \
+    extern template hipError_t launch_obj<P>(int, const ObjParams&, const double*, int, int, hipStream_t, int);          \
     extern template int occupancy_cons_jac<P>(int, const KParams&, int, size_t);                                         \
-    extern template hipError_t launch_grad<P>(int, int, const GradParams&, const double*, int, hipStream_t);
+    extern template hipError_t launch_grad<P>(int, int, const GradParams&, const double*, int, hipStream_t, int);
 
 #endif  // !__HIPCC_RTC__
 

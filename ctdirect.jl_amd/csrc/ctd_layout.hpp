@@ -287,5 +287,11 @@ struct KParams {
     int32_t wg_stride;
     int32_t wt_store;       // 1: the emit phase's stores are write-through (sc1): small launches, see emit_store (ctd_kernel_body.hpp)
 };
+// BATCHED launches (ctd_cons_jac_batch_dev_async, cons_jac_batch_kernel): workgroup (x, y) evaluates tile x of member y, which reads
+// xu + y * ldx and writes c + y * ldc, vals + y * ldv (leading dimensions in doubles).  A kernel argument of the batched kernel
+// only: the single-iterate kernel's argument block stays as it is (its size is part of every launch)
+struct BatchLd {
+    int64_t ldx, ldc, ldv;
+};
 
 }  // namespace ctd

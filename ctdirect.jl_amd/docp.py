@@ -472,6 +472,79 @@ class DOCP:
         if sync:
             self.sync()
 
+    # ---- batched callbacks: K iterates of this transcription per launch -----------------------------------------
+    def _batch_rows(self, t, n, name, k=None):
+        """A (K, n) float64 device tensor whose rows are contiguous (stride(1) == 1) on the handle's GPU, as (pointer, K, leading
+        dimension = stride(0)): row slices of wider buffers are fine.  NumPy arrays are refused -- there is no host batch path."""
+        if not _is_tensor(t):
+            raise TypeError(f"{name}: the batched callbacks take a (K, {n}) torch device tensor, not {type(t).__name__} "
+                            "(there is no host batch path)")
+        import torch
+        if not (t.is_cuda and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == n and t.shape[0] >= 1
+                and (t.stride(1) == 1 or n == 1) and t.stride(0) >= n):
+            raise ValueError(f"{name} must be a (K, {n}) float64 tensor on the handle's GPU with contiguous rows (stride(1) == 1), "
+                             f"got shape {tuple(t.shape)}, strides {tuple(t.stride())}, dtype {t.dtype}")
+        if t.device.index != self.device:
+            raise ValueError(f"{name} lives on cuda:{t.device.index}, handle is bound to device {self.device}")
+        if k is not None and t.shape[0] != k:
+            raise ValueError(f"{name} has {t.shape[0]} rows, X has {k}")
+        return C.c_void_p(t.data_ptr()), int(t.shape[0]), int(t.stride(0))
+
+    def _batch_out(self, t, x, n, name, k):
+        import torch
+        if t is None:
+            return torch.empty((k, n), dtype=torch.float64, device=x.device)
+        self._batch_rows(t, n, name, k)
+        return t
+
+    def cons_jac_batch(self, X, C=None, V=None, sync=True):
+        """cons! + jac_coord! at the K rows of X in ONE launch (`ctd_cons_jac_batch_dev_async`): row b of C / V equals
+        cons_jac(X[b]) bit for bit.  X: (K, nvar) device tensor with contiguous rows; C (K, ncon), V (K, nnzj) are allocated when
+        not given.  Returns (C, V)."""
+        px, k, ldx = self._batch_rows(X, self.dim_NLP_variables, "X")
+        C = self._batch_out(C, X, self.dim_NLP_constraints, "C", k)
+        V = self._batch_out(V, X, self.nnzj, "V", k)
+        self._ck(_lib.lib().ctd_cons_jac_batch_dev_async(self._h, k, px, ldx, C.data_ptr(), C.stride(0), V.data_ptr(), V.stride(0)))
+        if sync:
+            self.sync()
+        return C, V
+
+    def obj_batch(self, X, f=None, sync=True):
+        """obj(nlp, x) at the K rows of X (`ctd_obj_batch_dev_async`): f[b] = obj(X[b]).  f: K contiguous doubles on the device
+        (allocated when not given).  Returns f."""
+        import torch
+        px, k, ldx = self._batch_rows(X, self.dim_NLP_variables, "X")
+        if f is None:
+            f = torch.empty(k, dtype=torch.float64, device=X.device)
+        elif not (_is_tensor(f) and f.is_cuda and f.dtype == torch.float64 and f.is_contiguous() and f.numel() == k
+                  and f.device.index == self.device):
+            raise ValueError(f"f must be a contiguous float64 tensor of {k} entries on the handle's GPU")
+        self._ck(_lib.lib().ctd_obj_batch_dev_async(self._h, k, px, ldx, C.c_void_p(f.data_ptr())))
+        if sync:
+            self.sync()
+        return f
+
+    def grad_batch(self, X, G=None, sync=True):
+        """grad!(nlp, x, g) at the K rows of X (`ctd_grad_batch_dev_async`).  G: (K, nvar), allocated when not given.  Returns G."""
+        px, k, ldx = self._batch_rows(X, self.dim_NLP_variables, "X")
+        G = self._batch_out(G, X, self.dim_NLP_variables, "G", k)
+        self._ck(_lib.lib().ctd_grad_batch_dev_async(self._h, k, px, ldx, C.c_void_p(G.data_ptr()), G.stride(0)))
+        if sync:
+            self.sync()
+        return G
+
+    def hess_coord_batch(self, X, Y, obj_weight=1.0, H=None, sync=True):
+        """hess_coord!(nlp, x, y, vals; obj_weight) at the K rows of X with the multipliers of the K rows of Y
+        (`ctd_hess_coord_batch_dev_async`; obj_weight is shared).  H: (K, nnzh), allocated when not given.  Returns H."""
+        px, k, ldx = self._batch_rows(X, self.dim_NLP_variables, "X")
+        py, _, ldy = self._batch_rows(Y, self.dim_NLP_constraints, "Y", k)
+        H = self._batch_out(H, X, self.nnzh, "H", k)
+        self._ck(_lib.lib().ctd_hess_coord_batch_dev_async(self._h, k, px, ldx, py, ldy, float(obj_weight),
+                                                            C.c_void_p(H.data_ptr()), H.stride(0)))
+        if sync:
+            self.sync()
+        return H
+
     def sync(self):
         self._ck(_lib.lib().ctd_sync(self._h))
 

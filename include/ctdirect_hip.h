@@ -334,8 +334,38 @@ int32_t ctd_launch_info(const ctd_handle* h, int64_t* out8);
  * evaluation kernels by index range (all resident together: the launch costs about what the longest of them, the Hessian,
  * costs instead of their sum), then the fixed-order cross-workgroup sums.  Any output may be NULL to skip that callback.
  * Enqueue-only, like the *_dev_async entry points. */
+/* (single-iterate: ctd_eval_all_dev_async has no batched form -- batching it is out of scope; the *_batch_dev_async calls below
+ * batch the callbacks one by one) */
 int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* f_dev,
                                double* g_dev, double* c_dev, double* vals_dev, double* hvals_dev);
+
+/* ---- batched callbacks: K iterates of ONE transcription per launch -------------------------------------------------------
+ * No NLPModels counterpart (one iterate per call there): for hosts that hold many iterates of the same transcription at once --
+ * multistart, MPC scenarios / warm starts, parameter sweeps, line-search trial points, finite-difference checks.  One launch of
+ * the same kernels evaluates all `batch` members instead of `batch` launches: each launch of a single callback costs ~4 us of
+ * dispatch whatever its size.
+ * Layout: member b (0 <= b < batch) reads x_dev + b*ldx (and y_dev + b*ldy) and writes c_dev + b*ldc, vals_dev + b*ldv,
+ * g_dev + b*ldg, vals_dev + b*ldh (Hessian) and f_dev[b].  Leading dimensions are in doubles (not bytes) and at least the vector
+ * length: ldx >= nvar, ldy >= ncon, ldc >= ncon, ldv >= nnzj, ldg >= nvar, ldh >= nnzh; entries between a row's end and the next
+ * row are never touched (row slices of wider buffers work).  c_dev / vals_dev may be NULL to skip that output (as in
+ * ctd_cons_jac_dev_async; its leading dimension is then not checked).  All members share the handle's transcription, pattern,
+ * value order, tables and stream; obj_weight is shared by the members of a Hessian call.
+ * Contract: member b's results are BIT-IDENTICAL to one *_dev_async call on member b alone -- the same arithmetic per member and
+ * the same fixed-order cross-workgroup sums (one finish workgroup per member).
+ * Enqueue-only, like the *_dev_async calls (ctd_sync waits).  The partial-sum buffers of the objective, gradient and Hessian grow
+ * with the batch: a call that needs them larger drains the handle's stream first, and is refused (CTD_EINVAL) while the stream is
+ * capturing -- make one call with the batch size before a capture.  A run-time OCP compiles its batched constraint / Jacobian
+ * kernel at the first batched call.
+ * Checks, in this order: h NULL -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE (whatever the other arguments); batch < 1 or
+ * > 65535 (the grid's second dimension) -> CTD_EINVAL; a shard handle (step_begin / step_end not the whole grid, or a
+ * ctd_set_x_shards table) -> CTD_EINVAL: batched sharded evaluation is out of scope; then null pointers and leading dimensions
+ * that are too small -> CTD_EINVAL.  ctd_last_error names the reason. */
+int32_t ctd_cons_jac_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* c_dev, int64_t ldc,
+                                     double* vals_dev, int64_t ldv);
+int32_t ctd_obj_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* f_dev);   /* f_dev[batch] */
+int32_t ctd_grad_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* g_dev, int64_t ldg);
+int32_t ctd_hess_coord_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, const double* y_dev, int64_t ldy,
+                                       double obj_weight, double* vals_dev, int64_t ldh);
 
 /* 1-based (rows[k], cols[k]), k < nnzh, CSC order */
 int32_t ctd_hess_structure(const ctd_handle* h, int64_t* rows, int64_t* cols);
@@ -381,7 +411,9 @@ int32_t ctd_hess_debug_stamps(ctd_handle* h, const double* x_dev, const double* 
  * devices[k]; shard k writes its rows of c, its contiguous CSC range and its slices of the V columns
  * (ctd_sharded_shard_info).  The same device may appear several times (tests on a one-GPU box).  Exchanges between the
  * devices are peer-to-peer copies over xGMI (hipMemcpyPeerAsync on the shards' streams, ordered by events); a failure of one
- * of them is reported as CTD_ERCCL. */
+ * of them is reported as CTD_ERCCL.
+ * Single-iterate only: the batched callbacks (ctd_*_batch_dev_async) are out of scope for sharded evaluation -- they refuse a
+ * shard handle. */
 typedef struct ctd_sharded ctd_sharded;
 
 enum {
