@@ -224,7 +224,7 @@ int32_t jit_compile(const RtOcp& ro, const char* header, const std::vector<std::
                     std::string& code, std::vector<std::string>& lowered, std::string& err) {
     std::string key = ro.name + "|" + std::to_string((size_t)&ro) + "|" + header;
     for (const std::string& e : exprs) key += "|" + e;
-    // diagnostics: extra compiler options for the run-time kernels (e.g. CTD_JIT_EXTRA="-DCTD_NO_FOLD -DCTD_NO_SPLIT"), split at blanks
+    // diagnostics: extra compiler options for the run-time kernels (e.g. CTD_JIT_EXTRA="-DCTD_ABL=2"), split at blanks
     std::vector<std::string> extra;
     if (const char* ex = std::getenv("CTD_JIT_EXTRA")) {
         std::string cur;
@@ -474,7 +474,6 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
         h->kp.wt_store = wt >= 0 ? (wt ? 1 : 0) : (out_mb <= (double)env_int("CTD_WT_MB", 64) ? 1 : 0);
         h->out_mb = out_mb;
     }
-    h->kp.xcd_remap = env_int("CTD_XCD", 0);          // 1: every XCD walks one contiguous run of tiles (measured neutral)
     h->device = desc->device;
     if (h->device >= 0) {
         int ndev = 0;
@@ -1443,7 +1442,6 @@ static int32_t ensure_hess(ctd_handle* h) {
         const double out_mb = 8.0 * (double)(h->hp.step_end - h->hp.step_begin) * (double)H.Lseg / 1.0e6;
         hp.wt_store = wt >= 0 ? (wt ? 1 : 0) : (out_mb <= (double)std::min(16, env_int("CTD_WT_MB", 64)) ? 1 : 0);       // (sweep: gains up to ~10 MB, even at 16, losses from ~80)
     }
-    hp.xcd_remap = env_int("CTD_XCD", 0);
     if (h->hess_step) {
         HIP_TRY(h, upload(&h->d_hssrc, ssrc));
         HIP_TRY(h, upload(&h->d_hschunk, schunk));
@@ -1654,11 +1652,10 @@ int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double*
     ip.hp.near = h->kp.near;
     if (ip.hp.halo) { ip.hp.own_lo = h->halo_host.vbegin[h->halo_host.self]; ip.hp.own_hi = h->halo_host.vbegin[h->halo_host.self + 1]; }
     // The fused grid always carries the TILE body of the Hessian, also on handles whose stand-alone hess_coord runs the
-    // lane-per-step kernel (Gauss-Legendre 2 from 9 000 steps, 3 from 28 000: ensure_hess).  Measured (CTD_ITER_HESS_APART=1: fused
-    // first-order grid, then the step kernel and its finish as two more launches): Goddard GL2 N = 10 000 22.9 us against 14-16,
-    // GL3 N = 80 000 64.0 against 62.6 -- the two extra launches cost what the faster kernel gains
-    const bool hess_apart = hvals_dev && h->hess_step && env_int("CTD_ITER_HESS_APART", 0);
-    if (hvals_dev && !hess_apart) {
+    // lane-per-step kernel (Gauss-Legendre 2 from 9 000 steps, 3 from 28 000: ensure_hess).  Measured with the fused first-order
+    // grid, then the step kernel and its finish as two more launches: Goddard GL2 N = 10 000 22.9 us against 14-16, GL3 N = 80 000
+    // 64.0 against 62.6 -- the two extra launches cost what the faster kernel gains
+    if (hvals_dev) {
         ip.hp.obj_weight = obj_weight;
         ip.hp.vals = hvals_dev;
         ip.nb_h = ip.hp.ntiles + ip.hp.n_edge_blocks;
@@ -1685,7 +1682,6 @@ int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double*
         e = launch_iter<P>(ip, x_dev, y_dev, lds, h->stream);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    if (hess_apart) return enqueue_hess(h, x_dev, y_dev, obj_weight, hvals_dev);
     return CTD_OK;
 }
 

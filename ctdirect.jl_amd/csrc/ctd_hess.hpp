@@ -134,7 +134,7 @@ struct HParams {
     int32_t ntiles;
     int32_t n_edge_blocks;          // workgroups 0 .. n_edge_blocks - 1 share the edge entries, the tiles follow
     int64_t step_begin, step_end;   // shard of the time grid this launch evaluates (tiles cover [step_begin, step_end))
-    int32_t xcd_remap;              // tiles follow xcd_tile(block - 1) (ctd_layout.hpp)
+    int32_t xcd_remap;              // RETIRED, read by nothing (as KParams::xcd_remap)
     int32_t edge_begin, edge_end;   // edge entries this shard emits: irregular leading columns of its own steps ...
     int32_t edge2_begin, edge2_end; // ... and the trailing columns (owner of step N-1)
     int32_t edge_vv;                // 1: this shard adds the V x V terms of the final-path / boundary / last-node points

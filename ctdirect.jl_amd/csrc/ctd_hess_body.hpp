@@ -20,15 +20,11 @@
 
 namespace ctd {
 
-// inner directions per second-order eval lane (-DCTD_HESSK_OVERRIDE=k for tuning experiments)
-#ifdef CTD_HESSK_OVERRIDE
-template <class P> struct HessK { static constexpr int value = CTD_HESSK_OVERRIDE; };
-#else
-// Four for small OCPs; one for state dimension >= 8, where every further inner direction costs 2 doubles for each of the
-// ~3 n + m second-order numbers a lane holds: with two, the 12-state quadrotor needed 356 registers per lane (one wave per
-// SIMD) and ran 1.6x slower than with one (216 registers, two waves per SIMD); the 8-state one gains 4 %.
+// inner directions per second-order eval lane.  Four for small OCPs; one for state dimension >= 8, where every further inner
+// direction costs 2 doubles for each of the ~3 n + m second-order numbers a lane holds: with two, the 12-state quadrotor needed
+// 356 registers per lane (one wave per SIMD) and ran 1.6x slower than with one (216 registers, two waves per SIMD); the 8-state
+// one gains 4 %.
 template <class P> struct HessK { static constexpr int value = (P::NX >= 8) ? 1 : 4; };
-#endif
 
 template <class P, int SC, int S> struct HRL {
     static constexpr HessRecLayout R =
@@ -95,7 +91,7 @@ CTD_HD HBlockCtx make_hctx(const HParams& hp, int block, double* lds) {
         cx.cp = cx.rec + (cx.nslots + 2) * hp.R.stride;
         cx.red = cx.rec;
     } else {
-        const int tile = hp.xcd_remap ? xcd_tile(block - hp.n_edge_blocks, hp.ntiles) : block - hp.n_edge_blocks;
+        const int tile = block - hp.n_edge_blocks;
         const int cap = hp.T + hp.HL + hp.HH;
         if (hess_tables_staged(hp)) {
             const uint32_t* w = reinterpret_cast<const uint32_t*>(lds);

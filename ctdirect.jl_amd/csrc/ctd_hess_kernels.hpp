@@ -49,13 +49,7 @@ __device__ __forceinline__ void hess_pin_kernargs(const HParams& hp, const doubl
 }
 
 // at least two waves per SIMD: an instance a few registers over 256 per lane spills them instead of halving its occupancy
-#ifdef CTD_HESS_NO_CAP          // ablation
-#define CTD_HESS_CAP
-#elif defined(CTD_HESS_WAVES)   // experiment: more waves per SIMD (fewer registers per lane)
-#define CTD_HESS_CAP __attribute__((amdgpu_waves_per_eu(CTD_HESS_WAVES)))
-#else
 #define CTD_HESS_CAP __attribute__((amdgpu_waves_per_eu(2)))
-#endif
 // DBG = true: diagnostics instantiation (ctd_hess_debug_stamps, env CTD_HESS_STOP); the default one holds no stamp / stop code
 template <class P, int SC, int S, bool DBG>
 __device__ __forceinline__ void hess_body(const HParams& hp, const double* __restrict__ xu, const double* __restrict__ y, int block,

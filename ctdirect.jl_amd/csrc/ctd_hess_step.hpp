@@ -97,11 +97,8 @@ __device__ __forceinline__ void step_lds_order() {
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 // two waves per SIMD: 255 registers per lane without scratch (three: 168 registers, 68-420 B of scratch, 42 vs 28 us at cfg 4)
-#ifndef CTD_STEP_WAVES
-#define CTD_STEP_WAVES 2
-#endif
 template <class P, int S, bool SW>
-__global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(CTD_STEP_WAVES))) void hess_step_kernel(const HParams hp, const SParams sp, const double* __restrict__ xu,
+__global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2))) void hess_step_kernel(const HParams hp, const SParams sp, const double* __restrict__ xu,
                                                                 const double* __restrict__ y) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV;
     constexpr bool FREE = Dirs<P>::FREE;

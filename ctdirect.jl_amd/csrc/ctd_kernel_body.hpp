@@ -124,8 +124,7 @@ CTD_HD BlockCtx make_ctx(const KParams& kp, int block, double* lds) {
         cx.tau = cx.v + kMaxNV;
         cx.rec = cx.tau + 2 * kMaxEdgeSlots + 2;
     } else {
-        const int tb = block - kp.has_edge;
-        const int tile = kp.xcd_remap ? xcd_tile(tb, kp.ntiles) : tb;
+        const int tile = block - kp.has_edge;
         const int cap = kp.T + kp.HL + kp.HH;
         cx.is_edge = 0;
         cx.a = kp.step_begin + (int64_t)tile * kp.T;
@@ -734,12 +733,6 @@ CTD_HD void eval_point(const KParams& kp, const double* vv, int q, double t, con
         for (int c = 0; c < m; ++c) prm[1 + n + c] = uv[c];
 #pragma unroll
         for (int c = 0; c < nv; ++c) prm[1 + n + m + c] = cx.v[c];
-#ifdef CTD_ABL_NOEVAL      /* EXPERIMENT build only (profiles/r04_experiments.md): no arithmetic in the evaluation -- the bound of anything a
-                              restructured evaluation (row split, ...) could gain.  Outputs are garbage. */
-#pragma unroll
-        for (int e = 0; e < R.eval_sz; ++e) ev[e] = prm[e % (1 + n + m + nv)];
-        return;
-#endif
         if constexpr (split) SymDyn<P>::eval_part(q, prm, ev);
         else SymDyn<P>::eval(prm, ev);
         return;
@@ -1080,12 +1073,8 @@ template <class P, int SC, int S = 1> struct RegEval {
 // whatever launch bound and fin variant was chosen; ctd_jit.cpp routes them to the forward-dual path, profiles/r04_experiments.md.)
 template <class P, int SC, int S>
 CTD_HD bool fin_folded(const BlockCtx& cx) {
-#ifdef CTD_NO_FOLD
-    return false;
-#else
     constexpr bool path_ok = P::NPATH == 0 || SymPath<P>::value || Dirs<P>::NCH_PATH == 1;
     return !Dirs<P>::FUSED && SymDyn<P>::value && path_ok && !cx.is_edge;
-#endif
 }
 
 // EDGE BLOCK of an OCP with generated dynamics code (one workgroup of every launch: first / last steps, final-time path rows,
@@ -1097,29 +1086,19 @@ CTD_HD bool fin_folded(const BlockCtx& cx) {
 // generated dynamics code that comes in at least this many parts (= direction chunks) runs one part per wave.  Four: with three
 // (the 8-state quadrotor, 12 directions) the split measured SLOWER in both rounds -- round 2, 7-step tiles: +4 %; round 3, 16-step
 // tiles (48 lanes per part-wave): cfg 5' 38.6 -> 40.2 us, optimized 16.9 -> 18.5, trapeze 10.9 -> 11.7 (profiles/r03_experiments.md)
-#ifndef CTD_SPLIT_MIN_PARTS
-#define CTD_SPLIT_MIN_PARTS 4
-#endif
-constexpr int kSplitMinParts = CTD_SPLIT_MIN_PARTS;
+constexpr int kSplitMinParts = 4;
 
 template <class P, int SC, int S>
 CTD_HD bool edge_sym_layout(const BlockCtx& cx, int nthr) {
-#ifdef CTD_NO_EDGE_SYM
-    return false;
-#else
     constexpr int r_path = (P::NPATH > 0) ? Dirs<P>::NCH_PATH : 0;
     constexpr int n_b = (P::NBC > 0) ? Dirs<P>::NCH_BND : 0;
     constexpr bool parts = SymDyn<P>::parts >= kSplitMinParts && SymDyn<P>::parts == Dirs<P>::NCH_DYN;      // then one wave per part
     return SymDyn<P>::value && !Dirs<P>::FUSED && cx.is_edge && cx.nslots <= 8 && nthr >= 256 && r_path <= 4 && n_b <= 32 &&
            StagePoints<SC, S>::value * 8 <= 32 && (!parts || Dirs<P>::NCH_DYN * 64 <= nthr);
-#endif
 }
 
 template <class P, int SC, int S>
 CTD_HD bool split_eval(const BlockCtx& cx, int nthr) {
-#ifdef CTD_NO_SPLIT
-    return false;
-#else
     // (four parts and more: measured +2 % for the 12-state quadrotor, -4 % for the 8-state one with three, profiles/r02_tile_sweeps.log)
     constexpr bool ok = SymDyn<P>::value && SymDyn<P>::parts >= kSplitMinParts && SymDyn<P>::parts == Dirs<P>::NCH_DYN && !Dirs<P>::FUSED;
     constexpr int NP = Dirs<P>::NCH_DYN;
@@ -1128,20 +1107,11 @@ CTD_HD bool split_eval(const BlockCtx& cx, int nthr) {
     // dynamics lanes of all waves; one-point schemes: one task per step on the last wave -- run BEHIND the dynamics on the same
     // lanes) | ns path points
     return ok && !cx.is_edge && StagePoints<SC, S>::value * cx.nslots + ((P::NPATH > 0) ? cx.nslots : 0) <= 64 && r_path <= NP && NP * 64 <= nthr;
-#endif
 }
 
-// stores of the emit phase: outputs are written once and not read again by this kernel.  CTD_NT_STORE=1: nontemporal stores
-// (they bypass the L2's allocation, so the next evaluation finds x still cached) -- an experiment knob, see DESIGN.md
-#ifndef CTD_NT_STORE
-#define CTD_NT_STORE 0
-#endif
+// stores of the emit phase: outputs are written once and not read again by this kernel
 CTD_HD void emit_store(double* p, double v, int wt = 0) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#if CTD_NT_STORE
-    __builtin_nontemporal_store(v, p);
-    return;
-#endif
     // wt (KParams::wt_store, wave-uniform): WRITE-THROUGH store (sc1) -- the line leaves the XCD's L2 at once instead of staying dirty
     // until the end of the kernel, where the write-back of what is left is serial with the next launch (MI355X_MICROARCH.md: a
     // dependent kernel boundary costs + B / 6 TB/s for B dirty bytes).  Small launches gain (one round of workgroups: their stores

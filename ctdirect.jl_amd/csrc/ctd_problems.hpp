@@ -17,13 +17,6 @@
 #include <vector>
 #include "ctd_common.hpp"
 
-// dual directions evaluated per pass by one lane (per-problem default; -DCTD_DC_OVERRIDE=k for tuning experiments)
-#ifdef CTD_DC_OVERRIDE
-#define CTD_DC(dflt) (CTD_DC_OVERRIDE)
-#else
-#define CTD_DC(dflt) (dflt)
-#endif
-
 namespace ctd {
 
 struct BoxItem { int index; double lb, ub; };   // (lb, index, ub) triplets, src/DOCP_variables.jl:88-98
@@ -56,7 +49,7 @@ struct GoddardOCP {
     static constexpr bool HAS_LAGRANGE = false, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(4);                     // dual directions per pass
+    static constexpr int DC = 4;                     // dual directions per pass
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -95,7 +88,7 @@ struct GoddardAllOCP {
     static constexpr bool HAS_LAGRANGE = false, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = true;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(4);
+    static constexpr int DC = 4;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -137,7 +130,7 @@ struct DoubleIntegratorPathOCP {
     static constexpr bool HAS_LAGRANGE = true, HAS_MAYER = false;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(3);
+    static constexpr int DC = 3;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -171,7 +164,7 @@ struct QuadrotorOCP {
     static constexpr bool HAS_LAGRANGE = true, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(4);
+    static constexpr int DC = 4;
     static constexpr int MAXB = 320;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -230,7 +223,7 @@ struct Quadrotor12OCP {
     static constexpr bool HAS_LAGRANGE = true, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(4);
+    static constexpr int DC = 4;
     static constexpr int MAXB = 320;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -294,7 +287,7 @@ struct StagewiseScalarOCP {
     static constexpr bool HAS_LAGRANGE = true, HAS_MAYER = false;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(2);
+    static constexpr int DC = 2;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -320,7 +313,7 @@ struct EstimateInitialConditionOCP {                                            
     static constexpr bool HAS_LAGRANGE = false, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(2);
+    static constexpr int DC = 2;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -343,7 +336,7 @@ struct EstimateRotationRateOCP {                                                
     static constexpr bool HAS_LAGRANGE = false, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = true, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(3);
+    static constexpr int DC = 3;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -371,7 +364,7 @@ struct LeastSquaresConstraintOCP {                                              
     static constexpr bool HAS_LAGRANGE = true, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = true, LAG_V = false;       // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(2);
+    static constexpr int DC = 2;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }
@@ -400,7 +393,7 @@ struct DoubleIntegratorFreeT0TfOCP {
     static constexpr bool HAS_LAGRANGE = false, HAS_MAYER = true;
     static constexpr bool DYN_T = false, DYN_V = false, PATH_T = false, PATH_V = false;
     static constexpr bool LAG_T = false, LAG_V = false;      // explicit dependence of the Lagrange cost on t / v
-    static constexpr int DC = CTD_DC(3);
+    static constexpr int DC = 3;
     static constexpr int MAXB = 1024;                       // largest workgroup the kernels are compiled for (register budget)
     static constexpr bool HAS_SYM = false, HAS_SYM_DYN = false, HAS_SYM_PATH = false, HAS_SYM_LAG = false;   // symbolic functions: generated specialisations (ctd_sym_registry.hpp)
     static constexpr double t0_fixed() { return 0.0; }

@@ -181,7 +181,6 @@ int emu_cons_jac(int problem, int scheme, int pattern_mode, int64_t N, const dou
     if (tile <= 0) tile = default_tile(mo);
     KParams kp;
     mo.fill_kparams(kp, step_begin, step_end, tile);
-    if (const char* e = std::getenv("CTD_XCD")) kp.xcd_remap = std::atoi(e);      // same ablation knob as the engine
     if (const char* e = std::getenv("CTD_EMU_WG_STRIDE")) kp.wg_stride = std::atoi(e);      // multi-tile workgroups
     kp.tau = mo.uniform ? nullptr : mo.tau.data();
     kp.tmpl = mo.tmpl.data();
@@ -320,7 +319,6 @@ int emu_hess(int problem, int scheme, int pattern_mode, int64_t N, const double*
     if (tile <= 0) tile = default_hess_tile(mo);
     HParams hp;
     mo.fill_hparams(hp, tile, step_begin, step_end);
-    if (const char* e = std::getenv("CTD_XCD")) hp.xcd_remap = std::atoi(e);
     const HessModel& H = mo.H;
     hp.tau = mo.uniform ? nullptr : mo.tau.data();
     hp.tptr = H.ctptr.data(); hp.terms = H.tcode.data(); hp.pair_c = H.pair_c.data();
