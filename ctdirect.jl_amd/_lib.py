@@ -99,6 +99,10 @@ SYMBOLS = {
     "ctd_cons_jac_batch_dev_async": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
     "ctd_obj_batch_dev_async": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _vp]),
     "ctd_grad_batch_dev_async": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64]),
+    "ctd_jprod": (C.c_int32, [_vp, _dp, _dp, _dp]),
+    "ctd_jtprod": (C.c_int32, [_vp, _dp, _dp, _dp]),
+    "ctd_jprod_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "ctd_jtprod_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hess_coord_batch_dev_async": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64]),
     # one transcription on several GPUs of one process
     "ctd_create_sharded": (C.c_int32, [C.POINTER(ctd_desc), C.POINTER(C.c_int32), C.c_int32, C.POINTER(_vp)]),

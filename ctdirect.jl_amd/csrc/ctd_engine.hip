@@ -23,6 +23,7 @@
 #include "ctd_hess_kernels.hpp"
 #include "ctd_hess_step.hpp"
 #include "ctd_iter_kernels.hpp"
+#include "ctd_prod_kernels.hpp"
 #include "ctd_jit.hpp"
 
 using namespace ctd;
@@ -69,6 +70,16 @@ CTD_EXTERN_ITER(EstimateInitialConditionOCP)
 CTD_EXTERN_ITER(EstimateRotationRateOCP)
 CTD_EXTERN_ITER(LeastSquaresConstraintOCP)
 CTD_EXTERN_ITER(DoubleIntegratorFreeT0TfOCP)
+CTD_EXTERN_PROD(GoddardOCP)
+CTD_EXTERN_PROD(GoddardAllOCP)
+CTD_EXTERN_PROD(DoubleIntegratorPathOCP)
+CTD_EXTERN_PROD(QuadrotorOCP)
+CTD_EXTERN_PROD(Quadrotor12OCP)
+CTD_EXTERN_PROD(StagewiseScalarOCP)
+CTD_EXTERN_PROD(EstimateInitialConditionOCP)
+CTD_EXTERN_PROD(EstimateRotationRateOCP)
+CTD_EXTERN_PROD(LeastSquaresConstraintOCP)
+CTD_EXTERN_PROD(DoubleIntegratorFreeT0TfOCP)
 }  // namespace ctd
 
 struct ctd_handle {
@@ -137,6 +148,13 @@ struct ctd_handle {
     double out_mb = 0.0;            // megabytes of constraint / Jacobian outputs of one evaluation (the write-through rule, ctd_create)
     hipModule_t jit_bmod = nullptr;
     hipFunction_t f_cons_jac_batch = nullptr;
+    // matrix-free Jacobian products (ctd_jprod*, ctd_jtprod*): per-workgroup partial sums of d/dv, host-call staging of the
+    // direction and the product (nvar / ncon entries: nothing proportional to nnzj); the product kernels of a run-time OCP
+    double* d_ppartial = nullptr;
+    int64_t ppartial_cap = 0;
+    double *d_pdir = nullptr, *d_pout = nullptr;
+    hipModule_t jit_pmod = nullptr;
+    hipFunction_t f_jprod = nullptr, f_jtprod_units = nullptr, f_jtprod_finish = nullptr;
     std::string err;
 };
 
@@ -192,7 +210,8 @@ static void free_device(ctd_handle* h) {
                     (void*)h->d_x, (void*)h->d_c, (void*)h->d_vals, (void*)h->d_partial, (void*)h->d_obj, (void*)h->d_g,
                     (void*)h->d_gpartial, (void*)h->d_htptr, (void*)h->d_hterms, (void*)h->d_hvptr, (void*)h->d_hvterms,
                     (void*)h->d_heptr, (void*)h->d_hevptr, (void*)h->d_heterms, (void*)h->d_hedge_idx, (void*)h->d_htasks,
-                    (void*)h->d_hptasks, (void*)h->d_hbtasks, (void*)h->d_hpair_c, (void*)h->d_hcpos, (void*)h->d_hzpos, (void*)h->d_hssrc, (void*)h->d_hschunk, (void*)h->d_hsck, (void*)h->d_hpartials, (void*)h->d_y, (void*)h->d_hvals, (void*)h->d_halo, (void*)h->d_stitch_send, (void*)h->d_stitch_recv})
+                    (void*)h->d_hptasks, (void*)h->d_hbtasks, (void*)h->d_hpair_c, (void*)h->d_hcpos, (void*)h->d_hzpos, (void*)h->d_hssrc, (void*)h->d_hschunk, (void*)h->d_hsck, (void*)h->d_hpartials, (void*)h->d_y, (void*)h->d_hvals, (void*)h->d_halo, (void*)h->d_stitch_send, (void*)h->d_stitch_recv,
+                    (void*)h->d_ppartial, (void*)h->d_pdir, (void*)h->d_pout})
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -200,6 +219,7 @@ static void free_device(ctd_handle* h) {
     if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
     if (h->jit_hmod) (void)hipModuleUnload(h->jit_hmod);
     if (h->jit_bmod) (void)hipModuleUnload(h->jit_bmod);
+    if (h->jit_pmod) (void)hipModuleUnload(h->jit_pmod);
 }
 
 // ---- run-time compilation of the kernel templates for a registered OCP -------------------------------------------------
@@ -320,6 +340,23 @@ static int32_t jit_load_batch(ctd_handle* h) {
     if (st) return fail(h, st, err);
     HIP_TRY(h, hipModuleLoadData(&h->jit_bmod, code.data()));
     HIP_TRY(h, hipModuleGetFunction(&h->f_cons_jac_batch, h->jit_bmod, names[0].c_str()));
+    return CTD_OK;
+}
+// the product kernels (ctd_prod_kernels.hpp) of a run-time OCP: compiled at the first jprod / jtprod call
+static int32_t jit_load_prod(ctd_handle* h) {
+    std::string code, err;
+    std::vector<std::string> names;
+    const Layout& Lj = h->model.L;
+    const std::string a = std::to_string(Lj.sc), b = std::to_string(Lj.sc == SC_IRK && Lj.s > 0 ? Lj.s : 1);
+    const std::vector<std::string> exprs = {"ctd::jprod_kernel<ctd::UserOCP, " + a + ", " + b + ">",
+                                            "ctd::jtprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">",
+                                            "ctd::jtprod_finish_kernel<ctd::UserOCP>"};
+    int32_t st = jit_compile(*h->rt, "ctd_prod_kernels.hpp", exprs, "off", code, names, err);
+    if (st) return fail(h, st, err);
+    HIP_TRY(h, hipModuleLoadData(&h->jit_pmod, code.data()));
+    HIP_TRY(h, hipModuleGetFunction(&h->f_jprod, h->jit_pmod, names[0].c_str()));
+    HIP_TRY(h, hipModuleGetFunction(&h->f_jtprod_units, h->jit_pmod, names[1].c_str()));
+    HIP_TRY(h, hipModuleGetFunction(&h->f_jtprod_finish, h->jit_pmod, names[2].c_str()));
     return CTD_OK;
 }
 static int32_t jit_load_hess(ctd_handle* h) {
@@ -1263,6 +1300,93 @@ int32_t ctd_grad(ctd_handle* h, const double* x, double* g) {
     HIP_TRY(h, hipMemcpy(g, h->d_g, sizeof(double) * nvar, hipMemcpyDeviceToHost));
     return CTD_OK;
 }
+
+// ---- matrix-free Jacobian products: jprod!(nlp, x, v, Jv), jtprod!(nlp, x, w, Jtw) -------------------------------------
+// ctd_prod_kernels.hpp.  Checks in this order: handle, device (CTD_ENODEVICE), whole-grid handle, then pointers (CTD_EINVAL).
+static int32_t prod_check(ctd_handle* h, const char* fn, const double* x, const double* d, const double* out) {
+    if (!h) return CTD_EINVAL;
+    if (h->device < 0) return fail(h, CTD_ENODEVICE, std::string(fn) + ": compute call on a host-only handle (device = -1); there is no CPU fallback");
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": products need a handle of the whole grid; sharded products (step_begin / step_end, "
+                                   "ctd_set_x_shards) are not supported");
+    if (!x || !d || !out) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument");
+    if (out == x || out == d) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
+    return CTD_OK;
+}
+
+// the JC directions per jtprod lane of a run-time OCP (ProdDirs<UserOCP>::JC, the same formula)
+static int prod_chunk_rt(const RtOcp& ro) { return ro.info.n >= 8 ? 2 : (ro.dc < 4 ? ro.dc : 4); }
+
+static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, const double* d_dev, double* out_dev) {
+    const char* fn = transpose ? "ctd_jtprod" : "ctd_jprod";
+    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
+    if (h->rt && !h->f_jprod) { const int32_t st = jit_load_prod(h); if (st) return st; }
+    const Layout& L = h->model.L;
+    ProdParams pp;
+    std::memset(&pp, 0, sizeof(pp));
+    pp.L = L;
+    pp.tau = h->d_tau;
+    pp.dir = d_dev;
+    pp.out = out_dev;
+    hipError_t e = hipErrorInvalidValue;
+    if (!transpose) {
+        if (h->rt) {
+            void* args[] = {&pp, &x_dev};
+            e = jit_launch(h->f_jprod, (int)((L.N + 1 + 255) / 256), 256, 0, h->stream, args);
+        }
+        for_problem(h->model.problem, [&](auto tag) { e = launch_jprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
+    } else {
+        int jc = 1;
+        if (h->rt) jc = prod_chunk_rt(*h->rt);
+        for_problem(h->model.problem, [&](auto tag) { jc = prod_chunk<typename decltype(tag)::type>(); });
+        pp.nch = (int32_t)((prod_dirs_per_node(L) + jc - 1) / jc);
+        const int64_t blocks = ((L.N + 1) * (int64_t)pp.nch + 255) / 256;
+        if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
+        pp.nblocks = (int32_t)blocks;
+        const int32_t st = grow_scratch(h, &h->d_ppartial, h->ppartial_cap, blocks * kMaxNV, fn);
+        if (st) return st;
+        pp.partial = h->d_ppartial;
+        if (h->rt) {
+            void* args[] = {&pp, &x_dev};
+            e = jit_launch(h->f_jtprod_units, (int)blocks, 256, 0, h->stream, args);
+            if (e == hipSuccess) e = jit_launch(h->f_jtprod_finish, 1, 64, 0, h->stream, args);
+        }
+        for_problem(h->model.problem, [&](auto tag) { e = launch_jtprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
+    }
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_jprod_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
+    const int32_t st = prod_check(h, "ctd_jprod_dev_async", x_dev, v_dev, Jv_dev);
+    return st ? st : enqueue_prod(h, false, x_dev, v_dev, Jv_dev);
+}
+int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
+    const int32_t st = prod_check(h, "ctd_jtprod_dev_async", x_dev, w_dev, Jtw_dev);
+    return st ? st : enqueue_prod(h, true, x_dev, w_dev, Jtw_dev);
+}
+
+// host pointers: staged through the handle's x buffer and two vectors of max(nvar, ncon) entries
+static int32_t host_prod(ctd_handle* h, bool transpose, const double* x, const double* d, double* out) {
+    const int32_t st0 = prod_check(h, transpose ? "ctd_jtprod" : "ctd_jprod", x, d, out);
+    if (st0) return st0;
+    const Layout& L = h->model.L;
+    const int64_t nin = transpose ? L.ncon : L.nvar, nout = transpose ? L.nvar : L.ncon;
+    int32_t st = ensure_staging(h, false, false);
+    if (st) return st;
+    const size_t len = (size_t)std::max<int64_t>(std::max<int64_t>(L.nvar, L.ncon), 1);
+    if (!h->d_pdir) HIP_TRY(h, hipMalloc((void**)&h->d_pdir, sizeof(double) * len));
+    if (!h->d_pout) HIP_TRY(h, hipMalloc((void**)&h->d_pout, sizeof(double) * len));
+    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_pdir, d, sizeof(double) * nin, hipMemcpyHostToDevice, h->stream));
+    st = enqueue_prod(h, transpose, h->d_x, h->d_pdir, h->d_pout);
+    if (st) return st;
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_pout, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CTD_OK;
+}
+int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv) { return host_prod(h, false, x, v, Jv); }
+int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw) { return host_prod(h, true, x, w, Jtw); }
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {
     if (!h) return CTD_EINVAL;

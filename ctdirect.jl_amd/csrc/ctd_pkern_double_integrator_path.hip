@@ -1,0 +1,5 @@
+// Matrix-free Jacobian product kernels (ctd_prod_kernels.hpp) of one registry entry (DoubleIntegratorPathOCP).
+#include "ctd_prod_kernels.hpp"
+namespace ctd {
+CTD_INSTANTIATE_PROD(DoubleIntegratorPathOCP)
+}

@@ -449,6 +449,40 @@ class DOCP:
         self._ck(L.ctd_grad(self._h, _dp(x), _dp(g)))
         return g
 
+    def _prod(self, x, d, out, sync, transpose):
+        nin, nout = ((self.dim_NLP_constraints, self.dim_NLP_variables) if transpose
+                     else (self.dim_NLP_variables, self.dim_NLP_constraints))
+        name = "w" if transpose else "v"
+        L = _lib.lib()
+        self._check_x(x)
+        if _is_tensor(x):
+            import torch
+            if out is None:
+                out = torch.empty(nout, dtype=torch.float64, device=x.device)
+            fn = L.ctd_jtprod_dev_async if transpose else L.ctd_jprod_dev_async
+            self._ck(fn(self._h, self._dev_ptr(x, self.dim_NLP_variables, "x"), self._dev_ptr(d, nin, name),
+                        self._dev_ptr(out, nout, "out")))
+            if sync:
+                self.sync()
+            return out
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        if d.size != nin:
+            raise ValueError(f"{name} has {d.size} entries, expected {nin}")
+        out = np.empty(nout) if out is None else _host_out(out, nout, "out")
+        self._ck((L.ctd_jtprod if transpose else L.ctd_jprod)(self._h, _dp(x), _dp(d), _dp(out)))
+        return out
+
+    def jprod(self, x, v, out=None, sync=True):
+        """jprod!(nlp, x, v, Jv): J(x) v without assembling J (ncon entries).  J is the exact derivative of the constraints
+        (the structural Jacobian, whatever the pattern mode).  NumPy inputs use the host entry point; device tensors are
+        enqueued on the handle's stream (`ctd_jprod_dev_async`), followed by a sync when `sync`."""
+        return self._prod(x, v, out, sync, False)
+
+    def jtprod(self, x, w, out=None, sync=True):
+        """jtprod!(nlp, x, w, Jtw): J(x)' w without assembling J (nvar entries); see `jprod`."""
+        return self._prod(x, w, out, sync, True)
+
     def grad_shard(self, x, g, sync=False):
         """`ctd_grad_shard_dev_async`: the gradient entries of THIS shard's own variables into the full-length device tensor g
         (+ the shard's partial sums of d/dv in the nv tail entries), from a sharded iterate read in place -- no all-gathered x."""

@@ -367,6 +367,27 @@ int32_t ctd_grad_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_d
 int32_t ctd_hess_coord_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, const double* y_dev, int64_t ldy,
                                        double obj_weight, double* vals_dev, int64_t ldh);
 
+/* Matrix-free Jacobian products at x (NLPModels jprod! / jtprod!; the reference leaves both backends empty,
+ * jprod_backend = jtprod_backend = EmptyADbackend, src/collocation.jl:104-110):
+ *   Jv  = J(x) v   (ncon entries, the row order of ctd_cons: [C_i^x, C_i^{k,1..s}, G_i].., G_N+1, B)
+ *   Jtw = J(x)' w  (nvar entries, the variable layout of the transcription).
+ * J is the exact derivative of what ctd_cons computes: the Jacobian of the STRUCTURAL pattern, whatever the handle's
+ * pattern_mode or value_order.  On a REFERENCE_MANUAL handle with ctd_dropped_nonzeros > 0 the products therefore include the
+ * entries the manual pattern drops, as ADNLPModels' ForwardDiff product backends do.  Results are reproducible bit for bit
+ * (fixed summation order, no floating-point atomics) and equal for every pattern_mode / value_order of one transcription.
+ * No device memory proportional to nnzj is allocated: the products never assemble J (scratch: one row of kMaxNV partial sums
+ * per workgroup; the host calls stage x, the direction and the result).
+ * Run-time OCPs (ctd_register_ocp) compile their product kernels on the first call: make one call before capturing a graph.
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle (step_begin / step_end not
+ * the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (sharded products are not supported); null pointers or an output
+ * that equals an input -> CTD_EINVAL. */
+/* host pointers: return when the result is in the caller's buffer */
+int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv);
+int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw);
+/* device pointers on the handle's device: enqueue-only on the handle's stream (ctd_sync waits), capturable after one warm call */
+int32_t ctd_jprod_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev);
+int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev);
+
 /* 1-based (rows[k], cols[k]), k < nnzh, CSC order */
 int32_t ctd_hess_structure(const ctd_handle* h, int64_t* rows, int64_t* cols);
 /* same pattern as 0-based CSC (colptr[nvar + 1], rowval[nnzh]) */
