@@ -15,13 +15,20 @@ At N > 1 the ITERATE IS SHARDED like the steps: a rank's x buffer holds its own 
 NaN everywhere else.  The few entries of other ranks its rows read (next rank's first node, previous rank's last block for
 one-point schemes, first / final state) are loaded by the evaluation kernel IN PLACE from the owner's HBM over xGMI (IPC-
 mapped buffers, `ShardedDOCP.enable_peer_x` / `ctd_set_x_shards`): the timed step contains no collective, no copy and no
-extra kernel.  The same line carries secondary figures: `halo_allgather` (the entries fetched with one RCCL all-gather
+extra kernel.  The --full line carries secondary figures: `halo_allgather` (the entries fetched with one RCCL all-gather
 instead), `stitched_c` (+ the all-gather that hands every rank the whole constraint vector), `broadcast_x` (a replicated
 iterate sent whole from rank 0) and `no_exchange` (x in place), and the per-rank kernel times.
 `value`: weak scaling = shard evaluations all ranks completed per second; strong scaling = evaluations of the whole
 transcription per second; both over the max-over-ranks wall time of the K timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--x-mode peer|halo] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--x-mode peer|halo] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up the workload, warms up, times the K steps, writes the outputs
+(--dump-outputs) and prints the line (`value`, `ms_per_step`, and at N = 1 the roofline of the timed region).  Everything
+else moves behind --full: the secondary figures of the workload and their per-dispatch kernel times, the CPU baseline, the
+kernel-only figures of the other configs, patterns, orders, grid sizes and the Hessian, the other callbacks, and at N > 1
+the sharded-iterate check, the other x mode and the `strong` block.  --no-cpu-baseline, --no-extras, --no-strong and
+--two-streams shape a --full run.
 
 --dump-outputs DIR writes what the last timed step handed its caller -- the constraint vector c and the Jacobian values, float64
 -- as DIR/constraints.npy and DIR/jacobian_values.npy (N > 1: each rank's full-length buffers as DIR/<name>_rank<r>.npy;
@@ -36,7 +43,7 @@ any rank exits non-zero the others are terminated and the launcher exits non-zer
 in a collective for a peer that died).  On a box with fewer than N GPUs the ranks find that out themselves, share the
 devices (gloo carries the barrier: RCCL refuses two ranks on one device) and the line says `"rehearsal": true`.
 
-At N > 1 the default line (`--config cfg2_weak`) also carries a `strong` block: the strong-scaling workloads north_star names
+At N > 1 the --full line of the default config (`--config cfg2_weak`) also carries a `strong` block: the strong-scaling workloads north_star names
 (cfg2_strong = the 10 000-step Goddard transcription sharded over the N GPUs, cfg4, cfg5), each with evals/s, per-rank kernel
 time and roofline fraction, and the `stitched_c` variant (+ the RCCL all-gather of the constraint vector).
 """
@@ -212,13 +219,16 @@ def _main(real_stdout):
     ap.add_argument("--x-mode", choices=("peer", "halo"), default="peer",
                     help="N > 1: how a rank obtains the few entries of x its neighbours own: 'peer' = read in place by the kernel from "
                          "the owner's HBM (IPC-mapped buffers over xGMI; falls back to 'halo' when the mapping is refused), 'halo' = "
-                         "one all-gather before the evaluation.  The line records the other one as a secondary figure")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the kernel-only figures of the other configs")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the `strong` block (cfg2_strong / cfg4 / cfg5) of the default line")
+                         "one all-gather before the evaluation.  The --full line records the other one as a secondary figure")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: secondary figures, per-dispatch kernel times, CPU baseline, "
+                         "the other configs' kernel-only figures, other callbacks, and at N > 1 the sharded-iterate check and the `strong` block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the kernel-only figures of the other configs and the other callbacks")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the `strong` block (cfg2_strong / cfg4 / cfg5) of the default line")
     ap.add_argument("--two-streams", action="store_true",
-                    help="also time independent evaluations on two streams (overlapping kernels: keeps it out of the default run, whose rocprofv3 "
-                         "kernel statistics are the timed region's)")
+                    help="--full: also time independent evaluations on two streams (overlapping kernels: keeps it out of the default run, whose "
+                         "rocprofv3 kernel statistics are the timed region's)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write the outputs of the last timed step (c and the Jacobian values, float64, at most 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -318,8 +328,8 @@ def _main(real_stdout):
             el = float(t[0])
         return el
 
-    def measure(name, steps, warmup, ksec, keep_outputs=False):
-        """One workload of CONFIGS on this job's ranks: the timed step + its secondary figures + per-rank kernel times.
+    def measure(name, steps, warmup, ksec, keep_outputs=False, full=True):
+        """One workload of CONFIGS on this job's ranks: the timed step + (full) its secondary figures + per-rank kernel times.
         keep_outputs: copy c and the Jacobian values as the last timed step left them (out.outputs).
         N = 1: one fused evaluation, pointers pre-bound.  N > 1: the rank's evaluation on the SHARDED iterate -- x_mode "peer":
         the neighbours' entries read in place by the kernel, outputs row-sharded, no collective before or
@@ -364,7 +374,7 @@ def _main(real_stdout):
                               steps=steps, x_mode=x_mode, peer_error=peer_error, region_ms=region["ms_per_launch"],
                               per_step_value=(world if cf["scaling"] == "weak" else 1), secondary={}, outputs=outputs)
         secondary = out.secondary
-        if dist_on:
+        if dist_on and full:
             # the rank's outputs from the sharded iterate (NaN outside what it owns) equal those from the whole iterate, bit for bit
             c_chk, v_chk = torch.zeros_like(c), torch.zeros_like(vals)
             sh.bind_cons_jac(x_full, c_chk, v_chk, stitch=False, x_mode=None)()
@@ -453,14 +463,14 @@ def _main(real_stdout):
             except Exception as e:
                 secondary["sharded_iteration"] = {"error": repr(e)[:300]}
         # kernel time per rank: per-dispatch start / stop events (hipExtLaunchKernelGGL), median of five batches of 200
-        out.per_dispatch = sorted(docp.time_cons_jac(x_full, c, vals, iters=200) for _ in range(5))[2]
+        out.per_dispatch = sorted(docp.time_cons_jac(x_full, c, vals, iters=200) for _ in range(5))[2] if full else None
         # algorithmic bytes of one launch: read the shard's x, write its c rows and Jacobian values:
         # B = 8 (nvar + ncon + nnzj) of the per-rank sub-problem
         b, e = sh.steps
         out.one = ct.DOCP(prob, e - b, sch, device=-1)
         out.alg_bytes = 8 * (out.one.dim_NLP_variables + out.one.dim_NLP_constraints + out.one.nnzj)
         out.per_rank = None
-        if dist_on:
+        if dist_on and full:
             t = torch.zeros(world, dtype=torch.float64, device=dev)
             t[rank] = out.per_dispatch
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -468,7 +478,7 @@ def _main(real_stdout):
                             for r in range(world)]
         return out
 
-    m = measure(args.config, args.steps, args.warmup, 500, keep_outputs=bool(args.dump_outputs))
+    m = measure(args.config, args.steps, args.warmup, 500, keep_outputs=bool(args.dump_outputs), full=args.full)
     sh, docp, x_host, x_full, x, c, vals = m.sh, m.docp, m.x_host, m.x_full, m.x, m.c, m.vals
     N, el, x_mode, one, alg_bytes = m.N, m.el, m.x_mode, m.one, m.alg_bytes
     region_ms, per_step_value, secondary, per_dispatch, per_rank = m.region_ms, m.per_step_value, m.secondary, m.per_dispatch, m.per_rank
@@ -482,7 +492,7 @@ def _main(real_stdout):
     # N > 1, default line: the strong-scaling workloads north_star names ("a 10k-step Goddard transcription at 1/2/4/8" =
     # cfg2_strong; BASELINE configs[3] / [4] sharded), each with its stitched-c variant -- `value` stays the weak-scaling figure
     strong = {}
-    if world > 1 and args.config == "cfg2_weak" and not args.no_strong:
+    if world > 1 and args.config == "cfg2_weak" and args.full and not args.no_strong:
         for name in ("cfg2_strong", "cfg4", "cfg5"):
             if not within_budget():
                 strong[name] = {"skipped": f"wall-time budget of {budget_s:.0f} s (CTD_BENCH_BUDGET_S) used up"}
@@ -504,9 +514,10 @@ def _main(real_stdout):
 
     # roofline of the dominant (only) kernel, per rank.  kernel_ms: N = 1: HIP events on the launch stream around the K
     # timed launches / K (back-to-back launches: the kernel's average duration including the dispatch gap); N > 1 (the
-    # region also holds collectives): per-dispatch start / stop events (hipExtLaunchKernelGGL), median of five batches of 200
+    # region also holds collectives; --full only): per-dispatch start / stop events (hipExtLaunchKernelGGL), median of five
+    # batches of 200
     kernel_ms = region_ms if not dist_on else per_dispatch
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms is not None else None
     traffic, traffic_src = None, None
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     if world == 1 and args.config == "cfg2_weak" and os.path.exists(pmc):
@@ -519,7 +530,7 @@ def _main(real_stdout):
 
     # the other single-GPU BASELINE configs (parity-test cases, not the bench line): kernel time and roofline fraction
     others, hessian, optimized, csr_rows, large = [], [], [], [], []
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         for prob, sch, n in (("double_integrator_path", "midpoint", 100000), ("goddard", "gauss_legendre_3", 80000),
                              ("quadrotor", "gauss_legendre_3", 20000), ("quadrotor12", "gauss_legendre_3", 20000),
                              ("quadrotor12", "midpoint", 20000)):
@@ -614,7 +625,7 @@ def _main(real_stdout):
     # workload (never `value`): objective, gradient, one whole solver iteration (obj + grad + cons + Jacobian + Hessian in two
     # launches) with everything resident in HBM, and the fused evaluation through the host-pointer entry point (PCIe inclusive)
     separately = {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         try:
             import time as _t
             K2 = 200
@@ -716,6 +727,7 @@ def _main(real_stdout):
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": f"{args.config}: {PROBLEM} / {SCHEME}, {shard_txt}; fused cons!+jac_coord! on HBM-resident x; "
                             + cfg["what"] + ("" if world == 1 else
@@ -729,14 +741,17 @@ def _main(real_stdout):
                 "nvar_per_gpu": one.dim_NLP_variables, "ncon_per_gpu": one.dim_NLP_constraints, "nnzj_per_gpu": one.nnzj,
                 "launch": docp.launch_info(),
             },
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": f"ctd::cons_jac_kernel<{PROBLEM}, {SCHEME}>", "kernel_ms": kernel_ms,
-                         "kernel_ms_per_dispatch_events": per_dispatch,
-                         "timing": ("HIP events on the launch stream around the K timed launches / K" if world == 1 else
-                                    "per-dispatch HIP events of rank 0's kernel (the timed region also holds collectives)"),
-                         "algorithmic_bytes_per_launch": alg_bytes},
         }
+        if kernel_ms is not None:       # (N > 1: the per-dispatch kernel times of --full)
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": f"ctd::cons_jac_kernel<{PROBLEM}, {SCHEME}>", "kernel_ms": kernel_ms,
+                               "kernel_ms_per_dispatch_events": per_dispatch,
+                               "timing": ("HIP events on the launch stream around the K timed launches / K" if world == 1 else
+                                          "per-dispatch HIP events of rank 0's kernel (the timed region also holds collectives)"),
+                               "algorithmic_bytes_per_launch": alg_bytes}
+            if per_dispatch is None:    # (plain run at N = 1: the per-dispatch figure is a run of its own)
+                del out["roofline"]["kernel_ms_per_dispatch_events"]
         if per_rank is not None:
             out["roofline"]["per_rank"] = per_rank
         if rehearsal:
@@ -752,7 +767,7 @@ def _main(real_stdout):
             out["large_grid_kernel_only"] = large
         if hessian:
             out["hessian_kernel_only"] = hessian
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(PROBLEM, SCHEME, N, x_host)
         out.update(secondary)
         if strong:

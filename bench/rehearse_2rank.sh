@@ -6,8 +6,9 @@ out=${1:-gpurun_out/r02_rehearsal_2rank.jsonl}
 : > "$out"
 for cfg in cfg2_weak cfg2_strong cfg4 cfg5; do
   CTD_BENCH_DEVICE=0 CTD_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 200 --warmup 20 --config $cfg 2>gpurun_out/rehearsal_$cfg.err | grep '^{' >> "$out" \
-      || { echo "rehearsal $cfg failed"; tail -5 gpurun_out/rehearsal_$cfg.err; }
+      --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 200 --warmup 20 --config $cfg --full \
+      2>"$(dirname "$out")/rehearsal_$cfg.err" | grep '^{' >> "$out" \
+      || { echo "rehearsal $cfg failed"; tail -5 "$(dirname "$out")/rehearsal_$cfg.err"; }
 done
 python - "$out" <<'PY'
 import json, sys

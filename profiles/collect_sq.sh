@@ -11,7 +11,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline"
+BENCH="python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline"      # (--full: the Hessian kernels come from its extras)
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT \
   --kernel-trace --output-format csv -d $OUT/pmc_sq1 -- $BENCH > $OUT/pmc_sq1.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS \
@@ -25,7 +25,7 @@ for d in ("pmc_sq1", "pmc_sq2"):
         for r in csv.DictReader(open(f)):
             if "ctd::cons_jac_kernel" in r["Kernel_Name"] or "ctd::hess_kernel" in r["Kernel_Name"] or "ctd::hess_step_kernel" in r["Kernel_Name"]:
                 pmc[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
-res = {"command": "python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline",
+res = {"command": "python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline",
        "note": "mean per launch over all launches of the kernel; SQ_*_CYCLES / WAIT / ACTIVE counters are in quad-cycles summed "
                "over waves; fractions are of SQ_WAVE_CYCLES", "kernels": {}}
 for k, d in pmc.items():

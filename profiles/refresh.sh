@@ -8,9 +8,9 @@ cd "$(dirname "$0")/.."
 TAG=${1:-r02}
 E=gpurun_out/evidence_$TAG
 mkdir -p $E
-python3 bench.py --steps 20 --warmup 5 > $E/bench_line_steps20.json 2> $E/bench_steps20.err
-python3 bench.py > $E/bench_line_default.json 2> $E/bench_default.err
-python3 bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-extras > $E/bench_line_steps2000.json 2> $E/bench_steps2000.err
+python3 bench.py --steps 20 --warmup 5 --full > $E/bench_line_steps20.json 2> $E/bench_steps20.err
+python3 bench.py --full > $E/bench_line_default.json 2> $E/bench_default.err
+python3 bench.py --steps 2000 --warmup 200 --full --no-cpu-baseline --no-extras > $E/bench_line_steps2000.json 2> $E/bench_steps2000.err
 echo "bench lines done"
 bash profiles/collect.sh $TAG > $E/collect.log 2>&1
 echo "rocprof + HBM counters done"
