@@ -24,6 +24,7 @@
 #include "ctd_hess_step.hpp"
 #include "ctd_iter_kernels.hpp"
 #include "ctd_prod_kernels.hpp"
+#include "ctd_hprod_kernels.hpp"
 #include "ctd_jit.hpp"
 
 using namespace ctd;
@@ -80,6 +81,16 @@ CTD_EXTERN_PROD(EstimateInitialConditionOCP)
 CTD_EXTERN_PROD(EstimateRotationRateOCP)
 CTD_EXTERN_PROD(LeastSquaresConstraintOCP)
 CTD_EXTERN_PROD(DoubleIntegratorFreeT0TfOCP)
+CTD_EXTERN_HPROD(GoddardOCP)
+CTD_EXTERN_HPROD(GoddardAllOCP)
+CTD_EXTERN_HPROD(DoubleIntegratorPathOCP)
+CTD_EXTERN_HPROD(QuadrotorOCP)
+CTD_EXTERN_HPROD(Quadrotor12OCP)
+CTD_EXTERN_HPROD(StagewiseScalarOCP)
+CTD_EXTERN_HPROD(EstimateInitialConditionOCP)
+CTD_EXTERN_HPROD(EstimateRotationRateOCP)
+CTD_EXTERN_HPROD(LeastSquaresConstraintOCP)
+CTD_EXTERN_HPROD(DoubleIntegratorFreeT0TfOCP)
 }  // namespace ctd
 
 struct ctd_handle {
@@ -155,6 +166,12 @@ struct ctd_handle {
     double *d_pdir = nullptr, *d_pout = nullptr;
     hipModule_t jit_pmod = nullptr;
     hipFunction_t f_jprod = nullptr, f_jtprod_units = nullptr, f_jtprod_finish = nullptr;
+    // matrix-free Hessian products (ctd_hprod*): their own partial sums (a graph captured over jtprod keeps its buffer), host-call
+    // staging of v and Hv in d_pdir / d_pout and of y in d_y; the hprod kernels of a run-time OCP (a module of their own)
+    double* d_hppartial = nullptr;
+    int64_t hppartial_cap = 0;
+    hipModule_t jit_hpmod = nullptr;
+    hipFunction_t f_hprod_units = nullptr, f_hprod_finish = nullptr;
     std::string err;
 };
 
@@ -211,7 +228,7 @@ static void free_device(ctd_handle* h) {
                     (void*)h->d_gpartial, (void*)h->d_htptr, (void*)h->d_hterms, (void*)h->d_hvptr, (void*)h->d_hvterms,
                     (void*)h->d_heptr, (void*)h->d_hevptr, (void*)h->d_heterms, (void*)h->d_hedge_idx, (void*)h->d_htasks,
                     (void*)h->d_hptasks, (void*)h->d_hbtasks, (void*)h->d_hpair_c, (void*)h->d_hcpos, (void*)h->d_hzpos, (void*)h->d_hssrc, (void*)h->d_hschunk, (void*)h->d_hsck, (void*)h->d_hpartials, (void*)h->d_y, (void*)h->d_hvals, (void*)h->d_halo, (void*)h->d_stitch_send, (void*)h->d_stitch_recv,
-                    (void*)h->d_ppartial, (void*)h->d_pdir, (void*)h->d_pout})
+                    (void*)h->d_ppartial, (void*)h->d_pdir, (void*)h->d_pout, (void*)h->d_hppartial})
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -220,6 +237,7 @@ static void free_device(ctd_handle* h) {
     if (h->jit_hmod) (void)hipModuleUnload(h->jit_hmod);
     if (h->jit_bmod) (void)hipModuleUnload(h->jit_bmod);
     if (h->jit_pmod) (void)hipModuleUnload(h->jit_pmod);
+    if (h->jit_hpmod) (void)hipModuleUnload(h->jit_hpmod);
 }
 
 // ---- run-time compilation of the kernel templates for a registered OCP -------------------------------------------------
@@ -357,6 +375,21 @@ static int32_t jit_load_prod(ctd_handle* h) {
     HIP_TRY(h, hipModuleGetFunction(&h->f_jprod, h->jit_pmod, names[0].c_str()));
     HIP_TRY(h, hipModuleGetFunction(&h->f_jtprod_units, h->jit_pmod, names[1].c_str()));
     HIP_TRY(h, hipModuleGetFunction(&h->f_jtprod_finish, h->jit_pmod, names[2].c_str()));
+    return CTD_OK;
+}
+// the Hessian product kernels (ctd_hprod_kernels.hpp) of a run-time OCP: compiled at the first hprod call
+static int32_t jit_load_hprod(ctd_handle* h) {
+    std::string code, err;
+    std::vector<std::string> names;
+    const Layout& Lj = h->model.L;
+    const std::string a = std::to_string(Lj.sc), b = std::to_string(Lj.sc == SC_IRK && Lj.s > 0 ? Lj.s : 1);
+    const std::vector<std::string> exprs = {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">",
+                                            "ctd::hprod_finish_kernel<ctd::UserOCP>"};
+    int32_t st = jit_compile(*h->rt, "ctd_hprod_kernels.hpp", exprs, "off", code, names, err);
+    if (st) return fail(h, st, err);
+    HIP_TRY(h, hipModuleLoadData(&h->jit_hpmod, code.data()));
+    HIP_TRY(h, hipModuleGetFunction(&h->f_hprod_units, h->jit_hpmod, names[0].c_str()));
+    HIP_TRY(h, hipModuleGetFunction(&h->f_hprod_finish, h->jit_hpmod, names[1].c_str()));
     return CTD_OK;
 }
 static int32_t jit_load_hess(ctd_handle* h) {
@@ -1387,6 +1420,77 @@ static int32_t host_prod(ctd_handle* h, bool transpose, const double* x, const d
 }
 int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv) { return host_prod(h, false, x, v, Jv); }
 int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw) { return host_prod(h, true, x, w, Jtw); }
+
+// ---- matrix-free Hessian products: hprod!(nlp, x, y, v, Hv; obj_weight) ------------------------------------------------
+// ctd_hprod_kernels.hpp.  Checks in the order of prod_check; y may be null (objective only) but Hv must not alias it.
+static int32_t hprod_check(ctd_handle* h, const char* fn, const double* x, const double* y, const double* v, const double* out) {
+    const int32_t st = prod_check(h, fn, x, v, out);
+    if (st) return st;
+    if (y && out == y) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
+    return CTD_OK;
+}
+
+static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                             double* out_dev) {
+    const char* fn = "ctd_hprod";
+    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
+    if (h->rt && !h->f_hprod_units) { const int32_t st = jit_load_hprod(h); if (st) return st; }
+    const Layout& L = h->model.L;
+    HProdParams hp;
+    std::memset(&hp, 0, sizeof(hp));
+    hp.p.L = L;
+    hp.p.tau = h->d_tau;
+    hp.p.dir = y_dev;
+    hp.p.out = out_dev;
+    hp.vt = v_dev;
+    hp.sigma = obj_weight;
+    int jc = 1;
+    if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
+    for_problem(h->model.problem, [&](auto tag) { jc = hprod_chunk_of<typename decltype(tag)::type>(); });
+    hp.p.nch = (int32_t)((hprod_dirs_per_node(L) + jc - 1) / jc);
+    const int64_t blocks = ((L.N + 1) * (int64_t)hp.p.nch + 255) / 256;
+    if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
+    hp.p.nblocks = (int32_t)blocks;
+    const int32_t st = grow_scratch(h, &h->d_hppartial, h->hppartial_cap, blocks * kMaxNV, fn);
+    if (st) return st;
+    hp.p.partial = h->d_hppartial;
+    hipError_t e = hipErrorInvalidValue;
+    if (h->rt) {
+        void* args[] = {&hp, &x_dev};
+        e = jit_launch(h->f_hprod_units, (int)blocks, 256, 0, h->stream, args);
+        if (e == hipSuccess) e = jit_launch(h->f_hprod_finish, 1, 64, 0, h->stream, args);
+    }
+    for_problem(h->model.problem, [&](auto tag) { e = launch_hprod<typename decltype(tag)::type>(hp, x_dev, h->stream); });
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                            double* Hv_dev) {
+    const int32_t st = hprod_check(h, "ctd_hprod_dev_async", x_dev, y_dev, v_dev, Hv_dev);
+    return st ? st : enqueue_hprod(h, x_dev, y_dev, obj_weight, v_dev, Hv_dev);
+}
+
+// host pointers: x, y and v staged through the handle's x, y and direction buffers
+int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* v, double* Hv) {
+    int32_t st = hprod_check(h, "ctd_hprod", x, y, v, Hv);
+    if (st) return st;
+    const Layout& L = h->model.L;
+    st = ensure_staging(h, false, false);
+    if (st) return st;
+    const size_t len = (size_t)std::max<int64_t>(std::max<int64_t>(L.nvar, L.ncon), 1);
+    if (!h->d_pdir) HIP_TRY(h, hipMalloc((void**)&h->d_pdir, sizeof(double) * len));
+    if (!h->d_pout) HIP_TRY(h, hipMalloc((void**)&h->d_pout, sizeof(double) * len));
+    if (y && !h->d_y) HIP_TRY(h, hipMalloc((void**)&h->d_y, sizeof(double) * L.ncon));
+    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_pdir, v, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
+    if (y) HIP_TRY(h, hipMemcpyAsync(h->d_y, y, sizeof(double) * L.ncon, hipMemcpyHostToDevice, h->stream));
+    st = enqueue_hprod(h, h->d_x, y ? h->d_y : nullptr, obj_weight, h->d_pdir, h->d_pout);
+    if (st) return st;
+    HIP_TRY(h, hipMemcpyAsync(Hv, h->d_pout, sizeof(double) * L.nvar, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CTD_OK;
+}
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {
     if (!h) return CTD_EINVAL;

@@ -1,5 +1,6 @@
-// Matrix-free Jacobian product kernels (ctd_prod_kernels.hpp) of one registry entry (DoubleIntegratorPathOCP).
-#include "ctd_prod_kernels.hpp"
+// Matrix-free Jacobian and Hessian product kernels (ctd_prod_kernels.hpp, ctd_hprod_kernels.hpp) of one registry entry (DoubleIntegratorPathOCP).
+#include "ctd_hprod_kernels.hpp"
 namespace ctd {
 CTD_INSTANTIATE_PROD(DoubleIntegratorPathOCP)
+CTD_INSTANTIATE_HPROD(DoubleIntegratorPathOCP)
 }

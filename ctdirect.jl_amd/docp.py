@@ -483,6 +483,36 @@ class DOCP:
         """jtprod!(nlp, x, w, Jtw): J(x)' w without assembling J (nvar entries); see `jprod`."""
         return self._prod(x, w, out, sync, True)
 
+    def hprod(self, x, y, v, obj_weight=1.0, out=None, sync=True):
+        """hprod!(nlp, x, y, v, Hv; obj_weight): (obj_weight d2 f + sum_i y_i d2 c_i)(x) v without assembling the Hessian (nvar
+        entries).  y = None: the objective-only hprod!(nlp, x, v, Hv; obj_weight).  The Hessian is the exact second derivative
+        of the objective and the constraints (the structural one, whatever the pattern mode).  NumPy inputs use the host entry
+        point; device tensors are enqueued on the handle's stream (`ctd_hprod_dev_async`), followed by a sync when `sync`."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        L = _lib.lib()
+        self._check_x(x)
+        if _is_tensor(x):
+            import torch
+            if out is None:
+                out = torch.empty(nvar, dtype=torch.float64, device=x.device)
+            py = None if y is None else self._dev_ptr(y, ncon, "y")
+            self._ck(L.ctd_hprod_dev_async(self._h, self._dev_ptr(x, nvar, "x"), py, float(obj_weight), self._dev_ptr(v, nvar, "v"),
+                                           self._dev_ptr(out, nvar, "out")))
+            if sync:
+                self.sync()
+            return out
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.size != nvar:
+            raise ValueError(f"v has {v.size} entries, expected {nvar}")
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            if y.size != ncon:
+                raise ValueError(f"y has {y.size} entries, expected {ncon}")
+        out = np.empty(nvar) if out is None else _host_out(out, nvar, "out")
+        self._ck(L.ctd_hprod(self._h, _dp(x), _dp(y), float(obj_weight), _dp(v), _dp(out)))
+        return out
+
     def grad_shard(self, x, g, sync=False):
         """`ctd_grad_shard_dev_async`: the gradient entries of THIS shard's own variables into the full-length device tensor g
         (+ the shard's partial sums of d/dv in the nv tail entries), from a sharded iterate read in place -- no all-gathered x."""

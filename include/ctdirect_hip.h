@@ -388,6 +388,27 @@ int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw)
 int32_t ctd_jprod_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev);
 int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev);
 
+/* Matrix-free Hessian-of-the-Lagrangian products at (x, y) (NLPModels hprod!; the reference leaves the backend empty,
+ * hprod_backend = EmptyADbackend, src/collocation.jl:104-110):
+ *   Hv = (obj_weight H_f(x) + sum_r y_r H_{c_r}(x)) v   (nvar entries, the variable layout of the transcription)
+ * x, v and Hv have nvar entries, y has ncon entries in the row order of ctd_cons.  y == NULL: every multiplier is zero (the
+ * objective-only hprod!(nlp, x, v, Hv; obj_weight)), bit-identical to passing a zero vector.
+ * H is the exact second derivative of what ctd_obj and ctd_cons compute: the Hessian of the STRUCTURAL pattern, whatever the
+ * handle's pattern_mode or value_order -- Mayer and Lagrange terms, boundary and path rows, and the second-order terms through a
+ * free t0 / tf (time grid, step length h, the h K products of the Gauss-Legendre steps) included; kinks (abs, floor, max, min)
+ * follow the conventions of ctd_hess_coord.  On a REFERENCE_MANUAL handle the product therefore includes the entries the manual
+ * pattern drops.  Results are reproducible bit for bit (fixed summation order, no floating-point atomics) and equal for every
+ * pattern_mode / value_order of one transcription.  No device memory proportional to nnzh or nnzj is allocated (scratch: one row
+ * of kMaxNV partial sums per workgroup; the host call stages x, y, v and the result).
+ * Run-time OCPs (ctd_register_ocp) compile their hprod kernels on the first hprod call: make one call before capturing a graph.
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle (step_begin / step_end not
+ * the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL; null x, v or Hv, or Hv equal to x, y or v -> CTD_EINVAL. */
+/* host pointers: return when the result is in the caller's buffer */
+int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* v, double* Hv);
+/* device pointers on the handle's device: enqueue-only on the handle's stream (ctd_sync waits), capturable after one warm call */
+int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                            double* Hv_dev);
+
 /* 1-based (rows[k], cols[k]), k < nnzh, CSC order */
 int32_t ctd_hess_structure(const ctd_handle* h, int64_t* rows, int64_t* cols);
 /* same pattern as 0-based CSC (colptr[nvar + 1], rowval[nnzh]) */
