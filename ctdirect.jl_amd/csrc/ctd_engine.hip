@@ -31,67 +31,38 @@ using namespace ctd;
 
 namespace ctd {
 // the instantiations live in the per-problem translation units
-CTD_EXTERN_LAUNCHERS(GoddardOCP)
-CTD_EXTERN_LAUNCHERS(GoddardAllOCP)
-CTD_EXTERN_LAUNCHERS(DoubleIntegratorPathOCP)
-CTD_EXTERN_LAUNCHERS(QuadrotorOCP)
-CTD_EXTERN_LAUNCHERS(Quadrotor12OCP)
-CTD_EXTERN_LAUNCHERS(StagewiseScalarOCP)
-CTD_EXTERN_LAUNCHERS(EstimateInitialConditionOCP)
-CTD_EXTERN_LAUNCHERS(EstimateRotationRateOCP)
-CTD_EXTERN_LAUNCHERS(LeastSquaresConstraintOCP)
-CTD_EXTERN_LAUNCHERS(DoubleIntegratorFreeT0TfOCP)
-CTD_EXTERN_HESS(GoddardOCP)
-CTD_EXTERN_HESS(GoddardAllOCP)
-CTD_EXTERN_HESS(DoubleIntegratorPathOCP)
-CTD_EXTERN_HESS(QuadrotorOCP)
-CTD_EXTERN_HESS(Quadrotor12OCP)
-CTD_EXTERN_HESS(StagewiseScalarOCP)
-CTD_EXTERN_HESS(EstimateInitialConditionOCP)
-CTD_EXTERN_HESS(EstimateRotationRateOCP)
-CTD_EXTERN_HESS(LeastSquaresConstraintOCP)
-CTD_EXTERN_HESS(DoubleIntegratorFreeT0TfOCP)
-CTD_EXTERN_HESS_STEP(GoddardOCP)
-CTD_EXTERN_HESS_STEP(GoddardAllOCP)
-CTD_EXTERN_HESS_STEP(DoubleIntegratorPathOCP)
-CTD_EXTERN_HESS_STEP(QuadrotorOCP)
-CTD_EXTERN_HESS_STEP(Quadrotor12OCP)
-CTD_EXTERN_HESS_STEP(StagewiseScalarOCP)
-CTD_EXTERN_HESS_STEP(EstimateInitialConditionOCP)
-CTD_EXTERN_HESS_STEP(EstimateRotationRateOCP)
-CTD_EXTERN_HESS_STEP(LeastSquaresConstraintOCP)
-CTD_EXTERN_HESS_STEP(DoubleIntegratorFreeT0TfOCP)
-CTD_EXTERN_ITER(GoddardOCP)
-CTD_EXTERN_ITER(GoddardAllOCP)
-CTD_EXTERN_ITER(DoubleIntegratorPathOCP)
-CTD_EXTERN_ITER(QuadrotorOCP)
-CTD_EXTERN_ITER(Quadrotor12OCP)
-CTD_EXTERN_ITER(StagewiseScalarOCP)
-CTD_EXTERN_ITER(EstimateInitialConditionOCP)
-CTD_EXTERN_ITER(EstimateRotationRateOCP)
-CTD_EXTERN_ITER(LeastSquaresConstraintOCP)
-CTD_EXTERN_ITER(DoubleIntegratorFreeT0TfOCP)
-CTD_EXTERN_PROD(GoddardOCP)
-CTD_EXTERN_PROD(GoddardAllOCP)
-CTD_EXTERN_PROD(DoubleIntegratorPathOCP)
-CTD_EXTERN_PROD(QuadrotorOCP)
-CTD_EXTERN_PROD(Quadrotor12OCP)
-CTD_EXTERN_PROD(StagewiseScalarOCP)
-CTD_EXTERN_PROD(EstimateInitialConditionOCP)
-CTD_EXTERN_PROD(EstimateRotationRateOCP)
-CTD_EXTERN_PROD(LeastSquaresConstraintOCP)
-CTD_EXTERN_PROD(DoubleIntegratorFreeT0TfOCP)
-CTD_EXTERN_HPROD(GoddardOCP)
-CTD_EXTERN_HPROD(GoddardAllOCP)
-CTD_EXTERN_HPROD(DoubleIntegratorPathOCP)
-CTD_EXTERN_HPROD(QuadrotorOCP)
-CTD_EXTERN_HPROD(Quadrotor12OCP)
-CTD_EXTERN_HPROD(StagewiseScalarOCP)
-CTD_EXTERN_HPROD(EstimateInitialConditionOCP)
-CTD_EXTERN_HPROD(EstimateRotationRateOCP)
-CTD_EXTERN_HPROD(LeastSquaresConstraintOCP)
-CTD_EXTERN_HPROD(DoubleIntegratorFreeT0TfOCP)
+#define CTD_EXTERN_ALL(ID, P) \
+    CTD_EXTERN_LAUNCHERS(P) CTD_EXTERN_HESS(P) CTD_EXTERN_HESS_STEP(P) CTD_EXTERN_ITER(P) CTD_EXTERN_PROD(P) CTD_EXTERN_HPROD(P)
+CTD_REGISTRY(CTD_EXTERN_ALL)
 }  // namespace ctd
+
+// A device array the handle owns and frees when it is deleted; cap: the elements allocated.  ensure(n): at least n elements,
+// allocated when the array is smaller (at first use: static tables, host-call staging and the partial sums of calls that are
+// never captured); grow (below): the partial sums of the capturable calls.
+template <class T = double> struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t ensure(int64_t n) {
+        if (p && n <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void**)&p, sizeof(T) * (size_t)(n > 1 ? n : 1));      // (one element at least: never a null output)
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+    int32_t grow(ctd_handle* h, int64_t need, const char* fn);
+};
+
+// the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each, loaded at first use (jit_load)
+enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, kJitFamilies };
+struct JitModule {
+    hipModule_t mod = nullptr;
+    hipFunction_t f[5] = {};        // in the order of the family's name expressions (kJit)
+};
 
 struct ctd_handle {
     Model model;
@@ -104,76 +75,63 @@ struct ctd_handle {
     size_t lds_bytes = 0;
     int grid = 0;
     // static device data
-    double* d_tau = nullptr;
-    uint32_t* d_tmpl = nullptr;
-    uint32_t* d_vtmpl = nullptr;
-    uint16_t* d_pos = nullptr;
-    int64_t* d_edge_idx = nullptr;
-    uint32_t* d_edge_code = nullptr;
+    DevBuf<double> d_tau;
+    DevBuf<uint32_t> d_tmpl, d_vtmpl;
+    DevBuf<uint16_t> d_pos;
+    DevBuf<int64_t> d_edge_idx;
+    DevBuf<uint32_t> d_edge_code;
     // staging for the host-pointer entry points
-    double* d_x = nullptr;
-    double* d_c = nullptr;
-    double* d_vals = nullptr;
+    DevBuf<> d_x, d_c, d_vals;
     // objective
-    double* d_partial = nullptr;
-    double* d_obj = nullptr;
-    double* d_g = nullptr;          // staging for ctd_grad (host pointers)
-    double* d_gpartial = nullptr;   // per-workgroup partial sums of dg/dv
-    int64_t gblocks = 0;            // rows of kMaxNV partial sums d_gpartial holds
+    DevBuf<> d_partial;         // per-workgroup partial sums (batched calls: one set per member)
+    DevBuf<> d_obj;
+    DevBuf<> d_g;               // staging for ctd_grad (host pointers)
+    DevBuf<> d_gpartial;        // per-workgroup partial sums of dg/dv
     int obj_blocks = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // run-time defined OCP (ctd_register_ocp): kernels compiled with hiprtc and launched through the module API
     const RtOcp* rt = nullptr;
-    hipModule_t jit_mod = nullptr, jit_hmod = nullptr;
-    hipFunction_t f_cons_jac = nullptr, f_obj_partial = nullptr, f_obj_finish = nullptr, f_grad_units = nullptr,
-                  f_grad_finish = nullptr, f_hess = nullptr, f_hess_finish = nullptr;
+    JitModule jit[kJitFamilies];
     // Hessian of the Lagrangian: tables are uploaded by the first Hessian call (hess_ready)
     bool hess_ready = false;
     HParams hp;
     int hess_tile = 0;
     size_t hess_lds_bytes = 0;
-    uint32_t *d_htptr = nullptr, *d_hterms = nullptr, *d_hvptr = nullptr, *d_hvterms = nullptr, *d_heptr = nullptr,
-             *d_hevptr = nullptr, *d_heterms = nullptr;
-    int64_t* d_hedge_idx = nullptr;
-    double* d_hpair_c = nullptr;
-    uint32_t *d_hcpos = nullptr, *d_hzpos = nullptr;
+    DevBuf<uint32_t> d_htptr, d_hterms, d_hvptr, d_hvterms, d_heptr, d_hevptr, d_heterms;
+    DevBuf<int64_t> d_hedge_idx;
+    DevBuf<double> d_hpair_c;
+    DevBuf<uint32_t> d_hcpos, d_hzpos;
     // lane-per-step Hessian kernel (ctd_hess_step.hpp): position tables, parameters, the tile kernel's parameters for its edge blocks
-    int32_t *d_hssrc = nullptr, *d_hschunk = nullptr;
-    double* d_hsck = nullptr;
+    DevBuf<int32_t> d_hssrc, d_hschunk;
+    DevBuf<double> d_hsck;
     bool hess_step = false;
     SParams sp{};
     HParams hp_step{};
     size_t hess_step_lds = 0;
-    uint32_t *d_htasks = nullptr, *d_hptasks = nullptr, *d_hbtasks = nullptr;
-    double *d_hpartials = nullptr, *d_y = nullptr, *d_hvals = nullptr;
+    DevBuf<uint32_t> d_htasks, d_hptasks, d_hbtasks;
+    DevBuf<> d_hpartials, d_y, d_hvals;
     // sharded iterate read in place (ctd_set_x_shards): device table of the other shards' buffers, host copy of what it holds
-    XHalo* d_halo = nullptr;
+    DevBuf<XHalo> d_halo;
     XHalo halo_host{};
     // ctd_stitch_c: padded send block and gathered blocks
-    double *d_stitch_send = nullptr, *d_stitch_recv = nullptr;
-    int64_t stitch_cap = 0;
-    // batched callbacks (ctd_*_batch_dev_async): capacity (doubles) of the objective's partial sums, doubles of Hessian partial
-    // sums per member and their capacity -- the buffers grow with the batch; the batched constraint / Jacobian kernel of a
-    // run-time OCP (compiled on first use)
-    int64_t partial_cap = 0, hpart_member = 0, hpart_cap = 0;
+    DevBuf<> d_stitch_send, d_stitch_recv;
+    // batched callbacks (ctd_*_batch_dev_async): doubles of Hessian partial sums per member -- the partial-sum buffers grow with
+    // the batch
+    int64_t hpart_member = 0;
     double out_mb = 0.0;            // megabytes of constraint / Jacobian outputs of one evaluation (the write-through rule, ctd_create)
-    hipModule_t jit_bmod = nullptr;
-    hipFunction_t f_cons_jac_batch = nullptr;
     // matrix-free Jacobian products (ctd_jprod*, ctd_jtprod*): per-workgroup partial sums of d/dv, host-call staging of the
-    // direction and the product (nvar / ncon entries: nothing proportional to nnzj); the product kernels of a run-time OCP
-    double* d_ppartial = nullptr;
-    int64_t ppartial_cap = 0;
-    double *d_pdir = nullptr, *d_pout = nullptr;
-    hipModule_t jit_pmod = nullptr;
-    hipFunction_t f_jprod = nullptr, f_jtprod_units = nullptr, f_jtprod_finish = nullptr;
+    // direction and the product (nvar / ncon entries: nothing proportional to nnzj)
+    DevBuf<> d_ppartial, d_pdir, d_pout;
     // matrix-free Hessian products (ctd_hprod*): their own partial sums (a graph captured over jtprod keeps its buffer), host-call
-    // staging of v and Hv in d_pdir / d_pout and of y in d_y; the hprod kernels of a run-time OCP (a module of their own)
-    double* d_hppartial = nullptr;
-    int64_t hppartial_cap = 0;
-    hipModule_t jit_hpmod = nullptr;
-    hipFunction_t f_hprod_units = nullptr, f_hprod_finish = nullptr;
+    // staging of v and Hv in d_pdir / d_pout and of y in d_y
+    DevBuf<> d_hppartial;
     std::string err;
 };
+
+// write-through stores (emit_store) for launches whose outputs are small: what a kernel leaves dirty in the XCDs' L2s is written
+// back at its end, serial with the next launch.  Outputs up to these many megabytes (MI355X sweeps, profiles/r03_experiments.md)
+constexpr double kWtMB = 64.0;          // constraint / Jacobian
+constexpr double kHessWtMB = 16.0;      // Hessian (gains up to ~10 MB, even at 16, losses from ~80)
 
 static thread_local std::string g_create_err;      // error of this thread's last failed handle-less call (ctd_last_error(NULL))
 
@@ -196,22 +154,54 @@ struct DeviceGuard {
     int prev = -1;
     bool switched = false;
     hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
+    DeviceGuard() = default;
+    explicit DeviceGuard(int dev) { (void)bind(dev); }
+    hipError_t bind(int dev) {
         err = hipGetDevice(&prev);
         if (err == hipSuccess && prev != dev) { err = hipSetDevice(dev); switched = (err == hipSuccess); }
+        return err;
     }
     ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-template <class T> static hipError_t upload(T** dst, const std::vector<T>& src) {
-    if (*dst) { (void)hipFree(*dst); }       // idempotent: a retry after a partial failure (ensure_hess) replaces, never leaks
-    *dst = nullptr;
+// The prologue of every compute call: the handle, then its device -- a host-only handle is refused with CTD_ENODEVICE before
+// any other check (the refusal starts with `fn` where given) -- then the handle's device is current until the end of the
+// scope.  st: the first failure, CTD_OK if none.
+struct OnDevice {
+    DeviceGuard dg;
+    int32_t st = CTD_OK;
+    explicit OnDevice(ctd_handle* h, const char* fn = nullptr) {
+        if (!h) st = CTD_EINVAL;
+        else if (h->device < 0)
+            st = fail(h, CTD_ENODEVICE, std::string(fn ? fn : "") + (fn ? ": " : "") +
+                                            "compute call on a host-only handle (device = -1); there is no CPU fallback");
+        else if (dg.bind(h->device) != hipSuccess) st = fail(h, CTD_EHIP, std::string("dg_.err: ") + hipGetErrorString(dg.err));
+    }
+};
+
+// Grows a partial-sum buffer to `need` elements (batched calls: one set of partial sums per member).  The buffer may still be
+// read by launches in flight, so the handle's stream is drained first -- which a capturing stream cannot do, and nothing may be
+// allocated inside a capture either: the call is refused there.
+template <class T> int32_t DevBuf<T>::grow(ctd_handle* h, int64_t need, const char* fn) {
+    if (need <= cap && p) return CTD_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this batch needs larger partial-sum buffers, which cannot be allocated while the "
+                                   "stream is capturing; make one call with the same batch size before the capture");
+    (void)hipGetLastError();
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, ensure(need));
+    return CTD_OK;
+}
+
+template <class T> static hipError_t upload(DevBuf<T>& dst, const std::vector<T>& src) {
+    dst.release();       // idempotent: a retry after a partial failure (ensure_hess) replaces, never leaks
     if (src.empty()) return hipSuccess;
-    hipError_t e = hipMalloc((void**)dst, src.size() * sizeof(T));
+    const hipError_t e = dst.ensure((int64_t)src.size());
     if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    return hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 static int env_int(const char* name, int dflt) {
@@ -219,25 +209,20 @@ static int env_int(const char* name, int dflt) {
     return (s && *s) ? std::atoi(s) : dflt;
 }
 
-static void free_device(ctd_handle* h) {
-    if (h->device < 0) return;
-    DeviceGuard dg_(h->device);
-    (void)hipStreamSynchronize(h->stream);      // enqueue-only calls may still be running on the tables freed below
-    for (void* p : {(void*)h->d_pos, (void*)h->d_tau, (void*)h->d_tmpl, (void*)h->d_vtmpl, (void*)h->d_edge_idx, (void*)h->d_edge_code,
-                    (void*)h->d_x, (void*)h->d_c, (void*)h->d_vals, (void*)h->d_partial, (void*)h->d_obj, (void*)h->d_g,
-                    (void*)h->d_gpartial, (void*)h->d_htptr, (void*)h->d_hterms, (void*)h->d_hvptr, (void*)h->d_hvterms,
-                    (void*)h->d_heptr, (void*)h->d_hevptr, (void*)h->d_heterms, (void*)h->d_hedge_idx, (void*)h->d_htasks,
-                    (void*)h->d_hptasks, (void*)h->d_hbtasks, (void*)h->d_hpair_c, (void*)h->d_hcpos, (void*)h->d_hzpos, (void*)h->d_hssrc, (void*)h->d_hschunk, (void*)h->d_hsck, (void*)h->d_hpartials, (void*)h->d_y, (void*)h->d_hvals, (void*)h->d_halo, (void*)h->d_stitch_send, (void*)h->d_stitch_recv,
-                    (void*)h->d_ppartial, (void*)h->d_pdir, (void*)h->d_pout, (void*)h->d_hppartial})
-        if (p) (void)hipFree(p);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
-    if (h->jit_hmod) (void)hipModuleUnload(h->jit_hmod);
-    if (h->jit_bmod) (void)hipModuleUnload(h->jit_bmod);
-    if (h->jit_pmod) (void)hipModuleUnload(h->jit_pmod);
-    if (h->jit_hpmod) (void)hipModuleUnload(h->jit_hpmod);
+// Frees the handle and what it holds on its device, on that device: the stream is drained first (enqueue-only calls may still be
+// running on the buffers), the DevBufs free themselves with the handle
+static void destroy_handle(ctd_handle* h) {
+    DeviceGuard dg;
+    if (h->device >= 0) {
+        (void)dg.bind(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        if (h->ev0) (void)hipEventDestroy(h->ev0);
+        if (h->ev1) (void)hipEventDestroy(h->ev1);
+        if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+        for (JitModule& m : h->jit)
+            if (m.mod) (void)hipModuleUnload(m.mod);
+    }
+    delete h;
 }
 
 // ---- run-time compilation of the kernel templates for a registered OCP -------------------------------------------------
@@ -246,7 +231,7 @@ std::string jit_include_dir() {
     const char* env = std::getenv("CTD_JIT_INCLUDE");
     if (env && *env) return env;
     Dl_info info;
-    if (dladdr((const void*)&free_device, &info) && info.dli_fname) {
+    if (dladdr((const void*)&destroy_handle, &info) && info.dli_fname) {
         std::string path(info.dli_fname);
         const size_t slash = path.find_last_of('/');
         return (slash == std::string::npos ? std::string(".") : path.substr(0, slash)) + "/csrc";
@@ -314,7 +299,8 @@ int32_t jit_compile(const RtOcp& ro, const char* header, const std::vector<std::
     return CTD_OK;
 }
 
-// s: stages of a Gauss-Legendre scheme; for the midpoint scheme the controls per step (control_steps)
+// The name expressions of each family.  s: stages of a Gauss-Legendre scheme; for the midpoint scheme the controls per step
+// (control_steps)
 std::vector<std::string> jit_first_exprs(int sc, int s) {
     const std::string P = "ctd::UserOCP", a = std::to_string(sc), b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
     return {"ctd::cons_jac_kernel<" + P + ", " + a + ", " + b + ", false>", "ctd::obj_partial_kernel<" + P + ", " + a + ">",
@@ -325,6 +311,28 @@ std::vector<std::string> jit_hess_exprs(int sc, int s) {
     const std::string P = "ctd::UserOCP", a = std::to_string(sc), b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
     return {"ctd::hess_kernel<" + P + ", " + a + ", " + b + ", false>", "ctd::hess_finish_kernel<" + P + ">"};
 }
+std::vector<std::string> jit_batch_exprs(int sc, int s) {
+    const std::string b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
+    return {"ctd::cons_jac_batch_kernel<ctd::UserOCP, " + std::to_string(sc) + ", " + b + ">"};
+}
+std::vector<std::string> jit_prod_exprs(int sc, int s) {
+    const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
+    return {"ctd::jprod_kernel<ctd::UserOCP, " + a + ", " + b + ">", "ctd::jtprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">",
+            "ctd::jtprod_finish_kernel<ctd::UserOCP>"};
+}
+std::vector<std::string> jit_hprod_exprs(int sc, int s) {
+    const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
+    return {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">", "ctd::hprod_finish_kernel<ctd::UserOCP>"};
+}
+
+// one row per JitFamily: the header, -ffp-contract, the name expressions
+const struct { const char* header; const char* fp_contract; std::vector<std::string> (*exprs)(int sc, int s); } kJit[kJitFamilies] = {
+    {"ctd_kernels.hpp", "off", jit_first_exprs},            // cons_jac, obj_partial, obj_finish, grad_units, grad_finish
+    {"ctd_kernels.hpp", "off", jit_batch_exprs},            // cons_jac_batch
+    {"ctd_prod_kernels.hpp", "off", jit_prod_exprs},        // jprod, jtprod_units, jtprod_finish
+    {"ctd_hprod_kernels.hpp", "off", jit_hprod_exprs},      // hprod_units, hprod_finish
+    {"ctd_hess_kernels.hpp", "fast", jit_hess_exprs},       // hess, hess_finish
+};
 
 // batch: the grid's second dimension (members of a batched launch)
 hipError_t jit_launch(hipFunction_t f, int grid, int block, size_t lds, hipStream_t st, void** args, hipEvent_t e0 = nullptr,
@@ -335,71 +343,40 @@ hipError_t jit_launch(hipFunction_t f, int grid, int block, size_t lds, hipStrea
 }
 }  // namespace
 
-static int32_t jit_load_first(ctd_handle* h) {
+// The kernels of family `fam` of a run-time OCP: compiled (or taken from the cache) and loaded once, nothing for a registry
+// problem.  The first family is loaded by ctd_create, whose errors go to ctd_last_error(NULL).
+static int32_t jit_load(ctd_handle* h, JitFamily fam) {
+    JitModule& m = h->jit[fam];
+    if (!h->rt || m.mod) return CTD_OK;
+    ctd_handle* eh = fam == JIT_FIRST ? nullptr : h;
+    const Layout& L = h->model.L;
     std::string code, err;
     std::vector<std::string> names;
-    const Layout& Lj = h->model.L;
-    int32_t st = jit_compile(*h->rt, "ctd_kernels.hpp", jit_first_exprs(Lj.sc, Lj.sc == SC_MIDPOINT ? Lj.cs : Lj.s), "off", code, names, err);
-    if (st) return fail(nullptr, st, err);
-    HIP_TRY(nullptr, hipModuleLoadData(&h->jit_mod, code.data()));
-    hipFunction_t* f[] = {&h->f_cons_jac, &h->f_obj_partial, &h->f_obj_finish, &h->f_grad_units, &h->f_grad_finish};
-    for (int i = 0; i < 5; ++i) HIP_TRY(nullptr, hipModuleGetFunction(f[i], h->jit_mod, names[i].c_str()));
-    return CTD_OK;
+    const int32_t st = jit_compile(*h->rt, kJit[fam].header, kJit[fam].exprs(L.sc, L.sc == SC_MIDPOINT ? L.cs : L.s), kJit[fam].fp_contract,
+                                   code, names, err);
+    if (st) return fail(eh, st, err);
+    hipError_t e = hipModuleLoadData(&m.mod, code.data());
+    for (size_t i = 0; e == hipSuccess && i < names.size(); ++i) e = hipModuleGetFunction(&m.f[i], m.mod, names[i].c_str());
+    if (e == hipSuccess) return CTD_OK;
+    if (m.mod) (void)hipModuleUnload(m.mod);      // (loaded whole or not at all: a later call tries again)
+    m = JitModule{};
+    return fail(eh, CTD_EHIP, std::string(kJit[fam].header) + " module: " + hipGetErrorString(e));
 }
-// the batched constraint / Jacobian kernel (cons_jac_batch_kernel) of a run-time OCP: compiled at the first batched call
-static int32_t jit_load_batch(ctd_handle* h) {
-    std::string code, err;
-    std::vector<std::string> names;
-    const Layout& Lj = h->model.L;
-    const int s = Lj.sc == SC_MIDPOINT ? Lj.cs : Lj.s;
-    const std::string b = std::to_string((Lj.sc == SC_IRK || Lj.sc == SC_MIDPOINT) && s > 0 ? s : 1);
-    const std::vector<std::string> exprs = {"ctd::cons_jac_batch_kernel<ctd::UserOCP, " + std::to_string(Lj.sc) + ", " + b + ">"};
-    int32_t st = jit_compile(*h->rt, "ctd_kernels.hpp", exprs, "off", code, names, err);
-    if (st) return fail(h, st, err);
-    HIP_TRY(h, hipModuleLoadData(&h->jit_bmod, code.data()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_cons_jac_batch, h->jit_bmod, names[0].c_str()));
-    return CTD_OK;
-}
-// the product kernels (ctd_prod_kernels.hpp) of a run-time OCP: compiled at the first jprod / jtprod call
-static int32_t jit_load_prod(ctd_handle* h) {
-    std::string code, err;
-    std::vector<std::string> names;
-    const Layout& Lj = h->model.L;
-    const std::string a = std::to_string(Lj.sc), b = std::to_string(Lj.sc == SC_IRK && Lj.s > 0 ? Lj.s : 1);
-    const std::vector<std::string> exprs = {"ctd::jprod_kernel<ctd::UserOCP, " + a + ", " + b + ">",
-                                            "ctd::jtprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">",
-                                            "ctd::jtprod_finish_kernel<ctd::UserOCP>"};
-    int32_t st = jit_compile(*h->rt, "ctd_prod_kernels.hpp", exprs, "off", code, names, err);
-    if (st) return fail(h, st, err);
-    HIP_TRY(h, hipModuleLoadData(&h->jit_pmod, code.data()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_jprod, h->jit_pmod, names[0].c_str()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_jtprod_units, h->jit_pmod, names[1].c_str()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_jtprod_finish, h->jit_pmod, names[2].c_str()));
-    return CTD_OK;
-}
-// the Hessian product kernels (ctd_hprod_kernels.hpp) of a run-time OCP: compiled at the first hprod call
-static int32_t jit_load_hprod(ctd_handle* h) {
-    std::string code, err;
-    std::vector<std::string> names;
-    const Layout& Lj = h->model.L;
-    const std::string a = std::to_string(Lj.sc), b = std::to_string(Lj.sc == SC_IRK && Lj.s > 0 ? Lj.s : 1);
-    const std::vector<std::string> exprs = {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">",
-                                            "ctd::hprod_finish_kernel<ctd::UserOCP>"};
-    int32_t st = jit_compile(*h->rt, "ctd_hprod_kernels.hpp", exprs, "off", code, names, err);
-    if (st) return fail(h, st, err);
-    HIP_TRY(h, hipModuleLoadData(&h->jit_hpmod, code.data()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_hprod_units, h->jit_hpmod, names[0].c_str()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_hprod_finish, h->jit_hpmod, names[1].c_str()));
-    return CTD_OK;
-}
-static int32_t jit_load_hess(ctd_handle* h) {
-    std::string code, err;
-    std::vector<std::string> names;
-    int32_t st = jit_compile(*h->rt, "ctd_hess_kernels.hpp", jit_hess_exprs(h->model.L.sc, h->model.L.sc == SC_MIDPOINT ? h->model.L.cs : h->model.L.s), "fast", code, names, err);
-    if (st) return fail(h, st, err);
-    HIP_TRY(h, hipModuleLoadData(&h->jit_hmod, code.data()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_hess, h->jit_hmod, names[0].c_str()));
-    HIP_TRY(h, hipModuleGetFunction(&h->f_hess_finish, h->jit_hmod, names[1].c_str()));
+
+// A host array of a host-pointer call and the handle's buffer that stages it: n doubles (a null host pointer is not staged)
+template <class T> struct Staged { T* host; DevBuf<>& buf; int64_t n; };
+
+// The host-pointer entry points, after their prologue and checks: the staging buffers allocated at first use, the inputs copied
+// in, the enqueue, the outputs copied back -- every copy on the handle's stream -- and one synchronisation
+template <class Enqueue>
+static int32_t host_call(ctd_handle* h, std::initializer_list<Staged<const double>> in, Enqueue&& enqueue,
+                         std::initializer_list<Staged<double>> out) {
+    for (const auto& a : in) if (a.host) HIP_TRY(h, a.buf.ensure(a.n));
+    for (const auto& a : out) if (a.host) HIP_TRY(h, a.buf.ensure(a.n));
+    for (const auto& a : in) if (a.host) HIP_TRY(h, hipMemcpyAsync(a.buf.p, a.host, sizeof(double) * a.n, hipMemcpyHostToDevice, h->stream));
+    if (const int32_t st = enqueue()) return st;
+    for (const auto& a : out) if (a.host) HIP_TRY(h, hipMemcpyAsync(a.host, a.buf.p, sizeof(double) * a.n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return CTD_OK;
 }
 
@@ -425,7 +402,7 @@ const char* ctd_last_error(const ctd_handle* h) { return h ? h->err.c_str() : g_
 int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     if (!desc || !out) return fail(nullptr, CTD_EINVAL, "ctd_create: null argument");
     *out = nullptr;
-    struct Del { void operator()(ctd_handle* p) const { if (p) { free_device(p); delete p; } } };
+    struct Del { void operator()(ctd_handle* p) const { if (p) destroy_handle(p); } };
     std::unique_ptr<ctd_handle, Del> h(new (std::nothrow) ctd_handle());
     if (!h) return fail(nullptr, CTD_ENOMEM, "ctd_create: out of memory");
     HostDesc hd{desc->problem, desc->scheme, desc->pattern_mode, desc->grid_size, desc->time_grid, desc->time_grid_len,
@@ -483,7 +460,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     // the number of rounds, the steps are spread evenly over them: 40 steps = 2001 tiles, 28.3 -> 26.9 us, optimized pattern
     // 20.3 -> 17.9; N = 200 000: 79.9 -> 74.3 (profiles/r03_experiments.md).  Only ever a LARGER tile than the rule's.
     const bool long_mid = mo.L.sc == SC_MIDPOINT && mo.L.cs == 1;      // midpoint and both Euler schemes (one point per step): long-grid rule only
-    if (desc->device >= 0 && !h->rt && env_int("CTD_TILE", 0) <= 0 && env_int("CTD_ROUND_TILES", 1) && mo.nch_dyn <= 1 && (mo.L.sc == SC_IRK || long_mid) && h->tile >= 16) {
+    if (desc->device >= 0 && !h->rt && env_int("CTD_TILE", 0) <= 0 && mo.nch_dyn <= 1 && (mo.L.sc == SC_IRK || long_mid) && h->tile >= 16) {
         DeviceGuard dgq(desc->device);
         if (dgq.err == hipSuccess) {
             auto resident = [&](int tile, size_t& lds) {
@@ -536,14 +513,8 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     }
     h->grid = h->kp.ntiles + h->kp.has_edge;
     h->kp.debug_stop = debug_stop;
-    {   // write-through stores (emit_store) for launches whose outputs are small: what a kernel leaves dirty in the XCDs' L2s is written
-        // back at its end, serial with the next launch.  CTD_WT_STORE: 0 never, 1 always, unset: outputs of this handle up to
-        // CTD_WT_MB megabytes (default from the MI355X sweep in profiles/r03_experiments.md)
-        const int wt = env_int("CTD_WT_STORE", -1);
-        const double out_mb = 8.0 * ((double)(h->step_end - h->step_begin) * (mo.L.cb + mo.Lseg + (double)mo.L.nv * mo.vr)) / 1.0e6;
-        h->kp.wt_store = wt >= 0 ? (wt ? 1 : 0) : (out_mb <= (double)env_int("CTD_WT_MB", 64) ? 1 : 0);
-        h->out_mb = out_mb;
-    }
+    h->out_mb = 8.0 * ((double)(h->step_end - h->step_begin) * (mo.L.cb + mo.Lseg + (double)mo.L.nv * mo.vr)) / 1.0e6;
+    h->kp.wt_store = h->out_mb <= kWtMB ? 1 : 0;
     h->device = desc->device;
     if (h->device >= 0) {
         int ndev = 0;
@@ -558,14 +529,14 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
         // could compute tau_i = i / N themselves, but an FP64 division is ~35 dependent instructions on the evaluating lane's
         // critical path while the table load is issued together with the loads of x (the values are identical: the host
         // fills the table with the same division).
-        HIP_TRY(nullptr, upload(&hp->d_tau, mo.tau));
-        HIP_TRY(nullptr, upload(&hp->d_tmpl, mo.tmpl));
-        HIP_TRY(nullptr, upload(&hp->d_vtmpl, mo.vtmpl));
-        HIP_TRY(nullptr, upload(&hp->d_edge_idx, mo.edge_idx));
-        HIP_TRY(nullptr, upload(&hp->d_edge_code, mo.edge_code));
-        hp->kp.tau = hp->d_tau;
-        hp->kp.tmpl = hp->d_tmpl;
-        hp->kp.vtmpl = hp->d_vtmpl;
+        HIP_TRY(nullptr, upload(hp->d_tau, mo.tau));
+        HIP_TRY(nullptr, upload(hp->d_tmpl, mo.tmpl));
+        HIP_TRY(nullptr, upload(hp->d_vtmpl, mo.vtmpl));
+        HIP_TRY(nullptr, upload(hp->d_edge_idx, mo.edge_idx));
+        HIP_TRY(nullptr, upload(hp->d_edge_code, mo.edge_code));
+        hp->kp.tau = hp->d_tau.p;
+        hp->kp.tmpl = hp->d_tmpl.p;
+        hp->kp.vtmpl = hp->d_vtmpl.p;
         // early emission (ctd_layout.hpp KParams::pos): direct tiles of the Gauss-Legendre schemes, when the lead wave can hold one
         // lane per early output of a step and the late positions fit the workgroup.  OFF by default (CTD_EARLY=1 switches it on):
         // measured on MI355X it LOSES -- Goddard GL2 N = 10 000: 8.4 us against 6.2, GL3 optimized pattern 28.8 against 20.1
@@ -579,23 +550,22 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
             const int early_lanes = mo.n_early + mo.c_early + mo.L.nv * mo.vr_early;
             if (env_int("CTD_EARLY", 0) && mo.n_early > 0 && !hp->rt && mo.fused && hp->tile <= 32 && leadbase + 64 <= hp->block && early_lanes <= 64 &&
                 mo.n_late > 0 && mo.n_late <= hp->block) {
-                HIP_TRY(nullptr, upload(&hp->d_pos, mo.pos_order));
-                hp->kp.pos = hp->d_pos;
+                HIP_TRY(nullptr, upload(hp->d_pos, mo.pos_order));
+                hp->kp.pos = hp->d_pos.p;
                 hp->kp.n_late = mo.n_late; hp->kp.n_early = mo.n_early; hp->kp.c_early = mo.c_early; hp->kp.vr_early = mo.vr_early;
                 hp->kp.div_late = make_fastdiv((uint32_t)mo.n_late);
             }
         }
-        hp->kp.edge_idx = hp->d_edge_idx;
-        hp->kp.edge_code = hp->d_edge_code;
+        hp->kp.edge_idx = hp->d_edge_idx.p;
+        hp->kp.edge_code = hp->d_edge_code.p;
         hp->obj_blocks = 256;
-        HIP_TRY(nullptr, hipMalloc((void**)&hp->d_partial, sizeof(double) * hp->obj_blocks));
-        hp->partial_cap = hp->obj_blocks;
-        HIP_TRY(nullptr, hipMalloc((void**)&hp->d_obj, sizeof(double)));
+        HIP_TRY(nullptr, hp->d_partial.ensure(hp->obj_blocks));
+        HIP_TRY(nullptr, hp->d_obj.ensure(1));
         HIP_TRY(nullptr, hipEventCreate(&hp->ev0));
         HIP_TRY(nullptr, hipEventCreate(&hp->ev1));
         if (hp->rt) {
             if (hp->lds_bytes > 64 * 1024) return fail(nullptr, CTD_EINVAL, "ctd_create: one step of this run-time OCP does not fit 64 KiB of LDS");
-            int32_t jst = jit_load_first(hp);
+            const int32_t jst = jit_load(hp, JIT_FIRST);
             if (jst) return jst;
         }
         // Multi-tile workgroups (staged driver only; KParams::wg_stride): when the tiles need several rounds of resident
@@ -611,7 +581,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
                 if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hp->device) != hipSuccess) cus = 256;
                 if (per_cu == 0) {
                     if (hp->rt) {
-                        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hp->f_cons_jac, hp->block, hp->lds_bytes) != hipSuccess) per_cu = 0;
+                        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hp->jit[JIT_FIRST].f[0], hp->block, hp->lds_bytes) != hipSuccess) per_cu = 0;
                     } else {
                         for_problem(mo.problem, [&](auto tag) {
                             using P = typename decltype(tag)::type;
@@ -669,8 +639,7 @@ int32_t ctd_jit_check(int32_t problem_id, int32_t scheme) {
 
 int32_t ctd_destroy(ctd_handle* h) {
     if (!h) return CTD_EINVAL;
-    free_device(h);
-    delete h;
+    destroy_handle(h);
     return CTD_OK;
 }
 
@@ -849,11 +818,11 @@ int32_t ctd_set_x_shards(ctd_handle* h, int32_t n_shards, const int64_t* step_be
     t.vbegin[n_shards] = L.v_off;       // the last shard also owns the final node; v is replicated
     if (h->kp.halo && std::memcmp(&t, &h->halo_host, sizeof(XHalo)) == 0) return CTD_OK;
     DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
-    if (!h->d_halo) HIP_TRY(h, hipMalloc((void**)&h->d_halo, sizeof(XHalo)));
+    HIP_TRY(h, h->d_halo.ensure(1));
     HIP_TRY(h, hipStreamSynchronize(h->stream));           // launches in flight still read the old table
-    HIP_TRY(h, hipMemcpy(h->d_halo, &t, sizeof(XHalo), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_halo.p, &t, sizeof(XHalo), hipMemcpyHostToDevice));
     h->halo_host = t;
-    h->kp.halo = h->d_halo;
+    h->kp.halo = h->d_halo.p;
     h->kp.near = make_xnear(t, L.blk, L.N, L.v_off);
     return CTD_OK;
 }
@@ -921,23 +890,20 @@ int32_t ctd_stitch_c(ctd_handle* h, void* nccl_comm, int32_t n_ranks, int32_t ra
         return check(g_nccl_allgather(c_dev + rank * S, c_dev, (size_t)S, kNcclDouble, nccl_comm, h->stream), "ncclAllGather");
     }
     const int64_t smax = ((N + G - 1) / G) * L.cb + tail;
-    if (h->stitch_cap < (int64_t)G * smax) {
-        if (h->d_stitch_send) (void)hipFree(h->d_stitch_send);
-        if (h->d_stitch_recv) (void)hipFree(h->d_stitch_recv);
-        h->d_stitch_send = h->d_stitch_recv = nullptr;
-        h->stitch_cap = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->d_stitch_send, sizeof(double) * smax));
-        HIP_TRY(h, hipMalloc((void**)&h->d_stitch_recv, sizeof(double) * G * smax));
-        HIP_TRY(h, hipMemsetAsync(h->d_stitch_send, 0, sizeof(double) * smax, h->stream));
-        h->stitch_cap = (int64_t)G * smax;
+    if (h->d_stitch_recv.cap < (int64_t)G * smax) {
+        h->d_stitch_send.release();
+        h->d_stitch_recv.release();
+        HIP_TRY(h, h->d_stitch_send.ensure(smax));
+        HIP_TRY(h, h->d_stitch_recv.ensure((int64_t)G * smax));
+        HIP_TRY(h, hipMemsetAsync(h->d_stitch_send.p, 0, sizeof(double) * smax, h->stream));
     }
     const int64_t own = (h->step_end - h->step_begin) * L.cb, mytail = rank + 1 == G ? tail : 0;
     const int64_t np = own + mytail;
-    stitch_pack_kernel<<<(unsigned)((np + 255) / 256), 256, 0, h->stream>>>(c_dev, h->d_stitch_send, h->step_begin * L.cb, own, N * L.cb, mytail);
+    stitch_pack_kernel<<<(unsigned)((np + 255) / 256), 256, 0, h->stream>>>(c_dev, h->d_stitch_send.p, h->step_begin * L.cb, own, N * L.cb, mytail);
     HIP_TRY(h, hipGetLastError());
-    const int32_t st = check(g_nccl_allgather(h->d_stitch_send, h->d_stitch_recv, (size_t)smax, kNcclDouble, nccl_comm, h->stream), "ncclAllGather");
+    const int32_t st = check(g_nccl_allgather(h->d_stitch_send.p, h->d_stitch_recv.p, (size_t)smax, kNcclDouble, nccl_comm, h->stream), "ncclAllGather");
     if (st) return st;
-    stitch_unpack_kernel<<<(unsigned)((L.ncon + 255) / 256), 256, 0, h->stream>>>(h->d_stitch_recv, c_dev, L.ncon, N, L.cb, G, smax);
+    stitch_unpack_kernel<<<(unsigned)((L.ncon + 255) / 256), 256, 0, h->stream>>>(h->d_stitch_recv.p, c_dev, L.ncon, N, L.cb, G, smax);
     HIP_TRY(h, hipGetLastError());
     return CTD_OK;
 }
@@ -1003,7 +969,7 @@ int32_t ctd_launch_info(const ctd_handle* h, int64_t* o) {
         DeviceGuard dg(h->device);
         int per_cu = 0;
         if (dg.err == hipSuccess) {
-            if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->f_cons_jac, h->block, h->lds_bytes) != hipSuccess) per_cu = 0; }
+            if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit[JIT_FIRST].f[0], h->block, h->lds_bytes) != hipSuccess) per_cu = 0; }
             else for_problem(h->model.problem, [&](auto tag) {
                 using P = typename decltype(tag)::type;
                 per_cu = occupancy_cons_jac<P>(h->model.L.sc, h->kp, h->block, h->lds_bytes);
@@ -1025,10 +991,9 @@ struct Batch {
 
 static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_dev, double* vals_dev, hipEvent_t te0 = nullptr,
                                 hipEvent_t te1 = nullptr, const Batch* bt = nullptr) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x_dev) return fail(h, CTD_EINVAL, "x is null");
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     KParams kp = h->kp;
     kp.c = c_dev;
     kp.vals = vals_dev;
@@ -1037,11 +1002,11 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     if (bt) {      // the batched instantiation of the kernel: grid (tiles, members)
         BatchLd bl{bt->ldx, bt->ldc, bt->ldv};
         // write-through stores by the rule of ctd_create, applied to what the whole LAUNCH writes (all members)
-        if (env_int("CTD_WT_STORE", -1) < 0) kp.wt_store = h->out_mb * bt->n <= (double)env_int("CTD_WT_MB", 64) ? 1 : 0;
+        kp.wt_store = h->out_mb * bt->n <= kWtMB ? 1 : 0;
         if (h->rt) {
-            if (!h->f_cons_jac_batch) { const int32_t jst = jit_load_batch(h); if (jst) return jst; }
+            if (const int32_t jst = jit_load(h, JIT_BATCH)) return jst;
             void* args[] = {&kp, &x_dev, &bl};
-            e = jit_launch(h->f_cons_jac_batch, h->grid, h->block, h->lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
+            e = jit_launch(h->jit[JIT_BATCH].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
         }
         for_problem(h->model.problem, [&](auto tag) {
             using P = typename decltype(tag)::type;
@@ -1052,7 +1017,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     }
     if (h->rt) {
         void* args[] = {&kp, &x_dev};
-        e = jit_launch(h->f_cons_jac, h->grid, h->block, h->lds_bytes, h->stream, args, te0, te1);
+        e = jit_launch(h->jit[JIT_FIRST].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, te0, te1);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1090,29 +1055,14 @@ int32_t ctd_cons_jac_dev(ctd_handle* h, const double* x_dev, double* c_dev, doub
     return ctd_sync(h);
 }
 
-static int32_t ensure_staging(ctd_handle* h, bool need_c, bool need_vals) {
-    const Model& mo = h->model;
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
-    if (!h->d_x) HIP_TRY(h, hipMalloc((void**)&h->d_x, sizeof(double) * mo.L.nvar));
-    if (need_c && !h->d_c) HIP_TRY(h, hipMalloc((void**)&h->d_c, sizeof(double) * mo.L.ncon));
-    if (need_vals && !h->d_vals) HIP_TRY(h, hipMalloc((void**)&h->d_vals, sizeof(double) * (mo.nnzj > 0 ? mo.nnzj : 1)));
-    return CTD_OK;
-}
-
 static int32_t host_cons_jac(ctd_handle* h, const double* x, double* c, double* vals) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x) return fail(h, CTD_EINVAL, "x is null");
     const Model& mo = h->model;
-    int32_t st = ensure_staging(h, c != nullptr, vals != nullptr);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * mo.L.nvar, hipMemcpyHostToDevice, h->stream));
-    st = enqueue_cons_jac(h, h->d_x, c ? h->d_c : nullptr, vals ? h->d_vals : nullptr);
-    if (st) return st;
-    if (c) HIP_TRY(h, hipMemcpyAsync(c, h->d_c, sizeof(double) * mo.L.ncon, hipMemcpyDeviceToHost, h->stream));
-    if (vals) HIP_TRY(h, hipMemcpyAsync(vals, h->d_vals, sizeof(double) * mo.nnzj, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CTD_OK;
+    return host_call(h, {{x, h->d_x, mo.L.nvar}},
+                     [&] { return enqueue_cons_jac(h, h->d_x.p, c ? h->d_c.p : nullptr, vals ? h->d_vals.p : nullptr); },
+                     {{c, h->d_c, mo.L.ncon}, {vals, h->d_vals, mo.nnzj}});
 }
 
 int32_t ctd_host_alloc(void** ptr, size_t bytes) {
@@ -1143,46 +1093,26 @@ int32_t ctd_cons_jac(ctd_handle* h, const double* x, double* c, double* vals) {
 // kernel parameters of the objective pass; returns the quadrature workgroups (0 for a Mayer-only cost)
 static int fill_obj_params(ctd_handle* h, double* f_dev, ObjParams& op);
 
-// Grows a partial-sum buffer of the handle to `need` doubles (batched calls: one set of partial sums per member).  The buffer
-// may still be read by launches in flight, so the handle's stream is drained first -- which a capturing stream cannot do, and
-// nothing may be allocated inside a capture either: the call is refused there.
-static int32_t grow_scratch(ctd_handle* h, double** buf, int64_t& cap, int64_t need, const char* fn) {
-    if (need <= cap && *buf) return CTD_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": this batch needs larger partial-sum buffers, which cannot be allocated while the "
-                                   "stream is capturing; make one call with the same batch size before the capture");
-    (void)hipGetLastError();
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    cap = 0;
-    HIP_TRY(h, hipMalloc((void**)buf, sizeof(double) * (size_t)need));
-    cap = need;
-    return CTD_OK;
-}
-
 static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev, const Batch* bt = nullptr) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x_dev || !f_dev) return fail(h, CTD_EINVAL, "null argument");
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     const Layout& L = h->model.L;
     ObjParams op;
     const int blocks = fill_obj_params(h, f_dev, op);
     const bool lagrange = h->model.info.lagrange;
     const int nb = bt ? bt->n : 1;
     if (bt) {
-        const int32_t st = grow_scratch(h, &h->d_partial, h->partial_cap, (int64_t)nb * (blocks > 0 ? blocks : 1), "ctd_obj_batch_dev_async");
+        const int32_t st = h->d_partial.grow(h, (int64_t)nb * (blocks > 0 ? blocks : 1), "ctd_obj_batch_dev_async");
         if (st) return st;
-        op.partial = h->d_partial;
+        op.partial = h->d_partial.p;
         op.ldx = bt->ldx;
     }
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&op, &x_dev};
-        e = lagrange ? jit_launch(h->f_obj_partial, blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
-        if (e == hipSuccess) e = jit_launch(h->f_obj_finish, 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
+        e = lagrange ? jit_launch(h->jit[JIT_FIRST].f[1], blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
+        if (e == hipSuccess) e = jit_launch(h->jit[JIT_FIRST].f[2], 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1196,13 +1126,13 @@ static int fill_obj_params(ctd_handle* h, double* f_dev, ObjParams& op) {
     const Layout& L = h->model.L;
     std::memset(&op, 0, sizeof(op));
     op.L = L;
-    op.tau = h->d_tau;
+    op.tau = h->d_tau.p;
     const bool last = h->step_end == L.N;
     // quadrature units: trapeze sums over nodes (node N belongs to the last shard), the others over steps
     op.unit_begin = h->step_begin;
     op.unit_end = (L.sc == SC_TRAPEZE && last) ? L.N + 1 : h->step_end;
     op.add_mayer = last ? 1 : 0;
-    op.partial = h->d_partial;
+    op.partial = h->d_partial.p;
     op.out = f_dev;
     op.halo = h->kp.halo;
     op.near = h->kp.near;
@@ -1219,11 +1149,9 @@ int32_t ctd_obj_dev_async(ctd_handle* h, const double* x_dev, double* f_dev) { r
 
 int32_t ctd_obj_dev(ctd_handle* h, const double* x_dev, double* f_host) {
     if (h && !f_host) return fail(h, CTD_EINVAL, "null argument");
-    int32_t st = enqueue_obj(h, x_dev, h ? h->d_obj : nullptr);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpyAsync(f_host, h->d_obj, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CTD_OK;
+    const OnDevice on(h);
+    if (on.st) return on.st;
+    return host_call(h, {}, [&] { return enqueue_obj(h, x_dev, h->d_obj.p); }, {{f_host, h->d_obj, 1}});
 }
 
 static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, GradParams* only_params = nullptr, bool shard = false,
@@ -1245,13 +1173,12 @@ __global__ void zero_rows_kernel(double* __restrict__ p, int64_t ld, int64_t len
 }
 
 static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, GradParams* only_params, bool shard, const Batch* bt) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x_dev || !g_dev) return fail(h, CTD_EINVAL, "null argument");
     // ctd_grad*: the gradient of the WHOLE objective (O(nvar) work on every rank), from the x it is given -- a whole iterate.
     // ctd_grad_shard_dev_async (shard = true): the quadrature units of this handle's steps only (the last shard also the final node),
     // neighbours' blocks through the shard table like the other callbacks: the shard's own entries of g + its partial d/dv
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     const Layout& L = h->model.L;
     const bool last = h->step_end == L.N, first = h->step_begin == 0;
     const int64_t all_units = (L.sc == SC_IRK) ? L.N : L.N + 1;
@@ -1260,22 +1187,15 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     const int blocks = (int)((units + 255) / 256);
     const int nb = bt ? bt->n : 1;
     if (bt) {
-        int64_t cap = h->d_gpartial ? h->gblocks * kMaxNV : 0;
-        const int32_t st = grow_scratch(h, &h->d_gpartial, cap, (int64_t)nb * blocks * kMaxNV, "ctd_grad_batch_dev_async");
+        const int32_t st = h->d_gpartial.grow(h, (int64_t)nb * blocks * kMaxNV, "ctd_grad_batch_dev_async");
         if (st) return st;
-        h->gblocks = cap / kMaxNV;
-    } else if (!h->d_gpartial || h->gblocks < blocks) {
-        if (h->d_gpartial) (void)hipFree(h->d_gpartial);
-        h->d_gpartial = nullptr;
-        HIP_TRY(h, hipMalloc((void**)&h->d_gpartial, sizeof(double) * (size_t)blocks * kMaxNV));
-        h->gblocks = blocks;
-    }
+    } else HIP_TRY(h, h->d_gpartial.ensure((int64_t)blocks * kMaxNV));      // (neither drained nor refused inside a capture)
     GradParams gp;
     std::memset(&gp, 0, sizeof(gp));
     gp.L = L;
-    gp.tau = h->d_tau;
+    gp.tau = h->d_tau.p;
     gp.g = g_dev;
-    gp.partial = h->d_gpartial;
+    gp.partial = h->d_gpartial.p;
     gp.nblocks = blocks;
     gp.unit_begin = ub; gp.unit_end = ue;
     gp.owns_first = (!shard || first) ? 1 : 0;
@@ -1308,8 +1228,8 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&gp, &x_dev};
-        e = lagrange ? jit_launch(h->f_grad_units, blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
-        if (e == hipSuccess) e = jit_launch(h->f_grad_finish, 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
+        e = lagrange ? jit_launch(h->jit[JIT_FIRST].f[3], blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
+        if (e == hipSuccess) e = jit_launch(h->jit[JIT_FIRST].f[4], 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1320,25 +1240,18 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
 }
 
 int32_t ctd_grad(ctd_handle* h, const double* x, double* g) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x || !g) return fail(h, CTD_EINVAL, "null argument");
-    int32_t st = ensure_staging(h, false, false);
-    if (st) return st;
     const int64_t nvar = h->model.L.nvar;
-    if (!h->d_g) HIP_TRY(h, hipMalloc((void**)&h->d_g, sizeof(double) * nvar));
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * nvar, hipMemcpyHostToDevice, h->stream));
-    st = ctd_grad_dev(h, h->d_x, h->d_g);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpy(g, h->d_g, sizeof(double) * nvar, hipMemcpyDeviceToHost));
-    return CTD_OK;
+    return host_call(h, {{x, h->d_x, nvar}}, [&] { return enqueue_grad(h, h->d_x.p, h->d_g.p); }, {{g, h->d_g, nvar}});
 }
 
 // ---- matrix-free Jacobian products: jprod!(nlp, x, v, Jv), jtprod!(nlp, x, w, Jtw) -------------------------------------
-// ctd_prod_kernels.hpp.  Checks in this order: handle, device (CTD_ENODEVICE), whole-grid handle, then pointers (CTD_EINVAL).
-static int32_t prod_check(ctd_handle* h, const char* fn, const double* x, const double* d, const double* out) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, std::string(fn) + ": compute call on a host-only handle (device = -1); there is no CPU fallback");
+// ctd_prod_kernels.hpp.  Checks in this order: handle, device (CTD_ENODEVICE) -- the prologue, OnDevice(h, fn) --, whole-grid
+// handle, then pointers (CTD_EINVAL).  The enqueue runs under the caller's prologue.
+static int32_t prod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* d, const double* out) {
+    if (on.st) return on.st;
     if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
         return fail(h, CTD_EINVAL, std::string(fn) + ": products need a handle of the whole grid; sharded products (step_begin / step_end, "
                                    "ctd_set_x_shards) are not supported");
@@ -1352,20 +1265,19 @@ static int prod_chunk_rt(const RtOcp& ro) { return ro.info.n >= 8 ? 2 : (ro.dc <
 
 static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, const double* d_dev, double* out_dev) {
     const char* fn = transpose ? "ctd_jtprod" : "ctd_jprod";
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
-    if (h->rt && !h->f_jprod) { const int32_t st = jit_load_prod(h); if (st) return st; }
+    if (const int32_t st = jit_load(h, JIT_PROD)) return st;
     const Layout& L = h->model.L;
     ProdParams pp;
     std::memset(&pp, 0, sizeof(pp));
     pp.L = L;
-    pp.tau = h->d_tau;
+    pp.tau = h->d_tau.p;
     pp.dir = d_dev;
     pp.out = out_dev;
     hipError_t e = hipErrorInvalidValue;
     if (!transpose) {
         if (h->rt) {
             void* args[] = {&pp, &x_dev};
-            e = jit_launch(h->f_jprod, (int)((L.N + 1 + 255) / 256), 256, 0, h->stream, args);
+            e = jit_launch(h->jit[JIT_PROD].f[0], (int)((L.N + 1 + 255) / 256), 256, 0, h->stream, args);
         }
         for_problem(h->model.problem, [&](auto tag) { e = launch_jprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
     } else {
@@ -1376,13 +1288,13 @@ static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, 
         const int64_t blocks = ((L.N + 1) * (int64_t)pp.nch + 255) / 256;
         if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
         pp.nblocks = (int32_t)blocks;
-        const int32_t st = grow_scratch(h, &h->d_ppartial, h->ppartial_cap, blocks * kMaxNV, fn);
+        const int32_t st = h->d_ppartial.grow(h, blocks * kMaxNV, fn);
         if (st) return st;
-        pp.partial = h->d_ppartial;
+        pp.partial = h->d_ppartial.p;
         if (h->rt) {
             void* args[] = {&pp, &x_dev};
-            e = jit_launch(h->f_jtprod_units, (int)blocks, 256, 0, h->stream, args);
-            if (e == hipSuccess) e = jit_launch(h->f_jtprod_finish, 1, 64, 0, h->stream, args);
+            e = jit_launch(h->jit[JIT_PROD].f[1], (int)blocks, 256, 0, h->stream, args);
+            if (e == hipSuccess) e = jit_launch(h->jit[JIT_PROD].f[2], 1, 64, 0, h->stream, args);
         }
         for_problem(h->model.problem, [&](auto tag) { e = launch_jtprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
     }
@@ -1391,40 +1303,35 @@ static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, 
 }
 
 int32_t ctd_jprod_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
-    const int32_t st = prod_check(h, "ctd_jprod_dev_async", x_dev, v_dev, Jv_dev);
+    const OnDevice on(h, "ctd_jprod_dev_async");
+    const int32_t st = prod_check(on, h, "ctd_jprod_dev_async", x_dev, v_dev, Jv_dev);
     return st ? st : enqueue_prod(h, false, x_dev, v_dev, Jv_dev);
 }
 int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
-    const int32_t st = prod_check(h, "ctd_jtprod_dev_async", x_dev, w_dev, Jtw_dev);
+    const OnDevice on(h, "ctd_jtprod_dev_async");
+    const int32_t st = prod_check(on, h, "ctd_jtprod_dev_async", x_dev, w_dev, Jtw_dev);
     return st ? st : enqueue_prod(h, true, x_dev, w_dev, Jtw_dev);
 }
 
-// host pointers: staged through the handle's x buffer and two vectors of max(nvar, ncon) entries
+// host pointers: staged through the handle's x buffer and two vectors of nvar / ncon entries
 static int32_t host_prod(ctd_handle* h, bool transpose, const double* x, const double* d, double* out) {
-    const int32_t st0 = prod_check(h, transpose ? "ctd_jtprod" : "ctd_jprod", x, d, out);
-    if (st0) return st0;
+    const char* fn = transpose ? "ctd_jtprod" : "ctd_jprod";
+    const OnDevice on(h, fn);
+    const int32_t st = prod_check(on, h, fn, x, d, out);
+    if (st) return st;
     const Layout& L = h->model.L;
-    const int64_t nin = transpose ? L.ncon : L.nvar, nout = transpose ? L.nvar : L.ncon;
-    int32_t st = ensure_staging(h, false, false);
-    if (st) return st;
-    const size_t len = (size_t)std::max<int64_t>(std::max<int64_t>(L.nvar, L.ncon), 1);
-    if (!h->d_pdir) HIP_TRY(h, hipMalloc((void**)&h->d_pdir, sizeof(double) * len));
-    if (!h->d_pout) HIP_TRY(h, hipMalloc((void**)&h->d_pout, sizeof(double) * len));
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_pdir, d, sizeof(double) * nin, hipMemcpyHostToDevice, h->stream));
-    st = enqueue_prod(h, transpose, h->d_x, h->d_pdir, h->d_pout);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_pout, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CTD_OK;
+    return host_call(h, {{x, h->d_x, L.nvar}, {d, h->d_pdir, transpose ? L.ncon : L.nvar}},
+                     [&] { return enqueue_prod(h, transpose, h->d_x.p, h->d_pdir.p, h->d_pout.p); },
+                     {{out, h->d_pout, transpose ? L.nvar : L.ncon}});
 }
 int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv) { return host_prod(h, false, x, v, Jv); }
 int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw) { return host_prod(h, true, x, w, Jtw); }
 
 // ---- matrix-free Hessian products: hprod!(nlp, x, y, v, Hv; obj_weight) ------------------------------------------------
 // ctd_hprod_kernels.hpp.  Checks in the order of prod_check; y may be null (objective only) but Hv must not alias it.
-static int32_t hprod_check(ctd_handle* h, const char* fn, const double* x, const double* y, const double* v, const double* out) {
-    const int32_t st = prod_check(h, fn, x, v, out);
+static int32_t hprod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* y, const double* v,
+                           const double* out) {
+    const int32_t st = prod_check(on, h, fn, x, v, out);
     if (st) return st;
     if (y && out == y) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
     return CTD_OK;
@@ -1433,13 +1340,12 @@ static int32_t hprod_check(ctd_handle* h, const char* fn, const double* x, const
 static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
                              double* out_dev) {
     const char* fn = "ctd_hprod";
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
-    if (h->rt && !h->f_hprod_units) { const int32_t st = jit_load_hprod(h); if (st) return st; }
+    if (const int32_t st = jit_load(h, JIT_HPROD)) return st;
     const Layout& L = h->model.L;
     HProdParams hp;
     std::memset(&hp, 0, sizeof(hp));
     hp.p.L = L;
-    hp.p.tau = h->d_tau;
+    hp.p.tau = h->d_tau.p;
     hp.p.dir = y_dev;
     hp.p.out = out_dev;
     hp.vt = v_dev;
@@ -1451,14 +1357,14 @@ static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y
     const int64_t blocks = ((L.N + 1) * (int64_t)hp.p.nch + 255) / 256;
     if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
     hp.p.nblocks = (int32_t)blocks;
-    const int32_t st = grow_scratch(h, &h->d_hppartial, h->hppartial_cap, blocks * kMaxNV, fn);
+    const int32_t st = h->d_hppartial.grow(h, blocks * kMaxNV, fn);
     if (st) return st;
-    hp.p.partial = h->d_hppartial;
+    hp.p.partial = h->d_hppartial.p;
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&hp, &x_dev};
-        e = jit_launch(h->f_hprod_units, (int)blocks, 256, 0, h->stream, args);
-        if (e == hipSuccess) e = jit_launch(h->f_hprod_finish, 1, 64, 0, h->stream, args);
+        e = jit_launch(h->jit[JIT_HPROD].f[0], (int)blocks, 256, 0, h->stream, args);
+        if (e == hipSuccess) e = jit_launch(h->jit[JIT_HPROD].f[1], 1, 64, 0, h->stream, args);
     }
     for_problem(h->model.problem, [&](auto tag) { e = launch_hprod<typename decltype(tag)::type>(hp, x_dev, h->stream); });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
@@ -1467,48 +1373,36 @@ static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y
 
 int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
                             double* Hv_dev) {
-    const int32_t st = hprod_check(h, "ctd_hprod_dev_async", x_dev, y_dev, v_dev, Hv_dev);
+    const OnDevice on(h, "ctd_hprod_dev_async");
+    const int32_t st = hprod_check(on, h, "ctd_hprod_dev_async", x_dev, y_dev, v_dev, Hv_dev);
     return st ? st : enqueue_hprod(h, x_dev, y_dev, obj_weight, v_dev, Hv_dev);
 }
 
 // host pointers: x, y and v staged through the handle's x, y and direction buffers
 int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* v, double* Hv) {
-    int32_t st = hprod_check(h, "ctd_hprod", x, y, v, Hv);
+    const OnDevice on(h, "ctd_hprod");
+    const int32_t st = hprod_check(on, h, "ctd_hprod", x, y, v, Hv);
     if (st) return st;
     const Layout& L = h->model.L;
-    st = ensure_staging(h, false, false);
-    if (st) return st;
-    const size_t len = (size_t)std::max<int64_t>(std::max<int64_t>(L.nvar, L.ncon), 1);
-    if (!h->d_pdir) HIP_TRY(h, hipMalloc((void**)&h->d_pdir, sizeof(double) * len));
-    if (!h->d_pout) HIP_TRY(h, hipMalloc((void**)&h->d_pout, sizeof(double) * len));
-    if (y && !h->d_y) HIP_TRY(h, hipMalloc((void**)&h->d_y, sizeof(double) * L.ncon));
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_pdir, v, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
-    if (y) HIP_TRY(h, hipMemcpyAsync(h->d_y, y, sizeof(double) * L.ncon, hipMemcpyHostToDevice, h->stream));
-    st = enqueue_hprod(h, h->d_x, y ? h->d_y : nullptr, obj_weight, h->d_pdir, h->d_pout);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpyAsync(Hv, h->d_pout, sizeof(double) * L.nvar, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CTD_OK;
+    return host_call(h, {{x, h->d_x, L.nvar}, {v, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}},
+                     [&] { return enqueue_hprod(h, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_pout.p); },
+                     {{Hv, h->d_pout, L.nvar}});
 }
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x || !f) return fail(h, CTD_EINVAL, "null argument");
-    int32_t st = ensure_staging(h, false, false);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * h->model.L.nvar, hipMemcpyHostToDevice, h->stream));
-    return ctd_obj_dev(h, h->d_x, f);
+    return host_call(h, {{x, h->d_x, h->model.L.nvar}}, [&] { return enqueue_obj(h, h->d_x.p, h->d_obj.p); }, {{f, h->d_obj, 1}});
 }
 
 int32_t ctd_debug_stamps(ctd_handle* h, const double* x_dev, double* c_dev, double* vals_dev, uint64_t* out, int64_t cap) {
     if (!h || !out) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     int64_t words = (int64_t)h->grid * 12;
     if (cap < words) return fail(h, CTD_EINVAL, "stamp buffer too small");
     if (cap >= (int64_t)h->grid * 28) words = (int64_t)h->grid * 28;      // + sub-stamps of experiment builds (CTD_SUBSTAMPS)
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     unsigned long long* d_st = nullptr;
     HIP_TRY(h, hipMalloc((void**)&d_st, sizeof(unsigned long long) * words));
     HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(unsigned long long) * words, h->stream));
@@ -1563,7 +1457,8 @@ static int32_t time_dispatches(ctd_handle* h, int32_t iters, double* mean_ms,
 
 int32_t ctd_time_cons_jac_dev(ctd_handle* h, const double* x_dev, double* c_dev, double* vals_dev, int32_t iters, double* mean_ms) {
     if (!h || !mean_ms || iters < 1) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     return time_dispatches(h, iters, mean_ms, [&](hipEvent_t a, hipEvent_t b) { return enqueue_cons_jac(h, x_dev, c_dev, vals_dev, a, b); });
 }
 
@@ -1615,24 +1510,21 @@ static int32_t ensure_hess(ctd_handle* h) {
         h->hess_lds_bytes = (size_t)hess_lds_doubles(h->hp) * sizeof(double);
     }
     if (h->hess_lds_bytes > (h->rt ? 64u : 160u) * 1024) return fail(h, CTD_EINVAL, "Hessian records of one step do not fit the LDS");
-    if (h->rt && !h->jit_hmod) {
-        int32_t jst = jit_load_hess(h);
-        if (jst) return jst;
-    }
-    HIP_TRY(h, upload(&h->d_htptr, H.ctptr));
-    HIP_TRY(h, upload(&h->d_hcpos, H.cpos));
-    HIP_TRY(h, upload(&h->d_hzpos, H.zpos));
-    HIP_TRY(h, upload(&h->d_hterms, H.tcode));
-    HIP_TRY(h, upload(&h->d_hpair_c, H.pair_c));
-    HIP_TRY(h, upload(&h->d_hvptr, H.vptr));
-    HIP_TRY(h, upload(&h->d_hvterms, H.vterms));
-    HIP_TRY(h, upload(&h->d_hedge_idx, H.edge_idx));
-    HIP_TRY(h, upload(&h->d_heptr, H.eptr));
-    HIP_TRY(h, upload(&h->d_hevptr, H.evptr));
-    HIP_TRY(h, upload(&h->d_heterms, H.eterms));
-    HIP_TRY(h, upload(&h->d_htasks, H.tasks));
-    HIP_TRY(h, upload(&h->d_hptasks, H.ptasks));
-    HIP_TRY(h, upload(&h->d_hbtasks, H.btasks));
+    if (const int32_t jst = jit_load(h, JIT_HESS)) return jst;
+    HIP_TRY(h, upload(h->d_htptr, H.ctptr));
+    HIP_TRY(h, upload(h->d_hcpos, H.cpos));
+    HIP_TRY(h, upload(h->d_hzpos, H.zpos));
+    HIP_TRY(h, upload(h->d_hterms, H.tcode));
+    HIP_TRY(h, upload(h->d_hpair_c, H.pair_c));
+    HIP_TRY(h, upload(h->d_hvptr, H.vptr));
+    HIP_TRY(h, upload(h->d_hvterms, H.vterms));
+    HIP_TRY(h, upload(h->d_hedge_idx, H.edge_idx));
+    HIP_TRY(h, upload(h->d_heptr, H.eptr));
+    HIP_TRY(h, upload(h->d_hevptr, H.evptr));
+    HIP_TRY(h, upload(h->d_heterms, H.eterms));
+    HIP_TRY(h, upload(h->d_htasks, H.tasks));
+    HIP_TRY(h, upload(h->d_hptasks, H.ptasks));
+    HIP_TRY(h, upload(h->d_hbtasks, H.btasks));
     // Gauss-Legendre schemes with 2 / 3 stages of registry OCPs: the lane-per-step kernel takes the regular steps (CTD_HESS_STEP=0:
     // the tile kernel everywhere)
     std::vector<int32_t> ssrc, schunk;
@@ -1650,38 +1542,33 @@ static int32_t ensure_hess(ctd_handle* h) {
     }
     const int step_wgs = h->hess_step ? (int)((h->hp.step_end - h->hp.step_begin + kStepBlock - 1) / kStepBlock) : 0;
     const int edge_step = 32;      // (upper bound of the edge workgroups of the step launch)
-    if (h->d_hpartials) { (void)hipFree(h->d_hpartials); h->d_hpartials = nullptr; }
     h->hpart_member = (int64_t)(std::max(h->hp.ntiles, step_wgs) + std::max(h->hp.n_edge_blocks, edge_step)) * (H.nvv > 0 ? H.nvv : 1);
-    HIP_TRY(h, hipMalloc((void**)&h->d_hpartials, sizeof(double) * (size_t)h->hpart_member));
-    h->hpart_cap = h->hpart_member;
+    HIP_TRY(h, h->d_hpartials.ensure(h->hpart_member));
     HParams& hp = h->hp;
-    hp.tau = h->d_tau;
-    hp.tptr = h->d_htptr; hp.terms = h->d_hterms; hp.pair_c = h->d_hpair_c;
-    hp.cpos = h->d_hcpos; hp.zpos = h->d_hzpos;
-    hp.vptr = h->d_hvptr; hp.vterms = h->d_hvterms;
-    hp.edge_idx = h->d_hedge_idx; hp.eptr = h->d_heptr; hp.evptr = h->d_hevptr; hp.eterms = h->d_heterms;
-    hp.tasks = h->d_htasks; hp.ptasks = h->d_hptasks; hp.btasks = h->d_hbtasks;
-    hp.partials = h->d_hpartials;
+    hp.tau = h->d_tau.p;
+    hp.tptr = h->d_htptr.p; hp.terms = h->d_hterms.p; hp.pair_c = h->d_hpair_c.p;
+    hp.cpos = h->d_hcpos.p; hp.zpos = h->d_hzpos.p;
+    hp.vptr = h->d_hvptr.p; hp.vterms = h->d_hvterms.p;
+    hp.edge_idx = h->d_hedge_idx.p; hp.eptr = h->d_heptr.p; hp.evptr = h->d_hevptr.p; hp.eterms = h->d_heterms.p;
+    hp.tasks = h->d_htasks.p; hp.ptasks = h->d_hptasks.p; hp.btasks = h->d_hbtasks.p;
+    hp.partials = h->d_hpartials.p;
     // V x V partials: added in a fixed order by a second, one-workgroup kernel (a last-workgroup finish inside the main
     // kernel measured 2-7x slower on MI355X, profiles/r01_hessian_kernel.md: device-scope release per workgroup)
     hp.debug_stop = env_int("CTD_HESS_STOP", 0);
-    {   // write-through value stores for small Hessians (as for the constraint / Jacobian kernel, ctd_create)
-        const int wt = env_int("CTD_HESS_WT", -1);
-        const double out_mb = 8.0 * (double)(h->hp.step_end - h->hp.step_begin) * (double)H.Lseg / 1.0e6;
-        hp.wt_store = wt >= 0 ? (wt ? 1 : 0) : (out_mb <= (double)std::min(16, env_int("CTD_WT_MB", 64)) ? 1 : 0);       // (sweep: gains up to ~10 MB, even at 16, losses from ~80)
-    }
+    // write-through value stores for small Hessians (as for the constraint / Jacobian kernel, ctd_create)
+    hp.wt_store = 8.0 * (double)(h->hp.step_end - h->hp.step_begin) * (double)H.Lseg / 1.0e6 <= kHessWtMB ? 1 : 0;
     if (h->hess_step) {
-        HIP_TRY(h, upload(&h->d_hssrc, ssrc));
-        HIP_TRY(h, upload(&h->d_hschunk, schunk));
+        HIP_TRY(h, upload(h->d_hssrc, ssrc));
+        HIP_TRY(h, upload(h->d_hschunk, schunk));
         SParams& sp = h->sp;
         sp = SParams{};
         sp.L = mo.L;
-        sp.tau = h->d_tau;
+        sp.tau = h->d_tau.p;
         sp.step_begin = h->hp.step_begin; sp.step_end = h->hp.step_end;
         sp.reg_lo = sb; sp.reg_hi = se;
         sp.seg_base = H.seg_base; sp.reg_first = H.reg_first;
         sp.Lseg = H.Lseg; sp.nout = snout; sp.nchunk = (int)schunk.size() - 1; sp.nvv = H.nvv;
-        sp.src = h->d_hssrc; sp.chunk_pos = h->d_hschunk;
+        sp.src = h->d_hssrc.p; sp.chunk_pos = h->d_hschunk.p;
         {   // constant parts of the chain-rule coefficients (HC_*, ctd_hess.hpp) and of their pairs
             const Layout& L = mo.L;
             double kc[kHC];
@@ -1696,10 +1583,10 @@ static int32_t ensure_hess(ctd_handle* h) {
             std::vector<double> ck((size_t)kHC * kHC);
             for (int c1 = 0; c1 < kHC; ++c1)
                 for (int c2 = 0; c2 < kHC; ++c2) ck[(size_t)c1 * kHC + c2] = kc[c1] * kc[c2];
-            HIP_TRY(h, upload(&h->d_hsck, ck));
-            sp.ck = h->d_hsck;
+            HIP_TRY(h, upload(h->d_hsck, ck));
+            sp.ck = h->d_hsck.p;
         }
-        sp.partials = h->d_hpartials;
+        sp.partials = h->d_hpartials.p;
         // the tile kernel's edge path rides in the same launch on kStepBlock lanes: one edge workgroup per 64 edge entries
         h->hp_step = hp;
         const int ntot = (hp.edge_end - hp.edge_begin) + (hp.edge2_end - hp.edge2_begin);
@@ -1715,17 +1602,16 @@ static int32_t ensure_hess(ctd_handle* h) {
 
 static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* vals_dev,
                             hipEvent_t te0 = nullptr, hipEvent_t te1 = nullptr, const Batch* bt = nullptr) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x_dev || !y_dev || !vals_dev) return fail(h, CTD_EINVAL, "null argument");
     int32_t st = ensure_hess(h);
     if (st) return st;
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     const int nb = bt ? bt->n : 1;
     if (bt) {      // one set of V x V partial sums per member
-        st = grow_scratch(h, &h->d_hpartials, h->hpart_cap, (int64_t)nb * h->hpart_member, "ctd_hess_coord_batch_dev_async");
+        st = h->d_hpartials.grow(h, (int64_t)nb * h->hpart_member, "ctd_hess_coord_batch_dev_async");
         if (st) return st;
-        h->hp.partials = h->hp_step.partials = h->sp.partials = h->d_hpartials;
+        h->hp.partials = h->hp_step.partials = h->sp.partials = h->d_hpartials.p;
     }
     HParams hp = h->hp;
     if (bt) { hp.ldx = bt->ldx; hp.ldy = bt->ldy; hp.ldh = bt->ldh; hp.part_stride = h->hpart_member; }
@@ -1737,8 +1623,8 @@ static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&hp, &x_dev, &y_dev};
-        e = jit_launch(h->f_hess, hp.ntiles + hp.n_edge_blocks, kHessBlock, h->hess_lds_bytes, h->stream, args, te0, te1, nb);
-        if (e == hipSuccess && hp.nvv > 0) e = jit_launch(h->f_hess_finish, 1, kHessBlock, 0, h->stream, args, nullptr, nullptr, nb);
+        e = jit_launch(h->jit[JIT_HESS].f[0], hp.ntiles + hp.n_edge_blocks, kHessBlock, h->hess_lds_bytes, h->stream, args, te0, te1, nb);
+        if (e == hipSuccess && hp.nvv > 0) e = jit_launch(h->jit[JIT_HESS].f[1], 1, kHessBlock, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1772,31 +1658,22 @@ int32_t ctd_hess_coord_dev(ctd_handle* h, const double* x_dev, const double* y_d
 }
 
 int32_t ctd_hess_coord(ctd_handle* h, const double* x, const double* y, double obj_weight, double* vals) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x || !y || !vals) return fail(h, CTD_EINVAL, "null argument");
     const Model& mo = h->model;
-    int32_t st = ensure_staging(h, false, false);
-    if (st) return st;
-    if (!h->d_y) HIP_TRY(h, hipMalloc((void**)&h->d_y, sizeof(double) * mo.L.ncon));
-    if (!h->d_hvals) HIP_TRY(h, hipMalloc((void**)&h->d_hvals, sizeof(double) * (mo.H.nnzh > 0 ? mo.H.nnzh : 1)));
-    HIP_TRY(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * mo.L.nvar, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_y, y, sizeof(double) * mo.L.ncon, hipMemcpyHostToDevice, h->stream));
-    st = enqueue_hess(h, h->d_x, h->d_y, obj_weight, h->d_hvals);
-    if (st) return st;
-    HIP_TRY(h, hipMemcpyAsync(vals, h->d_hvals, sizeof(double) * mo.H.nnzh, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CTD_OK;
+    return host_call(h, {{x, h->d_x, mo.L.nvar}, {y, h->d_y, mo.L.ncon}},
+                     [&] { return enqueue_hess(h, h->d_x.p, h->d_y.p, obj_weight, h->d_hvals.p); }, {{vals, h->d_hvals, mo.H.nnzh}});
 }
 
 // ---- batched callbacks: K iterates of one transcription per launch ---------------------------------------------------
 // The same kernels on a grid whose second dimension is the member (include/ctdirect_hip.h).  Checks in this order: handle,
-// device (CTD_ENODEVICE), batch size, whole-grid handle, then pointers and leading dimensions (CTD_EINVAL).
+// device (CTD_ENODEVICE) -- the prologue, OnDevice(h, fn) --, batch size, whole-grid handle, then pointers and leading dimensions
+// (CTD_EINVAL).
 constexpr int32_t kMaxBatch = 65535;       // the grid's y limit
 
-static int32_t batch_check(ctd_handle* h, const char* fn, int32_t batch, const double* x_dev, int64_t ldx) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, std::string(fn) + ": compute call on a host-only handle (device = -1); there is no CPU fallback");
+static int32_t batch_check(const OnDevice& on, ctd_handle* h, const char* fn, int32_t batch, const double* x_dev, int64_t ldx) {
+    if (on.st) return on.st;
     if (batch < 1 || batch > kMaxBatch) return fail(h, CTD_EINVAL, std::string(fn) + ": batch must be in [1, 65535], got " + std::to_string(batch));
     if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
         return fail(h, CTD_EINVAL, std::string(fn) + ": batched calls need a handle of the whole grid; a shard handle (step_begin / step_end, "
@@ -1813,7 +1690,8 @@ static int32_t ld_check(ctd_handle* h, const char* fn, const char* name, int64_t
 int32_t ctd_cons_jac_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* c_dev, int64_t ldc,
                                      double* vals_dev, int64_t ldv) {
     static const char* fn = "ctd_cons_jac_batch_dev_async";
-    int32_t st = batch_check(h, fn, batch, x_dev, ldx);
+    const OnDevice on(h, fn);
+    int32_t st = batch_check(on, h, fn, batch, x_dev, ldx);
     if (!st && c_dev) st = ld_check(h, fn, "ldc", ldc, h->model.L.ncon);
     if (!st && vals_dev) st = ld_check(h, fn, "ldv", ldv, h->model.nnzj);
     if (st) return st;
@@ -1822,16 +1700,19 @@ int32_t ctd_cons_jac_batch_dev_async(ctd_handle* h, int32_t batch, const double*
 }
 
 int32_t ctd_obj_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* f_dev) {
-    int32_t st = batch_check(h, "ctd_obj_batch_dev_async", batch, x_dev, ldx);
+    static const char* fn = "ctd_obj_batch_dev_async";
+    const OnDevice on(h, fn);
+    const int32_t st = batch_check(on, h, fn, batch, x_dev, ldx);
     if (st) return st;
-    if (!f_dev) return fail(h, CTD_EINVAL, "ctd_obj_batch_dev_async: f is null");
+    if (!f_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": f is null");
     const Batch bt{batch, ldx, 0, 0, 0, 0, 0};
     return enqueue_obj(h, x_dev, f_dev, &bt);
 }
 
 int32_t ctd_grad_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, double* g_dev, int64_t ldg) {
     static const char* fn = "ctd_grad_batch_dev_async";
-    int32_t st = batch_check(h, fn, batch, x_dev, ldx);
+    const OnDevice on(h, fn);
+    int32_t st = batch_check(on, h, fn, batch, x_dev, ldx);
     if (st) return st;
     if (!g_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": g is null");
     if ((st = ld_check(h, fn, "ldg", ldg, h->model.L.nvar))) return st;
@@ -1842,7 +1723,8 @@ int32_t ctd_grad_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_d
 int32_t ctd_hess_coord_batch_dev_async(ctd_handle* h, int32_t batch, const double* x_dev, int64_t ldx, const double* y_dev, int64_t ldy,
                                        double obj_weight, double* vals_dev, int64_t ldh) {
     static const char* fn = "ctd_hess_coord_batch_dev_async";
-    int32_t st = batch_check(h, fn, batch, x_dev, ldx);
+    const OnDevice on(h, fn);
+    int32_t st = batch_check(on, h, fn, batch, x_dev, ldx);
     if (st) return st;
     if (!y_dev || !vals_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": y or vals is null");
     if ((st = ld_check(h, fn, "ldy", ldy, h->model.L.ncon))) return st;
@@ -1857,14 +1739,13 @@ int32_t ctd_hess_coord_batch_dev_async(ctd_handle* h, int32_t batch, const doubl
 // kernels are compiled by hiprtc per callback): the same callbacks one after the other on the handle's stream.
 int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* f_dev, double* g_dev,
                                double* c_dev, double* vals_dev, double* hvals_dev) {
-    if (!h) return CTD_EINVAL;
-    if (h->device < 0) return fail(h, CTD_ENODEVICE, "compute call on a host-only handle (device = -1); there is no CPU fallback");
+    const OnDevice on(h);
+    if (on.st) return on.st;
     if (!x_dev) return fail(h, CTD_EINVAL, "x is null");
     if (hvals_dev && !y_dev) return fail(h, CTD_EINVAL, "y is null");
-    DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     int32_t st = CTD_OK;
     if (hvals_dev) { st = ensure_hess(h); if (st) return st; }      // first use uploads the tables (not capturable)
-    if (h->rt || h->model.L.cs > 1 || env_int("CTD_ITER_SERIAL", 0)) {
+    if (h->rt || h->model.L.cs > 1) {
         if (f_dev) st = enqueue_obj(h, x_dev, f_dev);
         if (!st && g_dev) st = enqueue_grad(h, x_dev, g_dev);
         if (!st && (c_dev || vals_dev)) st = enqueue_cons_jac(h, x_dev, c_dev, vals_dev);

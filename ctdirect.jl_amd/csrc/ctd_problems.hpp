@@ -414,21 +414,19 @@ struct DoubleIntegratorFreeT0TfOCP {
 };
 
 constexpr int kNumProblems = 10;
+// the registry: X(problem id of include/ctdirect_hip.h, OCP type) -- for_problem below, the engine's extern declarations
+#define CTD_REGISTRY(X)                                                                                                      \
+    X(0, GoddardOCP) X(1, GoddardAllOCP) X(2, DoubleIntegratorPathOCP) X(3, QuadrotorOCP) X(4, Quadrotor12OCP)              \
+    X(5, StagewiseScalarOCP) X(6, EstimateInitialConditionOCP) X(7, EstimateRotationRateOCP) X(8, LeastSquaresConstraintOCP) \
+    X(9, DoubleIntegratorFreeT0TfOCP)
 
 // static dispatch over the registry: f(TypeTag<OCP>{})
 template <class P> struct TypeTag { using type = P; };
 template <class F> inline bool for_problem(int id, F&& f) {
     switch (id) {
-        case 0: f(TypeTag<GoddardOCP>{}); return true;
-        case 1: f(TypeTag<GoddardAllOCP>{}); return true;
-        case 2: f(TypeTag<DoubleIntegratorPathOCP>{}); return true;
-        case 3: f(TypeTag<QuadrotorOCP>{}); return true;
-        case 4: f(TypeTag<Quadrotor12OCP>{}); return true;
-        case 5: f(TypeTag<StagewiseScalarOCP>{}); return true;
-        case 6: f(TypeTag<EstimateInitialConditionOCP>{}); return true;
-        case 7: f(TypeTag<EstimateRotationRateOCP>{}); return true;
-        case 8: f(TypeTag<LeastSquaresConstraintOCP>{}); return true;
-        case 9: f(TypeTag<DoubleIntegratorFreeT0TfOCP>{}); return true;
+#define CTD_PROBLEM_CASE(ID, P) case ID: f(TypeTag<P>{}); return true;
+        CTD_REGISTRY(CTD_PROBLEM_CASE)
+#undef CTD_PROBLEM_CASE
         default: return false;
     }
 }
