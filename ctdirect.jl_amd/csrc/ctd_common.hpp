@@ -48,6 +48,43 @@ template <bool B> CTD_HD double* member_out(double* p, int64_t ld) {
     else return p;
 }
 
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+// ---- deterministic sums over the lanes of a launch (d/dv partials, quadrature) -------------------------------------------
+// The order of every addition is fixed, so a result is the same bits on every run; it is part of the contract:
+//  1. per wave, the shuffle tree: off = 32, 16, 8, 4, 2, 1, each lane l adding the value of lane l + off to its own
+//     (lane 0 ends with ((((((v0 + v32) + (v16 + v48)) + ...: the tree of __shfl_down over a 64-lane wave);
+//  2. per workgroup, thread 0 adds the waves' sums in wave order starting from 0.0 and writes the row;
+//  3. the finishing wave: lane l adds rows l, l + 64, l + 128, ... in that order starting from 0.0, then the tree of 1.
+// block_partial_sums: every thread of the workgroup calls it with its NV values; wsum is LDS, waves x LD doubles; row: this
+// workgroup's NV entries of the partial buffer.
+template <int NV, int LD>
+__device__ __forceinline__ void block_partial_sums(const double* val, double* wsum, double* row) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        double s = val[j];
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        if (lane == 0) wsum[wave * LD + j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int j = 0; j < NV; ++j) {
+            double s = 0.0;
+            for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) s += wsum[wv * LD + j];
+            row[j] = s;
+        }
+    }
+}
+// ordered_rows_sum: the 64 lanes of the finishing wave call it; entry j of the `rows` rows (LD doubles apart) summed, valid in lane 0
+template <int LD>
+__device__ __forceinline__ double ordered_rows_sum(const double* part, int rows, int j) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < rows; b += 64) s += part[(int64_t)b * LD + j];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    return s;
+}
+#endif
+
 // ---- forward-mode dual number with K directions, evaluated in registers ---------------------------------
 // The reference obtains Jacobian values by pushing ForwardDiff.Dual numbers through its generic callbacks
 // (ADNLPModels.SparseADJacobian, call site src/collocation.jl:116-120).  The engine differentiates the

@@ -380,6 +380,32 @@ static int32_t host_call(ctd_handle* h, std::initializer_list<Staged<const doubl
     return CTD_OK;
 }
 
+// The unit pass and the finish of a transposed product (jtprod, hprod): `dirs` directions per node in chunks of jc -- the
+// ProdDirs / HProdDirs of a registry problem, the same formula for a run-time OCP -- give the geometry and the size of the caller's
+// partial buffer, written into a's ProdParams; then the two kernels: f[f0], f[f0 + 1] of the run-time OCP's module, or
+// launch_prod_units.  a: the kernels' argument struct
+template <class K>
+static int32_t enqueue_prod_units(ctd_handle* h, const char* fn, typename K::Params& a, int dirs, int jc, DevBuf<>& partial,
+                                  const JitModule& jm, int f0, const double* x_dev) {
+    ProdParams& pp = K::prod(a);
+    pp.nch = (int32_t)((dirs + jc - 1) / jc);
+    const int64_t blocks = ((pp.L.N + 1) * (int64_t)pp.nch + 255) / 256;
+    if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
+    pp.nblocks = (int32_t)blocks;
+    const int32_t st = partial.grow(h, blocks * kMaxNV, fn);
+    if (st) return st;
+    pp.partial = partial.p;
+    hipError_t e = hipErrorInvalidValue;
+    if (h->rt) {
+        void* args[] = {&a, &x_dev};
+        e = jit_launch(jm.f[f0], (int)blocks, 256, 0, h->stream, args);
+        if (e == hipSuccess) e = jit_launch(jm.f[f0 + 1], 1, 64, 0, h->stream, args);
+    }
+    for_problem(h->model.problem, [&](auto tag) { e = launch_prod_units<typename decltype(tag)::type, K>(a, x_dev, h->stream); });
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
 extern "C" {
 
 const char* ctd_strerror(int32_t st) {
@@ -468,7 +494,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
                 mo.fill_kparams(kq, h->step_begin, h->step_end, tile);
                 lds = (size_t)lds_doubles(kq) * sizeof(double);
                 int r = 0;
-                for_problem(mo.problem, [&](auto tag) { r = occupancy_cons_jac<typename decltype(tag)::type>(mo.L.sc, kq, h->block, lds); });
+                for_problem(mo.problem, [&](auto tag) { r = occupancy_cons_jac<typename decltype(tag)::type>(kq, h->block, lds); });
                 (void)hipGetLastError();
                 return r;
             };
@@ -585,7 +611,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
                     } else {
                         for_problem(mo.problem, [&](auto tag) {
                             using P = typename decltype(tag)::type;
-                            per_cu = occupancy_cons_jac<P>(mo.L.sc, hp->kp, hp->block, hp->lds_bytes);
+                            per_cu = occupancy_cons_jac<P>(hp->kp, hp->block, hp->lds_bytes);
                         });
                     }
                 }
@@ -972,7 +998,7 @@ int32_t ctd_launch_info(const ctd_handle* h, int64_t* o) {
             if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit[JIT_FIRST].f[0], h->block, h->lds_bytes) != hipSuccess) per_cu = 0; }
             else for_problem(h->model.problem, [&](auto tag) {
                 using P = typename decltype(tag)::type;
-                per_cu = occupancy_cons_jac<P>(h->model.L.sc, h->kp, h->block, h->lds_bytes);
+                per_cu = occupancy_cons_jac<P>(h->kp, h->block, h->lds_bytes);
             });
         }
         (void)hipGetLastError();
@@ -998,7 +1024,6 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     kp.c = c_dev;
     kp.vals = vals_dev;
     hipError_t e = hipErrorInvalidValue;
-    const int sc = h->model.L.sc;
     if (bt) {      // the batched instantiation of the kernel: grid (tiles, members)
         BatchLd bl{bt->ldx, bt->ldc, bt->ldv};
         // write-through stores by the rule of ctd_create, applied to what the whole LAUNCH writes (all members)
@@ -1010,7 +1035,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
         }
         for_problem(h->model.problem, [&](auto tag) {
             using P = typename decltype(tag)::type;
-            e = launch_cons_jac_batch<P>(sc, kp, x_dev, bl, h->grid, h->block, h->lds_bytes, h->stream, bt->n);
+            e = launch_cons_jac_batch<P>(kp, x_dev, bl, h->grid, h->block, h->lds_bytes, h->stream, bt->n);
         });
         if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
         return CTD_OK;
@@ -1021,7 +1046,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_cons_jac<P>(sc, kp, x_dev, h->grid, h->block, h->lds_bytes, h->stream, te0, te1);
+        e = launch_cons_jac<P>(kp, x_dev, h->grid, h->block, h->lds_bytes, h->stream, te0, te1);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;
@@ -1116,7 +1141,7 @@ static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev, co
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_obj<P>(L.sc, op, x_dev, lagrange ? blocks : 0, 256, h->stream, nb);
+        e = launch_obj<P>(op, x_dev, lagrange ? blocks : 0, 256, h->stream, nb);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;
@@ -1233,7 +1258,7 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_grad<P>(L.sc, L.s, gp, x_dev, lagrange ? blocks : 0, h->stream, nb);
+        e = launch_grad<P>(gp, x_dev, lagrange ? blocks : 0, h->stream, nb);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;
@@ -1260,9 +1285,6 @@ static int32_t prod_check(const OnDevice& on, ctd_handle* h, const char* fn, con
     return CTD_OK;
 }
 
-// the JC directions per jtprod lane of a run-time OCP (ProdDirs<UserOCP>::JC, the same formula)
-static int prod_chunk_rt(const RtOcp& ro) { return ro.info.n >= 8 ? 2 : (ro.dc < 4 ? ro.dc : 4); }
-
 static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, const double* d_dev, double* out_dev) {
     const char* fn = transpose ? "ctd_jtprod" : "ctd_jprod";
     if (const int32_t st = jit_load(h, JIT_PROD)) return st;
@@ -1282,21 +1304,9 @@ static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, 
         for_problem(h->model.problem, [&](auto tag) { e = launch_jprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
     } else {
         int jc = 1;
-        if (h->rt) jc = prod_chunk_rt(*h->rt);
-        for_problem(h->model.problem, [&](auto tag) { jc = prod_chunk<typename decltype(tag)::type>(); });
-        pp.nch = (int32_t)((prod_dirs_per_node(L) + jc - 1) / jc);
-        const int64_t blocks = ((L.N + 1) * (int64_t)pp.nch + 255) / 256;
-        if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
-        pp.nblocks = (int32_t)blocks;
-        const int32_t st = h->d_ppartial.grow(h, blocks * kMaxNV, fn);
-        if (st) return st;
-        pp.partial = h->d_ppartial.p;
-        if (h->rt) {
-            void* args[] = {&pp, &x_dev};
-            e = jit_launch(h->jit[JIT_PROD].f[1], (int)blocks, 256, 0, h->stream, args);
-            if (e == hipSuccess) e = jit_launch(h->jit[JIT_PROD].f[2], 1, 64, 0, h->stream, args);
-        }
-        for_problem(h->model.problem, [&](auto tag) { e = launch_jtprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
+        if (h->rt) jc = jtprod_chunk(h->rt->info.n, h->rt->dc);
+        for_problem(h->model.problem, [&](auto tag) { jc = ProdDirs<typename decltype(tag)::type>::JC; });
+        return enqueue_prod_units<JtprodKernels>(h, fn, pp, prod_dirs_per_node(L), jc, h->d_ppartial, h->jit[JIT_PROD], 1, x_dev);
     }
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
     return CTD_OK;
@@ -1352,23 +1362,8 @@ static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y
     hp.sigma = obj_weight;
     int jc = 1;
     if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
-    for_problem(h->model.problem, [&](auto tag) { jc = hprod_chunk_of<typename decltype(tag)::type>(); });
-    hp.p.nch = (int32_t)((hprod_dirs_per_node(L) + jc - 1) / jc);
-    const int64_t blocks = ((L.N + 1) * (int64_t)hp.p.nch + 255) / 256;
-    if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
-    hp.p.nblocks = (int32_t)blocks;
-    const int32_t st = h->d_hppartial.grow(h, blocks * kMaxNV, fn);
-    if (st) return st;
-    hp.p.partial = h->d_hppartial.p;
-    hipError_t e = hipErrorInvalidValue;
-    if (h->rt) {
-        void* args[] = {&hp, &x_dev};
-        e = jit_launch(h->jit[JIT_HPROD].f[0], (int)blocks, 256, 0, h->stream, args);
-        if (e == hipSuccess) e = jit_launch(h->jit[JIT_HPROD].f[1], 1, 64, 0, h->stream, args);
-    }
-    for_problem(h->model.problem, [&](auto tag) { e = launch_hprod<typename decltype(tag)::type>(hp, x_dev, h->stream); });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    for_problem(h->model.problem, [&](auto tag) { jc = HProdDirs<typename decltype(tag)::type>::JC; });
+    return enqueue_prod_units<HprodKernels>(h, fn, hp, hprod_dirs_per_node(L), jc, h->d_hppartial, h->jit[JIT_HPROD], 0, x_dev);
 }
 
 int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,

@@ -136,17 +136,9 @@ hipError_t launch_hess_variant(const HParams& hp, const double* xu, const double
 template <class P>
 hipError_t launch_hess(const HParams& hp, const double* xu, const double* y, size_t lds_bytes, hipStream_t st, hipEvent_t e0,
                        hipEvent_t e1, int batch) {
-    const int sc = hp.L.sc;
-    if (sc == SC_TRAPEZE) return launch_hess_variant<P, SC_TRAPEZE, 1>(hp, xu, y, lds_bytes, st, e0, e1, batch);
-    if (sc == SC_MIDPOINT) {      // S: controls per step (registry problems 1 - 3, as the constraint / Jacobian kernels)
-        if (hp.L.cs == 2) return launch_hess_variant<P, SC_MIDPOINT, 2>(hp, xu, y, lds_bytes, st, e0, e1, batch);
-        if (hp.L.cs == 3) return launch_hess_variant<P, SC_MIDPOINT, 3>(hp, xu, y, lds_bytes, st, e0, e1, batch);
-        if (hp.L.cs > 3) return hipErrorInvalidValue;
-        return launch_hess_variant<P, SC_MIDPOINT, 1>(hp, xu, y, lds_bytes, st, e0, e1, batch);
-    }
-    if (hp.L.s == 1) return launch_hess_variant<P, SC_IRK, 1>(hp, xu, y, lds_bytes, st, e0, e1, batch);
-    if (hp.L.s == 2) return launch_hess_variant<P, SC_IRK, 2>(hp, xu, y, lds_bytes, st, e0, e1, batch);
-    return launch_hess_variant<P, SC_IRK, 3>(hp, xu, y, lds_bytes, st, e0, e1, batch);
+    hipError_t e = hipErrorInvalidValue;       // (midpoint: S = controls per step, 1 - 3, as the constraint / Jacobian kernels)
+    for_scheme<true>(hp.L, [&](auto t) { e = launch_hess_variant<P, t.sc, t.s>(hp, xu, y, lds_bytes, st, e0, e1, batch); });
+    return e;
 }
 
 #define CTD_INSTANTIATE_HESS(P) \

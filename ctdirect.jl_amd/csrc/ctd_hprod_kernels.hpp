@@ -144,33 +144,26 @@ __device__ __forceinline__ void hprod_unit_body(const HProdParams& hp, const dou
     for (int d = 0; d < JC; ++d) acc[d] = 0.0;
     const bool hits_x = g0 < n;                     // the chunk holds X_k directions
     const bool hits_u = g0 < n + L.cu && g0 + JC > n && m > 0;      // ... or control directions
-    auto rows_at = [&](int64_t r0) {
-        return [&, r0](int r, const T& val) {
-            const double wr = y[r0 + r];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.ab[d];
-        };
-    };
     if (y) {
         // rows of step k and path rows of node k: every input of node k carries its direction
         if (k < L.N) {
-            auto sink = rows_at(k * (int64_t)L.cb);
+            auto sink = weighted_rows<JC>(y, k * (int64_t)L.cb, acc);
             prod_step_rows<P, SC, S, T>(pp, src, k, ProdRoles{0, n, -1, -1, bk}, sink);
         }
         if (P::NPATH > 0) {
-            auto sink = rows_at(k < L.N ? k * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb);
+            auto sink = weighted_rows<JC>(y, k < L.N ? k * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb, acc);
             prod_path_rows<P, SC, S, T>(pp, src, k, 0, path_ctrl_node(L, k) == k ? n : -1, bk, sink);
         }
         // rows of step k-1: they read X_k (and U_k on the trapeze); Gauss-Legendre and explicit Euler read X_{i+1} through the
         // identity only, which has no second derivative
         const bool one_point = SC == SC_IRK || (SC == SC_MIDPOINT && L.euler == 1);
         if (k >= 1 && !one_point && (hits_x || (SC == SC_TRAPEZE && hits_u))) {
-            auto sink = rows_at((k - 1) * (int64_t)L.cb);
+            auto sink = weighted_rows<JC>(y, (k - 1) * (int64_t)L.cb, acc);
             prod_step_rows<P, SC, S, T>(pp, src, k - 1, ProdRoles{-1, -1, 0, n, -1}, sink);
         }
         // path rows of node k+1 when they read U_k
         if (P::NPATH > 0 && k < L.N && path_ctrl_node(L, k + 1) == k && hits_u) {
-            auto sink = rows_at(k + 1 < L.N ? (k + 1) * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb);
+            auto sink = weighted_rows<JC>(y, k + 1 < L.N ? (k + 1) * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb, acc);
             prod_path_rows<P, SC, S, T>(pp, src, k + 1, -1, n, -1, sink);
         }
     }
@@ -188,142 +181,35 @@ __device__ __forceinline__ void hprod_unit_body(const HProdParams& hp, const dou
             for (int d = 0; d < JC; ++d) acc[d] = acc[d] + sg * c.ab[d];
         }
     }
-    double* out = pp.out + k * (int64_t)L.blk;
-#pragma unroll
-    for (int d = 0; d < JC; ++d) {
-        const int g = g0 + d;
-        if (g < bk) out[g] = acc[d];
-        else if (g < bk + nv) {
-#pragma unroll
-            for (int j = 0; j < nv; ++j)
-                if (g - bk == j) gv[j] = acc[d];
-        }
-    }
+    prod_write_out<JC, nv>(acc, g0, bk, pp.out + k * (int64_t)L.blk, gv);
 }
 
-// body of the unit pass for workgroup `block` (wsum: 4 * kMaxNV doubles of LDS)
-template <class P, int SC, int S>
-__device__ __forceinline__ void hprod_units_body(const HProdParams& hp, const double* __restrict__ xu, int block, double (*wsum)[kMaxNV]) {
-    constexpr int nv = P::NV;
-    const ProdParams& pp = hp.p;
-    double gv[nv > 0 ? nv : 1];
-#pragma unroll
-    for (int j = 0; j < nv; ++j) gv[j] = 0.0;
-    const int64_t id = (int64_t)block * blockDim.x + threadIdx.x;
-    const int64_t k = id / pp.nch;
-    if (k <= pp.L.N) hprod_unit_body<P, SC, S>(hp, xu, k, (int)(id - k * pp.nch), gv);
-    if constexpr (nv > 0) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int j = 0; j < nv; ++j) {
-            double s = gv[j];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-            if (lane == 0) wsum[wave][j] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int j = 0; j < nv; ++j) {
-                double s = 0.0;
-                for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) s += wsum[wv][j];
-                pp.partial[(int64_t)block * kMaxNV + j] = s;
-            }
-        }
-    }
-}
-
+// the unit pass and the finish of ctd_prod_kernels.hpp (prod_units_body, prod_finish_body) around the second-order lanes
 template <class P, int SC, int S>
 __global__ void __launch_bounds__(256) hprod_units_kernel(const HProdParams hp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    hprod_units_body<P, SC, S>(hp, xu, (int)blockIdx.x, wsum);
-}
-
-// one wave: the boundary rows and the Mayer term -- lane l differentiates chunks l, l + 64, ... of (X_1, X_{N+1}, v) and adds to
-// the entries it owns -- then the v partials in block order (lane l adds blocks l, l + 64, ..., then a fixed shuffle tree)
-template <class P>
-__device__ __forceinline__ void hprod_finish_body(const HProdParams& hp, const double* __restrict__ xu, double* bv) {
-    constexpr int n = P::NX, nv = P::NV, nb = P::NBC, JC = HProdDirs<P>::JC;
-    using T = Dual2<JC>;
-    const ProdParams& pp = hp.p;
-    const Layout& L = pp.L;
-    const int lane = (int)threadIdx.x;
-    if (lane < kMaxNV) bv[lane] = 0.0;
-    __syncthreads();
-    const bool rows = nb > 0 && pp.dir != nullptr;
-    if (rows || P::HAS_MAYER) {
-        const int64_t gf = L.N * (int64_t)L.blk;
-        for (int g0 = lane * JC; g0 < 2 * n + nv; g0 += 64 * JC) {
-            const HSeedSrc<JC> src{xu, hp.vt, g0};
-            double acc[JC];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = 0.0;
-            if (rows) {
-                const int64_t rb = L.ncon - L.bc;
-                auto sink = [&](int r, const T& val) {
-                    const double wr = pp.dir[rb + r];
-#pragma unroll
-                    for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.ab[d];
-                };
-                prod_boundary_rows<P, T>(pp, src, true, sink);
-            }
-            if constexpr (P::HAS_MAYER) {        // src/DOCP_functions.jl:35-48; directions as the boundary rows'
-                T x0[n > 0 ? n : 1], xf[n > 0 ? n : 1], V[nv > 0 ? nv : 1];
-#pragma unroll
-                for (int c = 0; c < n; ++c) { x0[c] = src.at(c, c); xf[c] = src.at(gf + c, n + c); }
-#pragma unroll
-                for (int j = 0; j < nv; ++j) V[j] = src.at(L.v_off + j, 2 * n + j);
-                const T r = P::template mayer<T>(x0, xf, V);
-#pragma unroll
-                for (int d = 0; d < JC; ++d) acc[d] = acc[d] + hp.sigma * r.ab[d];
-            }
-#pragma unroll
-            for (int d = 0; d < JC; ++d) {
-                const int g = g0 + d;
-                if (g < n) pp.out[g] += acc[d];
-                else if (g < 2 * n) pp.out[gf + g - n] += acc[d];
-                else if (g < 2 * n + nv) bv[g - 2 * n] = acc[d];
-            }
-        }
-    }
-    __syncthreads();
-    if constexpr (nv > 0) {
-        for (int j = 0; j < nv; ++j) {
-            double s = 0.0;
-            for (int b = lane; b < pp.nblocks; b += 64) s += pp.partial[(int64_t)b * kMaxNV + j];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-            if (lane == 0) pp.out[L.v_off + j] = s + bv[j];
-        }
-    }
+    prod_units_body<P::NV>(hp.p, (int)blockIdx.x, wsum, [&](int64_t k, int q, double* gv) { hprod_unit_body<P, SC, S>(hp, xu, k, q, gv); });
 }
 
 template <class P>
 __global__ void __launch_bounds__(64) hprod_finish_kernel(const HProdParams hp, const double* __restrict__ xu) {
     __shared__ double bv[kMaxNV];
-    hprod_finish_body<P>(hp, xu, bv);
+    constexpr int JC = HProdDirs<P>::JC;
+    prod_finish_body<P, JC, true>(hp.p, bv, [&](int g0) { return HSeedSrc<JC>{xu, hp.vt, g0}; }, hp.sigma);
 }
 
 #if !defined(__HIPCC_RTC__)
-// ---- launchers (instantiated per registry problem in ctd_pkern_*.hip) ---------------------------------------------------
-// hp.p.nblocks / nch / partial filled in by the caller (enqueue_hprod)
-template <class P>
-hipError_t launch_hprod(const HProdParams& hp, const double* xu, hipStream_t st) {
-    const int sc = hp.p.L.sc, s = hp.p.L.s;
-    const unsigned grid = (unsigned)hp.p.nblocks;
-    if (sc == SC_TRAPEZE) hprod_units_kernel<P, SC_TRAPEZE, 1><<<grid, 256, 0, st>>>(hp, xu);
-    else if (sc == SC_MIDPOINT) hprod_units_kernel<P, SC_MIDPOINT, 1><<<grid, 256, 0, st>>>(hp, xu);
-    else if (s == 1) hprod_units_kernel<P, SC_IRK, 1><<<grid, 256, 0, st>>>(hp, xu);
-    else if (s == 2) hprod_units_kernel<P, SC_IRK, 2><<<grid, 256, 0, st>>>(hp, xu);
-    else hprod_units_kernel<P, SC_IRK, 3><<<grid, 256, 0, st>>>(hp, xu);
-    hprod_finish_kernel<P><<<1, 64, 0, st>>>(hp, xu);
-    return hipGetLastError();
-}
-template <class P> int hprod_chunk_of() { return HProdDirs<P>::JC; }
+// ---- launcher (launch_prod_units, instantiated per registry problem in ctd_pkern_*.hip) ----------------------------------
+struct HprodKernels {
+    using Params = HProdParams;
+    static ProdParams& prod(Params& a) { return a.p; }
+    static const ProdParams& prod(const Params& a) { return a.p; }
+    template <class P, int SC, int S> static constexpr auto units = &hprod_units_kernel<P, SC, S>;
+    template <class P> static constexpr auto finish = &hprod_finish_kernel<P>;
+};
 
-#define CTD_INSTANTIATE_HPROD(P)                                                      \
-    template hipError_t launch_hprod<P>(const HProdParams&, const double*, hipStream_t); \
-    template int hprod_chunk_of<P>();
-#define CTD_EXTERN_HPROD(P)                                                                  \
-    extern template hipError_t launch_hprod<P>(const HProdParams&, const double*, hipStream_t); \
-    extern template int hprod_chunk_of<P>();
+#define CTD_INSTANTIATE_HPROD(P) template hipError_t launch_prod_units<P, HprodKernels>(const HProdParams&, const double*, hipStream_t);
+#define CTD_EXTERN_HPROD(P) extern template hipError_t launch_prod_units<P, HprodKernels>(const HProdParams&, const double*, hipStream_t);
 #endif  // !__HIPCC_RTC__
 
 }  // namespace ctd

@@ -78,12 +78,9 @@ hipError_t launch_iter_variant(const IterParams& ip, const double* xu, const dou
 }
 template <class P>
 hipError_t launch_iter(const IterParams& ip, const double* xu, const double* y, size_t lds_bytes, hipStream_t st) {
-    const int sc = ip.kp.L.sc, s = ip.kp.L.s;
-    if (sc == SC_TRAPEZE) return launch_iter_variant<P, SC_TRAPEZE, 1>(ip, xu, y, lds_bytes, st);
-    if (sc == SC_MIDPOINT) return launch_iter_variant<P, SC_MIDPOINT, 1>(ip, xu, y, lds_bytes, st);
-    if (s == 1) return launch_iter_variant<P, SC_IRK, 1>(ip, xu, y, lds_bytes, st);
-    if (s == 2) return launch_iter_variant<P, SC_IRK, 2>(ip, xu, y, lds_bytes, st);
-    return launch_iter_variant<P, SC_IRK, 3>(ip, xu, y, lds_bytes, st);
+    hipError_t e = hipErrorInvalidValue;
+    for_scheme<false>(ip.kp.L, [&](auto t) { e = launch_iter_variant<P, t.sc, t.s>(ip, xu, y, lds_bytes, st); });
+    return e;
 }
 #define CTD_INSTANTIATE_ITER(P) template hipError_t launch_iter<P>(const IterParams&, const double*, const double*, size_t, hipStream_t);
 #define CTD_EXTERN_ITER(P) extern template hipError_t launch_iter<P>(const IterParams&, const double*, const double*, size_t, hipStream_t);

@@ -665,14 +665,10 @@ __global__ void grad_finish_kernel(const GradParams gp, const double* __restrict
 #if !defined(__HIPCC_RTC__)
 // batch: members of a batched launch (the grid's second dimension; 1 for one iterate)
 template <class P>
-hipError_t launch_grad(int sc, int s, const GradParams& gp, const double* xu, int grid, hipStream_t st, int batch) {
+hipError_t launch_grad(const GradParams& gp, const double* xu, int grid, hipStream_t st, int batch) {
     const dim3 g(grid > 0 ? grid : 1, batch);
-    if (grid <= 0) {}      // Mayer-only cost: nothing to integrate
-    else if (sc == SC_TRAPEZE) grad_units_kernel<P, SC_TRAPEZE, 1><<<g, 256, 0, st>>>(gp, xu);
-    else if (sc == SC_MIDPOINT) grad_units_kernel<P, SC_MIDPOINT, 1><<<g, 256, 0, st>>>(gp, xu);
-    else if (s == 1) grad_units_kernel<P, SC_IRK, 1><<<g, 256, 0, st>>>(gp, xu);
-    else if (s == 2) grad_units_kernel<P, SC_IRK, 2><<<g, 256, 0, st>>>(gp, xu);
-    else grad_units_kernel<P, SC_IRK, 3><<<g, 256, 0, st>>>(gp, xu);
+    if (grid > 0)          // (else a Mayer-only cost: nothing to integrate)
+        for_scheme<false>(gp.L, [&](auto t) { grad_units_kernel<P, t.sc, t.s><<<g, 256, 0, st>>>(gp, xu); });
     grad_finish_kernel<P><<<dim3(1, batch), 64, 0, st>>>(gp, xu);
     return hipGetLastError();
 }
@@ -707,18 +703,11 @@ hipError_t launch_variant(const KParams& kp, const double* xu, int grid, int blo
 }
 
 template <class P>
-hipError_t launch_cons_jac(int sc, const KParams& kp, const double* xu, int grid, int block, size_t lds_bytes, hipStream_t st,
+hipError_t launch_cons_jac(const KParams& kp, const double* xu, int grid, int block, size_t lds_bytes, hipStream_t st,
                            hipEvent_t e0, hipEvent_t e1) {
-    if (sc == SC_TRAPEZE) return launch_variant<P, SC_TRAPEZE, 1>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-    if (sc == SC_MIDPOINT) {       // (midpoint: the template's stage count is control_steps -- 1 in collocation, up to 3 compiled in)
-        if (kp.L.cs == 2) return launch_variant<P, SC_MIDPOINT, 2>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-        if (kp.L.cs == 3) return launch_variant<P, SC_MIDPOINT, 3>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-        if (kp.L.cs > 3) return hipErrorInvalidValue;
-        return launch_variant<P, SC_MIDPOINT, 1>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-    }
-    if (kp.L.s == 1) return launch_variant<P, SC_IRK, 1>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-    if (kp.L.s == 2) return launch_variant<P, SC_IRK, 2>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-    return launch_variant<P, SC_IRK, 3>(kp, xu, grid, block, lds_bytes, st, e0, e1);
+    hipError_t e = hipErrorInvalidValue;       // (midpoint: the template's stage count is control_steps -- 1 in collocation, up to 3 compiled in)
+    for_scheme<true>(kp.L, [&](auto t) { e = launch_variant<P, t.sc, t.s>(kp, xu, grid, block, lds_bytes, st, e0, e1); });
+    return e;
 }
 
 // resident workgroups per CU of the kernel launch_cons_jac would run (registers and LDS): sizes the multi-tile grid
@@ -743,59 +732,46 @@ hipError_t launch_variant_batch(const KParams& kp, const double* xu, const Batch
     return hipGetLastError();
 }
 template <class P>
-hipError_t launch_cons_jac_batch(int sc, const KParams& kp, const double* xu, const BatchLd& bl, int grid, int block, size_t lds_bytes,
+hipError_t launch_cons_jac_batch(const KParams& kp, const double* xu, const BatchLd& bl, int grid, int block, size_t lds_bytes,
                                  hipStream_t st, int batch) {
-    if (sc == SC_TRAPEZE) return launch_variant_batch<P, SC_TRAPEZE, 1>(kp, xu, bl, grid, block, lds_bytes, st, batch);
-    if (sc == SC_MIDPOINT) {
-        if (kp.L.cs == 2) return launch_variant_batch<P, SC_MIDPOINT, 2>(kp, xu, bl, grid, block, lds_bytes, st, batch);
-        if (kp.L.cs == 3) return launch_variant_batch<P, SC_MIDPOINT, 3>(kp, xu, bl, grid, block, lds_bytes, st, batch);
-        if (kp.L.cs > 3) return hipErrorInvalidValue;
-        return launch_variant_batch<P, SC_MIDPOINT, 1>(kp, xu, bl, grid, block, lds_bytes, st, batch);
-    }
-    if (kp.L.s == 1) return launch_variant_batch<P, SC_IRK, 1>(kp, xu, bl, grid, block, lds_bytes, st, batch);
-    if (kp.L.s == 2) return launch_variant_batch<P, SC_IRK, 2>(kp, xu, bl, grid, block, lds_bytes, st, batch);
-    return launch_variant_batch<P, SC_IRK, 3>(kp, xu, bl, grid, block, lds_bytes, st, batch);
+    hipError_t e = hipErrorInvalidValue;
+    for_scheme<true>(kp.L, [&](auto t) { e = launch_variant_batch<P, t.sc, t.s>(kp, xu, bl, grid, block, lds_bytes, st, batch); });
+    return e;
+}
+
+// (0 for the midpoint scheme with more than 3 controls per step, which the launchers refuse: ctd_create refuses such a handle for a
+// registry problem on a device, and the caller asks for Gauss-Legendre or control_steps = 1 only)
+template <class P>
+int occupancy_cons_jac(const KParams& kp, int block, size_t lds_bytes) {
+    int nb = 0;
+    for_scheme<true>(kp.L, [&](auto t) { nb = occupancy_variant<P, t.sc, t.s>(block, lds_bytes); });
+    return nb;
 }
 
 template <class P>
-int occupancy_cons_jac(int sc, const KParams& kp, int block, size_t lds_bytes) {
-    if (sc == SC_TRAPEZE) return occupancy_variant<P, SC_TRAPEZE, 1>(block, lds_bytes);
-    if (sc == SC_MIDPOINT) {
-        if (kp.L.cs == 2) return occupancy_variant<P, SC_MIDPOINT, 2>(block, lds_bytes);
-        if (kp.L.cs == 3) return occupancy_variant<P, SC_MIDPOINT, 3>(block, lds_bytes);
-        return occupancy_variant<P, SC_MIDPOINT, 1>(block, lds_bytes);
-    }
-    if (kp.L.s == 1) return occupancy_variant<P, SC_IRK, 1>(block, lds_bytes);
-    if (kp.L.s == 2) return occupancy_variant<P, SC_IRK, 2>(block, lds_bytes);
-    return occupancy_variant<P, SC_IRK, 3>(block, lds_bytes);
-}
-
-template <class P>
-hipError_t launch_obj(int sc, const ObjParams& op, const double* xu, int grid, int block, hipStream_t st, int batch) {
+hipError_t launch_obj(const ObjParams& op, const double* xu, int grid, int block, hipStream_t st, int batch) {
     const dim3 g(grid > 0 ? grid : 1, batch);
-    if (grid <= 0) {}      // Mayer-only cost: nothing to integrate
-    else if (sc == SC_TRAPEZE) obj_partial_kernel<P, SC_TRAPEZE><<<g, block, 0, st>>>(op, xu);
-    else if (sc == SC_MIDPOINT) obj_partial_kernel<P, SC_MIDPOINT><<<g, block, 0, st>>>(op, xu);
-    else obj_partial_kernel<P, SC_IRK><<<g, block, 0, st>>>(op, xu);
+    if (grid > 0)          // (else a Mayer-only cost: nothing to integrate; the quadrature kernel has no stage count)
+        for_scheme<false>(op.L, [&](auto t) { obj_partial_kernel<P, t.sc><<<g, block, 0, st>>>(op, xu); });
     obj_finish_kernel<P><<<dim3(1, batch), 64, 0, st>>>(op, xu);
     return hipGetLastError();
 }
 
 #define CTD_INSTANTIATE_LAUNCHERS(P)                                                                                       \
-    template hipError_t launch_cons_jac<P>(int, const KParams&, const double*, int, int, size_t, hipStream_t, hipEvent_t, \
+    template hipError_t launch_cons_jac<P>(const KParams&, const double*, int, int, size_t, hipStream_t, hipEvent_t, \
                                            hipEvent_t);                                                                    \
-    template hipError_t launch_cons_jac_batch<P>(int, const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, int); \
-    template hipError_t launch_obj<P>(int, const ObjParams&, const double*, int, int, hipStream_t, int);                  \
-    template int occupancy_cons_jac<P>(int, const KParams&, int, size_t);                                                 \
-    template hipError_t launch_grad<P>(int, int, const GradParams&, const double*, int, hipStream_t, int);
+    template hipError_t launch_cons_jac_batch<P>(const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, int); \
+    template hipError_t launch_obj<P>(const ObjParams&, const double*, int, int, hipStream_t, int);                  \
+    template int occupancy_cons_jac<P>(const KParams&, int, size_t);                                                 \
+    template hipError_t launch_grad<P>(const GradParams&, const double*, int, hipStream_t, int);
 #define CTD_EXTERN_LAUNCHERS(P)                                                                                            \
-    extern template hipError_t launch_cons_jac<P>(int, const KParams&, const double*, int, int, size_t, hipStream_t,      \
+    extern template hipError_t launch_cons_jac<P>(const KParams&, const double*, int, int, size_t, hipStream_t,      \
                                                   hipEvent_t, hipEvent_t);                                                 \
-    extern template hipError_t launch_cons_jac_batch<P>(int, const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, \
+    extern template hipError_t launch_cons_jac_batch<P>(const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, \
                                                         int);                                                                      \
-    extern template hipError_t launch_obj<P>(int, const ObjParams&, const double*, int, int, hipStream_t, int);          \
-    extern template int occupancy_cons_jac<P>(int, const KParams&, int, size_t);                                         \
-    extern template hipError_t launch_grad<P>(int, int, const GradParams&, const double*, int, hipStream_t, int);
+    extern template hipError_t launch_obj<P>(const ObjParams&, const double*, int, int, hipStream_t, int);          \
+    extern template int occupancy_cons_jac<P>(const KParams&, int, size_t);                                         \
+    extern template hipError_t launch_grad<P>(const GradParams&, const double*, int, hipStream_t, int);
 
 #endif  // !__HIPCC_RTC__
 

@@ -41,6 +41,29 @@ struct Layout {
                            // (direct shooting, src/direct_shooting.jl:55-71; sub-step dynamics midpoint.jl:137-155)
 };
 
+// static dispatch over the <SC, S> kernel instantiations (host side, like for_problem): f(SchemeTag<SC, S>{}) for L's scheme --
+// trapeze <., 1>, Gauss-Legendre <., s>, s = 1..3 -- and true; false, f not called, when there is no such instantiation.
+// MidpointCs: the kernel family's S for the midpoint class is control_steps (1..3 compiled in, more is refused) -- the constraint /
+// Jacobian and Hessian kernels, which unroll over the controls of a step; otherwise the midpoint class is <., 1> whatever cs is.
+// Only the MidpointCs form can return false; its callers preset their result to the refusal (hipErrorInvalidValue, 0) and so, like
+// the callers of the other form, need not look at the bool.  The branches are in the order the kernels have always been instantiated.
+template <int SC, int S> struct SchemeTag { static constexpr int sc = SC, s = S; };
+template <bool MidpointCs, class F> inline bool for_scheme(const Layout& L, F&& f) {
+    if (L.sc == SC_TRAPEZE) f(SchemeTag<SC_TRAPEZE, 1>{});
+    else if (L.sc == SC_MIDPOINT) {
+        if constexpr (MidpointCs) {        // (if constexpr: the other families must not instantiate <SC_MIDPOINT, 2 / 3>)
+            if (L.cs == 2) f(SchemeTag<SC_MIDPOINT, 2>{});
+            else if (L.cs == 3) f(SchemeTag<SC_MIDPOINT, 3>{});
+            else if (L.cs > 3) return false;
+            else f(SchemeTag<SC_MIDPOINT, 1>{});
+        } else f(SchemeTag<SC_MIDPOINT, 1>{});
+    }
+    else if (L.s == 1) f(SchemeTag<SC_IRK, 1>{});
+    else if (L.s == 2) f(SchemeTag<SC_IRK, 2>{});
+    else f(SchemeTag<SC_IRK, 3>{});
+    return true;
+}
+
 // Butcher entries for a stage index j that differs between the lanes of a wave.  The tables sit in the kernel arguments:
 // indexed with a vector register they cost a global load (and a full memory latency) per use, selected from the S scalar
 // values they stay in scalar registers.  Same values, so the arithmetic is unchanged.

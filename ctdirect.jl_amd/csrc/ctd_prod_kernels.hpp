@@ -41,9 +41,11 @@ struct ProdParams {
 };
 
 // directions per jtprod lane: three for the wide OCPs -- their Gauss-Legendre 3 lanes need 256 registers with three and spill
-// with four (288 bytes of scratch per lane for the 12-state quadrotor); fewer chunks mean fewer repeated primal evaluations
+// with four (288 bytes of scratch per lane for the 12-state quadrotor); fewer chunks mean fewer repeated primal evaluations.
+// The host sizes the grid of a run-time OCP with the same function (n states, dc = its DC).
+CTD_HD constexpr int jtprod_chunk(int n, int dc) { return n >= 8 ? 3 : (dc < 4 ? dc : 4); }
 template <class P> struct ProdDirs {
-    static constexpr int JC = P::NX >= 8 ? 3 : (P::DC < 4 ? P::DC : 4);
+    static constexpr int JC = jtprod_chunk(P::NX, P::DC);
 };
 
 // direction id of entry c of an input category (base < 0: the category carries no direction in this evaluation)
@@ -226,6 +228,35 @@ __device__ __forceinline__ void prod_boundary_rows(const ProdParams& pp, const S
     }
 }
 
+// the part of a number that holds the derivatives along a lane's JC directions: the tangents of a Dual, the mixed second
+// derivatives of a Dual2 (whose tangent a is the direction of the Hessian product)
+template <int K> CTD_HD double dir_part(const Dual<K>& x, int d) { return x.d[d]; }
+template <int K> CTD_HD double dir_part(const Dual2<K>& x, int d) { return x.ab[d]; }
+// sink of the row evaluators for the transposed products: acc[d] += w[r0 + r] * (row r's derivative along direction d).
+// The sink keeps REFERENCES to w and acc, as the lambdas written out in the lanes did (captured by value, the lanes' code
+// objects change): pass w as a named pointer that outlives the sink, never an expression such as `w + off`.
+template <int JC> __device__ __forceinline__ auto weighted_rows(const double* const& w, int64_t r0, double (&acc)[JC]) {
+    return [&w, r0, &acc](int r, const auto& val) {
+        const double wr = w[r0 + r];
+#pragma unroll
+        for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * dir_part(val, d);
+    };
+}
+// the tail of a lane: entry d of acc belongs to direction g0 + d of the node -- block entries [0, bk) go to out, v entries
+// [bk, bk + NV) to gv
+template <int JC, int NV> __device__ __forceinline__ void prod_write_out(const double* acc, int g0, int bk, double* out, double* gv) {
+#pragma unroll
+    for (int d = 0; d < JC; ++d) {
+        const int g = g0 + d;
+        if (g < bk) out[g] = acc[d];
+        else if (g < bk + NV) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (g - bk == j) gv[j] = acc[d];
+        }
+    }
+}
+
 // ---- jprod ----------------------------------------------------------------------------------------------------------------
 template <class P, int SC, int S>
 __device__ __forceinline__ void jprod_unit_body(const ProdParams& pp, const double* __restrict__ xu, int64_t k) {
@@ -319,18 +350,11 @@ __device__ __forceinline__ void jtprod_irk_step(const ProdParams& pp, const doub
         for (int d = 0; d < JC; ++d) acc[d] = acc[d] - wr * (hi.d[d] * sb);
     }
     // path rows of node k (X_k, own controls, v), and of node N when it reads this step's controls
-    auto sink_at = [&](int64_t rp) {
-        return [&, rp](int r, const T& val) {
-            const double wr = w[rp + r];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.d[d];
-        };
-    };
     if (P::NPATH > 0) {
-        auto sink = sink_at(r0 + L.eqs);
+        auto sink = weighted_rows<JC>(w, r0 + L.eqs, acc);
         prod_path_rows<P, SC_IRK, S, T>(pp, src, k, 0, du, dv, sink);
         if (k + 1 == L.N && g0 + JC > du && g0 < dv) {
-            auto fsink = sink_at(L.N * (int64_t)L.cb);
+            auto fsink = weighted_rows<JC>(w, L.N * (int64_t)L.cb, acc);
             prod_path_rows<P, SC_IRK, S, T>(pp, src, k + 1, -1, du, -1, fsink);
         }
     }
@@ -383,21 +407,11 @@ __device__ __forceinline__ void jtprod_unit_body(const ProdParams& pp, const dou
     const bool hits_u = g0 < n + L.cu && g0 + JC > n && m > 0;      // ... or control directions
     // rows of step k and path rows of node k: every input of node k carries its direction
     if (k < L.N) {
-        const int64_t r0 = k * (int64_t)L.cb;
-        auto sink = [&](int r, const Dual<JC>& val) {
-            const double wr = w[r0 + r];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.d[d];
-        };
+        auto sink = weighted_rows<JC>(w, k * (int64_t)L.cb, acc);
         prod_step_rows<P, SC, S, Dual<JC>>(pp, src, k, ProdRoles{0, n, -1, -1, bk}, sink);
     }
     if (P::NPATH > 0) {
-        const int64_t rp = k < L.N ? k * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb;
-        auto sink = [&](int r, const Dual<JC>& val) {
-            const double wr = w[rp + r];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.d[d];
-        };
+        auto sink = weighted_rows<JC>(w, k < L.N ? k * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb, acc);
         prod_path_rows<P, SC, S, Dual<JC>>(pp, src, k, 0, path_ctrl_node(L, k) == k ? n : -1, bk, sink);
     }
     // rows of step k-1: they read X_k (and U_k on the trapeze)
@@ -411,109 +425,86 @@ __device__ __forceinline__ void jtprod_unit_body(const ProdParams& pp, const dou
                     if (g0 + d < n) acc[d] = acc[d] + w[r0 + g0 + d];
             }
         } else if (hits_x || (SC == SC_TRAPEZE && hits_u)) {
-            auto sink = [&](int r, const Dual<JC>& val) {
-                const double wr = w[r0 + r];
-#pragma unroll
-                for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.d[d];
-            };
+            auto sink = weighted_rows<JC>(w, r0, acc);
             prod_step_rows<P, SC, S, Dual<JC>>(pp, src, k - 1, ProdRoles{-1, -1, 0, n, -1}, sink);
         }
     }
     // path rows of node k+1 when they read U_k
     if (P::NPATH > 0 && k < L.N && path_ctrl_node(L, k + 1) == k && hits_u) {
-        const int64_t rp = k + 1 < L.N ? (k + 1) * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb;
-        auto sink = [&](int r, const Dual<JC>& val) {
-            const double wr = w[rp + r];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.d[d];
-        };
+        auto sink = weighted_rows<JC>(w, k + 1 < L.N ? (k + 1) * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb, acc);
         prod_path_rows<P, SC, S, Dual<JC>>(pp, src, k + 1, -1, n, -1, sink);
     }
-    double* out = pp.out + k * (int64_t)L.blk;
-#pragma unroll
-    for (int d = 0; d < JC; ++d) {
-        const int g = g0 + d;
-        if (g < bk) out[g] = acc[d];
-        else if (g < bk + nv) {
-#pragma unroll
-            for (int j = 0; j < nv; ++j)
-                if (g - bk == j) gv[j] = acc[d];
-        }
-    }
+    prod_write_out<JC, nv>(acc, g0, bk, pp.out + k * (int64_t)L.blk, gv);
 }
 
-// body of the unit pass for workgroup `block` (wsum: 4 * kMaxNV doubles of LDS)
-template <class P, int SC, int S>
-__device__ __forceinline__ void jtprod_units_body(const ProdParams& pp, const double* __restrict__ xu, int block, double (*wsum)[kMaxNV]) {
-    constexpr int nv = P::NV;
-    double gv[nv > 0 ? nv : 1];
+// the unit pass of a transposed product for workgroup `block` (wsum: 4 * kMaxNV doubles of LDS): thread id = (node k, chunk q),
+// lane(k, q, gv) writes the entries of its own block and leaves its d/dv entries in gv; their sum over the workgroup becomes row
+// `block` of pp.partial (block_partial_sums, ctd_common.hpp)
+template <int NV, class Lane>
+__device__ __forceinline__ void prod_units_body(const ProdParams& pp, int block, double (*wsum)[kMaxNV], Lane&& lane) {
+    double gv[NV > 0 ? NV : 1];
 #pragma unroll
-    for (int j = 0; j < nv; ++j) gv[j] = 0.0;
+    for (int j = 0; j < NV; ++j) gv[j] = 0.0;
     const int64_t id = (int64_t)block * blockDim.x + threadIdx.x;
     const int64_t k = id / pp.nch;
-    if (k <= pp.L.N) jtprod_unit_body<P, SC, S>(pp, xu, k, (int)(id - k * pp.nch), gv);
-    if constexpr (nv > 0) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int j = 0; j < nv; ++j) {
-            double s = gv[j];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-            if (lane == 0) wsum[wave][j] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int j = 0; j < nv; ++j) {
-                double s = 0.0;
-                for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) s += wsum[wv][j];
-                pp.partial[(int64_t)block * kMaxNV + j] = s;
-            }
-        }
-    }
+    if (k <= pp.L.N) lane(k, (int)(id - k * pp.nch), gv);
+    if constexpr (NV > 0) block_partial_sums<NV, kMaxNV>(gv, &wsum[0][0], pp.partial + (int64_t)block * kMaxNV);
 }
 
 template <class P, int SC, int S>
 __global__ void __launch_bounds__(256) jtprod_units_kernel(const ProdParams pp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    jtprod_units_body<P, SC, S>(pp, xu, (int)blockIdx.x, wsum);
+    prod_units_body<P::NV>(pp, (int)blockIdx.x, wsum, [&](int64_t k, int q, double* gv) { jtprod_unit_body<P, SC, S>(pp, xu, k, q, gv); });
 }
 
-// one wave: the v partials in block order (lane l adds blocks l, l + 64, ..., then a fixed shuffle tree), and the boundary rows'
-// contributions -- lane q differentiates chunk q of (X_1, X_{N+1}, v) and adds to the entries it owns
-template <class P>
-__device__ __forceinline__ void jtprod_finish_body(const ProdParams& pp, const double* __restrict__ xu, double* bv) {
-    constexpr int n = P::NX, nv = P::NV, nb = P::NBC, JC = ProdDirs<P>::JC;
+// the finish of a transposed product, one wave: the boundary rows (and, SECOND order: the Mayer term, weight sigma) -- lane l
+// differentiates chunks l, l + 64, ... of (X_1, X_{N+1}, v), JC directions each, on the numbers make_src(g0) seeds, and adds to the
+// entries it owns -- then the v partials in block order (ordered_rows_sum, ctd_common.hpp).  First order (jtprod): pp.dir is never
+// null and the objective has no part in it; second order (hprod): the rows only with multipliers.
+template <class P, int JC, bool SECOND, class MakeSrc>
+__device__ __forceinline__ void prod_finish_body(const ProdParams& pp, double* bv, MakeSrc&& make_src, double sigma = 0.0) {
+    constexpr int n = P::NX, nv = P::NV, nb = P::NBC;
+    constexpr bool MAYER = SECOND && P::HAS_MAYER;
     const Layout& L = pp.L;
     const int lane = (int)threadIdx.x;
     if (lane < kMaxNV) bv[lane] = 0.0;
     __syncthreads();
-    if (nb > 0 && lane * JC < 2 * n + nv) {
-        const int g0 = lane * JC;
-        const SeedSrc<JC> src{xu, g0};
-        const int64_t rb = L.ncon - L.bc;
-        double acc[JC];
-#pragma unroll
-        for (int d = 0; d < JC; ++d) acc[d] = 0.0;
-        auto sink = [&](int r, const Dual<JC>& val) {
-            const double wr = pp.dir[rb + r];
-#pragma unroll
-            for (int d = 0; d < JC; ++d) acc[d] = acc[d] + wr * val.d[d];
-        };
-        prod_boundary_rows<P, Dual<JC>>(pp, src, true, sink);
+    const bool rows = nb > 0 && (!SECOND || pp.dir != nullptr);
+    if (rows || MAYER) {
         const int64_t gf = L.N * (int64_t)L.blk;
+        for (int g0 = lane * JC; g0 < 2 * n + nv; g0 += 64 * JC) {
+            const auto src = make_src(g0);
+            using T = decltype(src.at(0, 0));
+            double acc[JC];
 #pragma unroll
-        for (int d = 0; d < JC; ++d) {
-            const int g = g0 + d;
-            if (g < n) pp.out[g] += acc[d];
-            else if (g < 2 * n) pp.out[gf + g - n] += acc[d];
-            else if (g < 2 * n + nv) bv[g - 2 * n] = acc[d];
+            for (int d = 0; d < JC; ++d) acc[d] = 0.0;
+            if (rows) {
+                auto sink = weighted_rows<JC>(pp.dir, L.ncon - L.bc, acc);
+                prod_boundary_rows<P, T>(pp, src, true, sink);
+            }
+            if constexpr (MAYER) {        // src/DOCP_functions.jl:35-48; directions as the boundary rows'
+                T x0[n > 0 ? n : 1], xf[n > 0 ? n : 1], V[nv > 0 ? nv : 1];
+#pragma unroll
+                for (int c = 0; c < n; ++c) { x0[c] = src.at(c, c); xf[c] = src.at(gf + c, n + c); }
+#pragma unroll
+                for (int j = 0; j < nv; ++j) V[j] = src.at(L.v_off + j, 2 * n + j);
+                const T r = P::template mayer<T>(x0, xf, V);
+#pragma unroll
+                for (int d = 0; d < JC; ++d) acc[d] = acc[d] + sigma * dir_part(r, d);
+            }
+#pragma unroll
+            for (int d = 0; d < JC; ++d) {
+                const int g = g0 + d;
+                if (g < n) pp.out[g] += acc[d];
+                else if (g < 2 * n) pp.out[gf + g - n] += acc[d];
+                else if (g < 2 * n + nv) bv[g - 2 * n] = acc[d];
+            }
         }
     }
     __syncthreads();
     if constexpr (nv > 0) {
         for (int j = 0; j < nv; ++j) {
-            double s = 0.0;
-            for (int b = lane; b < pp.nblocks; b += 64) s += pp.partial[(int64_t)b * kMaxNV + j];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+            const double s = ordered_rows_sum<kMaxNV>(pp.partial, pp.nblocks, j);
             if (lane == 0) pp.out[L.v_off + j] = s + bv[j];
         }
     }
@@ -522,45 +513,42 @@ __device__ __forceinline__ void jtprod_finish_body(const ProdParams& pp, const d
 template <class P>
 __global__ void __launch_bounds__(64) jtprod_finish_kernel(const ProdParams pp, const double* __restrict__ xu) {
     __shared__ double bv[kMaxNV];
-    jtprod_finish_body<P>(pp, xu, bv);
+    constexpr int JC = ProdDirs<P>::JC;
+    prod_finish_body<P, JC, false>(pp, bv, [&](int g0) { return SeedSrc<JC>{xu, g0}; });
 }
 
 #if !defined(__HIPCC_RTC__)
 // ---- launchers (instantiated per registry problem in ctd_pkern_*.hip) ---------------------------------------------------
 template <class P>
 hipError_t launch_jprod(const ProdParams& pp, const double* xu, hipStream_t st) {
-    const int sc = pp.L.sc, s = pp.L.s;
     const unsigned grid = (unsigned)((pp.L.N + 1 + 255) / 256);
-    if (sc == SC_TRAPEZE) jprod_kernel<P, SC_TRAPEZE, 1><<<grid, 256, 0, st>>>(pp, xu);
-    else if (sc == SC_MIDPOINT) jprod_kernel<P, SC_MIDPOINT, 1><<<grid, 256, 0, st>>>(pp, xu);
-    else if (s == 1) jprod_kernel<P, SC_IRK, 1><<<grid, 256, 0, st>>>(pp, xu);
-    else if (s == 2) jprod_kernel<P, SC_IRK, 2><<<grid, 256, 0, st>>>(pp, xu);
-    else jprod_kernel<P, SC_IRK, 3><<<grid, 256, 0, st>>>(pp, xu);
+    for_scheme<false>(pp.L, [&](auto t) { jprod_kernel<P, t.sc, t.s><<<grid, 256, 0, st>>>(pp, xu); });
     return hipGetLastError();
 }
-// pp.nblocks / pp.nch / pp.partial filled in by the caller (prod_layout)
-template <class P>
-hipError_t launch_jtprod(const ProdParams& pp, const double* xu, hipStream_t st) {
-    const int sc = pp.L.sc, s = pp.L.s;
-    const unsigned grid = (unsigned)pp.nblocks;
-    if (sc == SC_TRAPEZE) jtprod_units_kernel<P, SC_TRAPEZE, 1><<<grid, 256, 0, st>>>(pp, xu);
-    else if (sc == SC_MIDPOINT) jtprod_units_kernel<P, SC_MIDPOINT, 1><<<grid, 256, 0, st>>>(pp, xu);
-    else if (s == 1) jtprod_units_kernel<P, SC_IRK, 1><<<grid, 256, 0, st>>>(pp, xu);
-    else if (s == 2) jtprod_units_kernel<P, SC_IRK, 2><<<grid, 256, 0, st>>>(pp, xu);
-    else jtprod_units_kernel<P, SC_IRK, 3><<<grid, 256, 0, st>>>(pp, xu);
-    jtprod_finish_kernel<P><<<1, 64, 0, st>>>(pp, xu);
+// A transposed product: K names its argument struct (Params; prod(a): the ProdParams inside) and its two kernels.  The units
+// kernel over nblocks workgroups, then the finish kernel on one wave; nblocks / nch / partial filled in by the caller
+// (enqueue_prod_units, ctd_engine.hip)
+struct JtprodKernels {
+    using Params = ProdParams;
+    static ProdParams& prod(Params& a) { return a; }
+    static const ProdParams& prod(const Params& a) { return a; }
+    template <class P, int SC, int S> static constexpr auto units = &jtprod_units_kernel<P, SC, S>;
+    template <class P> static constexpr auto finish = &jtprod_finish_kernel<P>;
+};
+template <class P, class K>
+hipError_t launch_prod_units(const typename K::Params& a, const double* xu, hipStream_t st) {
+    const ProdParams& pp = K::prod(a);
+    for_scheme<false>(pp.L, [&](auto t) { K::template units<P, t.sc, t.s><<<(unsigned)pp.nblocks, 256, 0, st>>>(a, xu); });
+    K::template finish<P><<<1, 64, 0, st>>>(a, xu);
     return hipGetLastError();
 }
-template <class P> int prod_chunk() { return ProdDirs<P>::JC; }
 
 #define CTD_INSTANTIATE_PROD(P)                                                     \
     template hipError_t launch_jprod<P>(const ProdParams&, const double*, hipStream_t);  \
-    template hipError_t launch_jtprod<P>(const ProdParams&, const double*, hipStream_t); \
-    template int prod_chunk<P>();
+    template hipError_t launch_prod_units<P, JtprodKernels>(const ProdParams&, const double*, hipStream_t);
 #define CTD_EXTERN_PROD(P)                                                                 \
     extern template hipError_t launch_jprod<P>(const ProdParams&, const double*, hipStream_t);  \
-    extern template hipError_t launch_jtprod<P>(const ProdParams&, const double*, hipStream_t); \
-    extern template int prod_chunk<P>();
+    extern template hipError_t launch_prod_units<P, JtprodKernels>(const ProdParams&, const double*, hipStream_t);
 #endif  // !__HIPCC_RTC__
 
 }  // namespace ctd
