@@ -58,7 +58,7 @@ template <class T = double> struct DevBuf {
 };
 
 // the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each, loaded at first use (jit_load)
-enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, kJitFamilies };
+enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, kJitFamilies };
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t f[5] = {};        // in the order of the family's name expressions (kJit)
@@ -315,15 +315,20 @@ std::vector<std::string> jit_batch_exprs(int sc, int s) {
     const std::string b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
     return {"ctd::cons_jac_batch_kernel<ctd::UserOCP, " + std::to_string(sc) + ", " + b + ">"};
 }
-std::vector<std::string> jit_prod_exprs(int sc, int s) {
+// sh: ", true" for the shard form of the product kernels (a family of its own, compiled by the first shard call), "" otherwise
+std::vector<std::string> prod_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
-    return {"ctd::jprod_kernel<ctd::UserOCP, " + a + ", " + b + ">", "ctd::jtprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">",
-            "ctd::jtprod_finish_kernel<ctd::UserOCP>"};
+    return {"ctd::jprod_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::jtprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">",
+            "ctd::jtprod_finish_kernel<ctd::UserOCP" + sh + ">"};
 }
-std::vector<std::string> jit_hprod_exprs(int sc, int s) {
+std::vector<std::string> hprod_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
-    return {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">", "ctd::hprod_finish_kernel<ctd::UserOCP>"};
+    return {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::hprod_finish_kernel<ctd::UserOCP" + sh + ">"};
 }
+std::vector<std::string> jit_prod_exprs(int sc, int s) { return prod_exprs(sc, s, ""); }
+std::vector<std::string> jit_hprod_exprs(int sc, int s) { return hprod_exprs(sc, s, ""); }
+std::vector<std::string> jit_prod_shard_exprs(int sc, int s) { return prod_exprs(sc, s, ", true"); }
+std::vector<std::string> jit_hprod_shard_exprs(int sc, int s) { return hprod_exprs(sc, s, ", true"); }
 
 // one row per JitFamily: the header, -ffp-contract, the name expressions
 const struct { const char* header; const char* fp_contract; std::vector<std::string> (*exprs)(int sc, int s); } kJit[kJitFamilies] = {
@@ -332,6 +337,8 @@ const struct { const char* header; const char* fp_contract; std::vector<std::str
     {"ctd_prod_kernels.hpp", "off", jit_prod_exprs},        // jprod, jtprod_units, jtprod_finish
     {"ctd_hprod_kernels.hpp", "off", jit_hprod_exprs},      // hprod_units, hprod_finish
     {"ctd_hess_kernels.hpp", "fast", jit_hess_exprs},       // hess, hess_finish
+    {"ctd_prod_kernels.hpp", "off", jit_prod_shard_exprs},  // the shard forms of jprod, jtprod_units, jtprod_finish
+    {"ctd_hprod_kernels.hpp", "off", jit_hprod_shard_exprs},    // ... and of hprod_units, hprod_finish
 };
 
 // batch: the grid's second dimension (members of a batched launch)
@@ -383,13 +390,14 @@ static int32_t host_call(ctd_handle* h, std::initializer_list<Staged<const doubl
 // The unit pass and the finish of a transposed product (jtprod, hprod): `dirs` directions per node in chunks of jc -- the
 // ProdDirs / HProdDirs of a registry problem, the same formula for a run-time OCP -- give the geometry and the size of the caller's
 // partial buffer, written into a's ProdParams; then the two kernels: f[f0], f[f0 + 1] of the run-time OCP's module, or
-// launch_prod_units.  a: the kernels' argument struct
+// launch_prod_units.  a: the kernels' argument struct, its unit range set by the caller (prod_units): the grid and the partial
+// sums cover those nodes -- all N + 1 of a whole-grid call; shard: the shard form of the kernels
 template <class K>
 static int32_t enqueue_prod_units(ctd_handle* h, const char* fn, typename K::Params& a, int dirs, int jc, DevBuf<>& partial,
-                                  const JitModule& jm, int f0, const double* x_dev) {
+                                  const JitModule& jm, int f0, const double* x_dev, bool shard) {
     ProdParams& pp = K::prod(a);
     pp.nch = (int32_t)((dirs + jc - 1) / jc);
-    const int64_t blocks = ((pp.L.N + 1) * (int64_t)pp.nch + 255) / 256;
+    const int64_t blocks = ((pp.unit_end - pp.unit_begin) * (int64_t)pp.nch + 255) / 256;
     if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
     pp.nblocks = (int32_t)blocks;
     const int32_t st = partial.grow(h, blocks * kMaxNV, fn);
@@ -401,7 +409,10 @@ static int32_t enqueue_prod_units(ctd_handle* h, const char* fn, typename K::Par
         e = jit_launch(jm.f[f0], (int)blocks, 256, 0, h->stream, args);
         if (e == hipSuccess) e = jit_launch(jm.f[f0 + 1], 1, 64, 0, h->stream, args);
     }
-    for_problem(h->model.problem, [&](auto tag) { e = launch_prod_units<typename decltype(tag)::type, K>(a, x_dev, h->stream); });
+    for_problem(h->model.problem, [&](auto tag) {
+        using P = typename decltype(tag)::type;
+        e = shard ? launch_prod_units<P, K, true>(a, x_dev, h->stream) : launch_prod_units<P, K, false>(a, x_dev, h->stream);
+    });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
     return CTD_OK;
 }
@@ -1274,20 +1285,36 @@ int32_t ctd_grad(ctd_handle* h, const double* x, double* g) {
 
 // ---- matrix-free Jacobian products: jprod!(nlp, x, v, Jv), jtprod!(nlp, x, w, Jtw) -------------------------------------
 // ctd_prod_kernels.hpp.  Checks in this order: handle, device (CTD_ENODEVICE) -- the prologue, OnDevice(h, fn) --, whole-grid
-// handle, then pointers (CTD_EINVAL).  The enqueue runs under the caller's prologue.
-static int32_t prod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* d, const double* out) {
+// handle (not for the shard calls, which take every handle), then pointers (CTD_EINVAL).  The enqueue runs under the caller's
+// prologue.
+static int32_t prod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* d, const double* out,
+                          bool shard = false) {
     if (on.st) return on.st;
-    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": products need a handle of the whole grid; sharded products (step_begin / step_end, "
-                                   "ctd_set_x_shards) are not supported");
+    if (!shard && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; on a shard handle (step_begin / "
+                                   "step_end, ctd_set_x_shards) call ctd_jprod_shard_dev_async, ctd_jtprod_shard_dev_async or "
+                                   "ctd_hprod_shard_dev_async");
     if (!x || !d || !out) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument");
     if (out == x || out == d) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
     return CTD_OK;
 }
 
-static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, const double* d_dev, double* out_dev) {
-    const char* fn = transpose ? "ctd_jtprod" : "ctd_jprod";
-    if (const int32_t st = jit_load(h, JIT_PROD)) return st;
+// The nodes a product launch evaluates.  Whole grid: all N + 1.  shard: the nodes of the handle's steps [step_begin, step_end),
+// node N too on the last shard; the iterate's entries of other shards through the handle's table when one is set
+static void prod_units(const ctd_handle* h, ProdParams& pp, bool shard) {
+    const int64_t N = h->model.L.N;
+    const bool first = !shard || h->step_begin == 0, last = !shard || h->step_end == N;
+    pp.unit_begin = shard ? h->step_begin : 0;
+    pp.unit_end = last ? N + 1 : h->step_end;
+    pp.owns_first = first ? 1 : 0;
+    pp.owns_last = last ? 1 : 0;
+    if (shard) { pp.halo = h->kp.halo; pp.near = h->kp.near; }
+}
+
+static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, const double* d_dev, double* out_dev, bool shard = false) {
+    const char* fn = transpose ? (shard ? "ctd_jtprod_shard_dev_async" : "ctd_jtprod") : (shard ? "ctd_jprod_shard_dev_async" : "ctd_jprod");
+    const JitFamily fam = shard ? JIT_PROD_SHARD : JIT_PROD;
+    if (const int32_t st = jit_load(h, fam)) return st;
     const Layout& L = h->model.L;
     ProdParams pp;
     std::memset(&pp, 0, sizeof(pp));
@@ -1295,18 +1322,22 @@ static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, 
     pp.tau = h->d_tau.p;
     pp.dir = d_dev;
     pp.out = out_dev;
+    prod_units(h, pp, shard);
     hipError_t e = hipErrorInvalidValue;
     if (!transpose) {
         if (h->rt) {
             void* args[] = {&pp, &x_dev};
-            e = jit_launch(h->jit[JIT_PROD].f[0], (int)((L.N + 1 + 255) / 256), 256, 0, h->stream, args);
+            e = jit_launch(h->jit[fam].f[0], (int)((pp.unit_end - pp.unit_begin + 255) / 256), 256, 0, h->stream, args);
         }
-        for_problem(h->model.problem, [&](auto tag) { e = launch_jprod<typename decltype(tag)::type>(pp, x_dev, h->stream); });
+        for_problem(h->model.problem, [&](auto tag) {
+            using P = typename decltype(tag)::type;
+            e = shard ? launch_jprod<P, true>(pp, x_dev, h->stream) : launch_jprod<P, false>(pp, x_dev, h->stream);
+        });
     } else {
         int jc = 1;
         if (h->rt) jc = jtprod_chunk(h->rt->info.n, h->rt->dc);
         for_problem(h->model.problem, [&](auto tag) { jc = ProdDirs<typename decltype(tag)::type>::JC; });
-        return enqueue_prod_units<JtprodKernels>(h, fn, pp, prod_dirs_per_node(L), jc, h->d_ppartial, h->jit[JIT_PROD], 1, x_dev);
+        return enqueue_prod_units<JtprodKernels>(h, fn, pp, prod_dirs_per_node(L), jc, h->d_ppartial, h->jit[fam], 1, x_dev, shard);
     }
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
     return CTD_OK;
@@ -1321,6 +1352,17 @@ int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w
     const OnDevice on(h, "ctd_jtprod_dev_async");
     const int32_t st = prod_check(on, h, "ctd_jtprod_dev_async", x_dev, w_dev, Jtw_dev);
     return st ? st : enqueue_prod(h, true, x_dev, w_dev, Jtw_dev);
+}
+// the shard's own rows of Jv / entries of Jtw (+ its partial sums of d/dv) from full-length buffers (see include/ctdirect_hip.h)
+int32_t ctd_jprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
+    const OnDevice on(h, "ctd_jprod_shard_dev_async");
+    const int32_t st = prod_check(on, h, "ctd_jprod_shard_dev_async", x_dev, v_dev, Jv_dev, true);
+    return st ? st : enqueue_prod(h, false, x_dev, v_dev, Jv_dev, true);
+}
+int32_t ctd_jtprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
+    const OnDevice on(h, "ctd_jtprod_shard_dev_async");
+    const int32_t st = prod_check(on, h, "ctd_jtprod_shard_dev_async", x_dev, w_dev, Jtw_dev, true);
+    return st ? st : enqueue_prod(h, true, x_dev, w_dev, Jtw_dev, true);
 }
 
 // host pointers: staged through the handle's x buffer and two vectors of nvar / ncon entries
@@ -1340,17 +1382,18 @@ int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw)
 // ---- matrix-free Hessian products: hprod!(nlp, x, y, v, Hv; obj_weight) ------------------------------------------------
 // ctd_hprod_kernels.hpp.  Checks in the order of prod_check; y may be null (objective only) but Hv must not alias it.
 static int32_t hprod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* y, const double* v,
-                           const double* out) {
-    const int32_t st = prod_check(on, h, fn, x, v, out);
+                           const double* out, bool shard = false) {
+    const int32_t st = prod_check(on, h, fn, x, v, out, shard);
     if (st) return st;
     if (y && out == y) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
     return CTD_OK;
 }
 
 static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
-                             double* out_dev) {
-    const char* fn = "ctd_hprod";
-    if (const int32_t st = jit_load(h, JIT_HPROD)) return st;
+                             double* out_dev, bool shard = false) {
+    const char* fn = shard ? "ctd_hprod_shard_dev_async" : "ctd_hprod";
+    const JitFamily fam = shard ? JIT_HPROD_SHARD : JIT_HPROD;
+    if (const int32_t st = jit_load(h, fam)) return st;
     const Layout& L = h->model.L;
     HProdParams hp;
     std::memset(&hp, 0, sizeof(hp));
@@ -1360,10 +1403,11 @@ static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y
     hp.p.out = out_dev;
     hp.vt = v_dev;
     hp.sigma = obj_weight;
+    prod_units(h, hp.p, shard);
     int jc = 1;
     if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
     for_problem(h->model.problem, [&](auto tag) { jc = HProdDirs<typename decltype(tag)::type>::JC; });
-    return enqueue_prod_units<HprodKernels>(h, fn, hp, hprod_dirs_per_node(L), jc, h->d_hppartial, h->jit[JIT_HPROD], 0, x_dev);
+    return enqueue_prod_units<HprodKernels>(h, fn, hp, hprod_dirs_per_node(L), jc, h->d_hppartial, h->jit[fam], 0, x_dev, shard);
 }
 
 int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
@@ -1371,6 +1415,13 @@ int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_
     const OnDevice on(h, "ctd_hprod_dev_async");
     const int32_t st = hprod_check(on, h, "ctd_hprod_dev_async", x_dev, y_dev, v_dev, Hv_dev);
     return st ? st : enqueue_hprod(h, x_dev, y_dev, obj_weight, v_dev, Hv_dev);
+}
+// the shard's own entries of Hv + its partial sums of d/dv (see include/ctdirect_hip.h)
+int32_t ctd_hprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                                  double* Hv_dev) {
+    const OnDevice on(h, "ctd_hprod_shard_dev_async");
+    const int32_t st = hprod_check(on, h, "ctd_hprod_shard_dev_async", x_dev, y_dev, v_dev, Hv_dev, true);
+    return st ? st : enqueue_hprod(h, x_dev, y_dev, obj_weight, v_dev, Hv_dev, true);
 }
 
 // host pointers: x, y and v staged through the handle's x, y and direction buffers

@@ -49,12 +49,15 @@ template <int K> struct HSeedSrc {
     const double* x;
     const double* t;
     int g0;
-    CTD_HD Dual2<K> at(int64_t g, int dir) const {
-        Dual2<K> r; r.v = x[g]; r.a = t[g];
+    XWhere wh;          // (where x is found on a shard: ctd_prod_kernels.hpp; t is always the caller's pointer)
+    CTD_HD const double* buf(int64_t g) const { return (wh.nr && wh.edge) ? xnear(*wh.nr, x, g) : x; }
+    CTD_HD Dual2<K> at(const double* xb, int64_t g, int dir) const {
+        Dual2<K> r; r.v = xb[g]; r.a = t[g];
 #pragma unroll
         for (int d = 0; d < K; ++d) { r.b[d] = (dir >= 0 && dir - g0 == d) ? 1.0 : 0.0; r.ab[d] = 0.0; }
         return r;
     }
+    CTD_HD Dual2<K> at(int64_t g, int dir) const { return at(x, g, dir); }
 };
 
 // Lagrange cost of quadrature unit i (trapeze: node i; otherwise step i) on scalar type T, in the form of lagrange_unit
@@ -64,6 +67,7 @@ __device__ __forceinline__ T prod_lagrange_unit(const ProdParams& pp, const Src&
     constexpr int n = P::NX, m = P::NU, nv = P::NV;
     const Layout& L = pp.L;
     const int64_t b0 = i * (int64_t)L.blk, b1 = (i + 1) * (int64_t)L.blk;
+    const double* x0 = src.buf(b0);
     T V[nv > 0 ? nv : 1], xa[n > 0 ? n : 1], u[m > 0 ? m : 1];
 #pragma unroll
     for (int k = 0; k < nv; ++k) V[k] = src.at(L.v_off + k, prod_dir(ro.v, k));
@@ -71,37 +75,38 @@ __device__ __forceinline__ T prod_lagrange_unit(const ProdParams& pp, const Src&
         const int64_t ia = i == 0 ? 0 : i - 1, ib = i == L.N ? L.N : i + 1;
         const T w = (prod_time<P, T>(pp, V, prod_tau(pp, ib)) - prod_time<P, T>(pp, V, prod_tau(pp, ia))) / 2.0;
 #pragma unroll
-        for (int c = 0; c < n; ++c) xa[c] = src.at(b0 + c, prod_dir(ro.xi, c));
+        for (int c = 0; c < n; ++c) xa[c] = src.at(x0, b0 + c, prod_dir(ro.xi, c));
 #pragma unroll
-        for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + c, prod_dir(ro.bi, c));
+        for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + c, prod_dir(ro.bi, c));
         return w * P::template lagrange<T>(prod_time<P, T>(pp, V, prod_tau(pp, i)), xa, u, V);
     } else {
         const T ti = prod_time<P, T>(pp, V, prod_tau(pp, i)), tip1 = prod_time<P, T>(pp, V, prod_tau(pp, i + 1));
         const T h = tip1 - ti;
         if constexpr (SC == SC_MIDPOINT) {
+            const double* x1 = src.buf(b1);
             if (L.cs > 1) {
                 const T hi = h / (double)L.cs;
 #pragma unroll
-                for (int c = 0; c < n; ++c) xa[c] = 0.5 * (src.at(b0 + c, prod_dir(ro.xi, c)) + src.at(b1 + c, prod_dir(ro.xn, c)));
+                for (int c = 0; c < n; ++c) xa[c] = 0.5 * (src.at(x0, b0 + c, prod_dir(ro.xi, c)) + src.at(x1, b1 + c, prod_dir(ro.xn, c)));
                 T val(0.0);
                 for (int j = 1; j <= L.cs; ++j) {
 #pragma unroll
-                    for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + (j - 1) * m + c, prod_dir(ro.bi, (j - 1) * m + c));
+                    for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + (j - 1) * m + c, prod_dir(ro.bi, (j - 1) * m + c));
                     const T term = hi * P::template lagrange<T>(ti + ((double)j - 0.5) * hi, xa, u, V);
                     val = (j == 1) ? term : val + term;
                 }
                 return val;
             }
 #pragma unroll
-            for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + c, prod_dir(ro.bi, c));
+            for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + c, prod_dir(ro.bi, c));
             if (L.euler == 0) {
 #pragma unroll
-                for (int c = 0; c < n; ++c) xa[c] = 0.5 * (src.at(b0 + c, prod_dir(ro.xi, c)) + src.at(b1 + c, prod_dir(ro.xn, c)));
+                for (int c = 0; c < n; ++c) xa[c] = 0.5 * (src.at(x0, b0 + c, prod_dir(ro.xi, c)) + src.at(x1, b1 + c, prod_dir(ro.xn, c)));
                 return h * P::template lagrange<T>(0.5 * (ti + tip1), xa, u, V);
             }
             const bool expl = L.euler == 1;
 #pragma unroll
-            for (int c = 0; c < n; ++c) xa[c] = expl ? src.at(b0 + c, prod_dir(ro.xi, c)) : src.at(b1 + c, prod_dir(ro.xn, c));
+            for (int c = 0; c < n; ++c) xa[c] = expl ? src.at(x0, b0 + c, prod_dir(ro.xi, c)) : src.at(x1, b1 + c, prod_dir(ro.xn, c));
             return h * P::template lagrange<T>(expl ? ti : tip1, xa, u, V);
         } else {
             const int ko = n + L.cu;
@@ -110,14 +115,14 @@ __device__ __forceinline__ T prod_lagrange_unit(const ProdParams& pp, const Src&
             for (int j = 0; j < S; ++j) {
 #pragma unroll
                 for (int c = 0; c < n; ++c) {
-                    T xc = src.at(b0 + c, prod_dir(ro.xi, c));
+                    T xc = src.at(x0, b0 + c, prod_dir(ro.xi, c));
 #pragma unroll
-                    for (int l = 0; l < S; ++l) xc = xc + h * L.a[3 * j + l] * src.at(b0 + ko + l * n + c, prod_dir(ro.bi, L.cu + l * n + c));
+                    for (int l = 0; l < S; ++l) xc = xc + h * L.a[3 * j + l] * src.at(x0, b0 + ko + l * n + c, prod_dir(ro.bi, L.cu + l * n + c));
                     xa[c] = xc;
                 }
                 const int uo = L.stagewise ? j * m : 0;
 #pragma unroll
-                for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + uo + c, prod_dir(ro.bi, uo + c));
+                for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + uo + c, prod_dir(ro.bi, uo + c));
                 const T term = L.b[j] * P::template lagrange<T>(ti + L.c[j] * h, xa, u, V);
                 local = (j == 0) ? term : local + term;
             }
@@ -128,7 +133,7 @@ __device__ __forceinline__ T prod_lagrange_unit(const ProdParams& pp, const Src&
 
 // lane (node k, chunk q): the JC entries of Hv in directions [q JC, (q + 1) JC) of node k's variables -- its block (bk entries)
 // and v [bk, bk + nv).  Block entries go to Hv, v entries to gv.
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __device__ __forceinline__ void hprod_unit_body(const HProdParams& hp, const double* __restrict__ xu, int64_t k, int q, double* gv) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV, JC = HProdDirs<P>::JC;
     using T = Dual2<JC>;
@@ -137,7 +142,7 @@ __device__ __forceinline__ void hprod_unit_body(const HProdParams& hp, const dou
     const int bk = (k < L.N || SC == SC_TRAPEZE) ? L.blk : n;         // the last node of the other schemes owns X_{N+1} only
     const int g0 = q * JC;
     if (g0 >= bk + nv) return;
-    const HSeedSrc<JC> src{xu, hp.vt, g0};
+    const HSeedSrc<JC> src{xu, hp.vt, g0, prod_where<SH>(pp, k)};
     const double* y = pp.dir;
     double acc[JC];
 #pragma unroll
@@ -185,17 +190,18 @@ __device__ __forceinline__ void hprod_unit_body(const HProdParams& hp, const dou
 }
 
 // the unit pass and the finish of ctd_prod_kernels.hpp (prod_units_body, prod_finish_body) around the second-order lanes
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __global__ void __launch_bounds__(256) hprod_units_kernel(const HProdParams hp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    prod_units_body<P::NV>(hp.p, (int)blockIdx.x, wsum, [&](int64_t k, int q, double* gv) { hprod_unit_body<P, SC, S>(hp, xu, k, q, gv); });
+    prod_units_body<P::NV, SH>(hp.p, (int)blockIdx.x, wsum,
+                               [&](int64_t k, int q, double* gv) { hprod_unit_body<P, SC, S, SH>(hp, xu, k, q, gv); });
 }
 
-template <class P>
+template <class P, bool SH = false>
 __global__ void __launch_bounds__(64) hprod_finish_kernel(const HProdParams hp, const double* __restrict__ xu) {
     __shared__ double bv[kMaxNV];
     constexpr int JC = HProdDirs<P>::JC;
-    prod_finish_body<P, JC, true>(hp.p, bv, [&](int g0) { return HSeedSrc<JC>{xu, hp.vt, g0}; }, hp.sigma);
+    prod_finish_body<P, JC, true, SH>(hp.p, bv, [&](int g0) { return HSeedSrc<JC>{xu, hp.vt, g0, finish_where<SH>(hp.p)}; }, hp.sigma);
 }
 
 #if !defined(__HIPCC_RTC__)
@@ -204,12 +210,15 @@ struct HprodKernels {
     using Params = HProdParams;
     static ProdParams& prod(Params& a) { return a.p; }
     static const ProdParams& prod(const Params& a) { return a.p; }
-    template <class P, int SC, int S> static constexpr auto units = &hprod_units_kernel<P, SC, S>;
-    template <class P> static constexpr auto finish = &hprod_finish_kernel<P>;
+    template <class P, int SC, int S, bool SH> static constexpr auto units = &hprod_units_kernel<P, SC, S, SH>;
+    template <class P, bool SH> static constexpr auto finish = &hprod_finish_kernel<P, SH>;
 };
 
-#define CTD_INSTANTIATE_HPROD(P) template hipError_t launch_prod_units<P, HprodKernels>(const HProdParams&, const double*, hipStream_t);
-#define CTD_EXTERN_HPROD(P) extern template hipError_t launch_prod_units<P, HprodKernels>(const HProdParams&, const double*, hipStream_t);
+#define CTD_HPROD_LAUNCHERS(X, P)                                                                                        \
+    X template hipError_t launch_prod_units<P, HprodKernels, false>(const HProdParams&, const double*, hipStream_t);     \
+    X template hipError_t launch_prod_units<P, HprodKernels, true>(const HProdParams&, const double*, hipStream_t);
+#define CTD_INSTANTIATE_HPROD(P) CTD_HPROD_LAUNCHERS(, P)
+#define CTD_EXTERN_HPROD(P) CTD_HPROD_LAUNCHERS(extern, P)
 #endif  // !__HIPCC_RTC__
 
 }  // namespace ctd

@@ -16,6 +16,9 @@
 //           a fixed order, and jtprod_finish_kernel sums them in block order and adds the boundary rows' contributions to X_1,
 //           X_{N+1} and v.  Deterministic: no atomics, fixed summation order.
 //
+// On a shard of the grid (ctd_jprod_shard_dev_async, ctd_jtprod_shard_dev_async: the SH = true instantiations) the same lanes run
+// over the nodes of the shard's steps only, and the finish adds the boundary rows' entries the shard owns: see ProdParams.
+//
 // The bodies are __device__ functions of (params, x, unit) so other drivers can call them; nothing here reads the emit tables
 // or the pattern, so the products are the same bits for every pattern_mode / value_order of one transcription.
 #pragma once
@@ -38,6 +41,16 @@ struct ProdParams {
     double* partial;        // jtprod: nblocks * kMaxNV partial sums of d/dv
     int32_t nblocks;        // jtprod: workgroups of the unit kernel
     int32_t nch;            // jtprod: direction chunks per node
+    // ON A SHARD (ctd_*prod_shard_dev_async, the SH = true instantiations): the nodes [unit_begin, unit_end) of the handle's steps
+    // -- node N included on the last shard -- are the only ones evaluated; thread ids, the grid and the partial sums count from
+    // unit_begin.  The finish adds the boundary rows' (hprod: and the Mayer term's) part of X_1 on the shard that owns it, of
+    // X_{N+1} and v on the last one.  halo set (ctd_set_x_shards): the iterate's entries of other shards come from their owners'
+    // buffers, resolved with `near` once per region read by the lanes at the shard's two ends and by the finish; null: xu holds
+    // everything the shard reads.  The whole-grid instantiations read none of these.
+    int64_t unit_begin, unit_end;
+    int32_t owns_first, owns_last;
+    const XHalo* halo;
+    XNear near;
 };
 
 // directions per jtprod lane: three for the wide OCPs -- their Gauss-Legendre 3 lanes need 256 registers with three and spill
@@ -52,22 +65,47 @@ template <class P> struct ProdDirs {
 struct ProdRoles { int xi, bi, xn, un, v; };       // X_i, rest of step i's block (controls, stage variables), X_{i+1}, U_{i+1}, v
 CTD_HD int prod_dir(int base, int c) { return base >= 0 ? base + c : -1; }
 
+// Where a source finds the iterate.  x: the launch's own buffer -- v and every block of a whole-grid launch.  On a shard whose
+// iterate is read in place, a lane at one of the shard's ends (edge) asks buf(g) ONCE per region it reads -- the block of a step,
+// X_1, X_{N+1} -- for the buffer that holds it (xnear, ctd_layout.hpp: compares on kernel arguments, no table load); interior
+// lanes and whole-grid launches (nr = null: the test folds away) read x.  The sources' at(xb, g, dir) reads entry g from xb,
+// at(g, dir) from x; directions are always read from the pointer the caller passed.
+// The rule: an edge lane resolves EVERY region it reads, its own blocks included (xnear returns x for those); an interior lane
+// resolves none.  A lane that reads a block of another shard, X_1 or X_{N+1} without being an edge lane is a bug; v is in x always.
+struct XWhere {
+    const XNear* nr = nullptr;
+    bool edge = false;
+};
+// the lanes that may look at the table: the shard's first node when a shard lies below it (it reads step unit_begin - 1), its last
+// node when one lies above (it reads node unit_end), and node N -- jprod's lane of the boundary rows, which read X_1
+template <bool SH> CTD_HD XWhere prod_where(const ProdParams& pp, int64_t k) {
+    if constexpr (SH)
+        return XWhere{&pp.near, pp.halo != nullptr && ((k == pp.unit_begin && !pp.owns_first) || (k + 1 >= pp.unit_end && !pp.owns_last) ||
+                                                       (k == pp.L.N && !pp.owns_first))};
+    else return XWhere{};
+}
 // the tangent of jprod: the direction's entry at the same position of x
 struct FwdSrc {
     const double* x;
     const double* dx;
-    CTD_HD Dual<1> at(int64_t g, int) const { Dual<1> r; r.v = x[g]; r.d[0] = dx[g]; return r; }
+    XWhere wh;
+    CTD_HD const double* buf(int64_t g) const { return (wh.nr && wh.edge) ? xnear(*wh.nr, x, g) : x; }
+    CTD_HD Dual<1> at(const double* xb, int64_t g, int) const { Dual<1> r; r.v = xb[g]; r.d[0] = dx[g]; return r; }
+    CTD_HD Dual<1> at(int64_t g, int dir) const { return at(x, g, dir); }
 };
 // unit seeds of jtprod: direction id `dir` is tangent dir - g0 of this chunk
 template <int K> struct SeedSrc {
     const double* x;
     int g0;
-    CTD_HD Dual<K> at(int64_t g, int dir) const {
-        Dual<K> r; r.v = x[g];
+    XWhere wh;
+    CTD_HD const double* buf(int64_t g) const { return (wh.nr && wh.edge) ? xnear(*wh.nr, x, g) : x; }
+    CTD_HD Dual<K> at(const double* xb, int64_t g, int dir) const {
+        Dual<K> r; r.v = xb[g];
 #pragma unroll
         for (int d = 0; d < K; ++d) r.d[d] = (dir >= 0 && dir - g0 == d) ? 1.0 : 0.0;
         return r;
     }
+    CTD_HD Dual<K> at(int64_t g, int dir) const { return at(x, g, dir); }
 };
 
 CTD_HD double prod_tau(const ProdParams& pp, int64_t i) { return pp.tau ? pp.tau[i] : (double)i / (double)pp.L.N; }
@@ -93,6 +131,7 @@ __device__ __forceinline__ void prod_step_rows(const ProdParams& pp, const Src& 
     constexpr int n = P::NX, m = P::NU, nv = P::NV;
     const Layout& L = pp.L;
     const int64_t b0 = i * (int64_t)L.blk, b1 = (i + 1) * (int64_t)L.blk;
+    const double *x0 = src.buf(b0), *x1 = src.buf(b1);
     T V[nv > 0 ? nv : 1];
 #pragma unroll
     for (int k = 0; k < nv; ++k) V[k] = src.at(L.v_off + k, prod_dir(ro.v, k));
@@ -102,18 +141,18 @@ __device__ __forceinline__ void prod_step_rows(const ProdParams& pp, const Src& 
         const T hh = 0.5 * (tip1 - ti);
         T g[n > 0 ? n : 1];
 #pragma unroll
-        for (int c = 0; c < n; ++c) xa[c] = src.at(b0 + c, prod_dir(ro.xi, c));
+        for (int c = 0; c < n; ++c) xa[c] = src.at(x0, b0 + c, prod_dir(ro.xi, c));
 #pragma unroll
-        for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + c, prod_dir(ro.bi, c));
+        for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + c, prod_dir(ro.bi, c));
         P::template dynamics<T>(f, ti, xa, u, V);
 #pragma unroll
-        for (int c = 0; c < n; ++c) xa[c] = src.at(b1 + c, prod_dir(ro.xn, c));
+        for (int c = 0; c < n; ++c) xa[c] = src.at(x1, b1 + c, prod_dir(ro.xn, c));
 #pragma unroll
-        for (int c = 0; c < m; ++c) u[c] = src.at(b1 + n + c, prod_dir(ro.un, c));
+        for (int c = 0; c < m; ++c) u[c] = src.at(x1, b1 + n + c, prod_dir(ro.un, c));
         P::template dynamics<T>(g, tip1, xa, u, V);
 #pragma unroll
         for (int c = 0; c < n; ++c) {
-            const T xi = src.at(b0 + c, prod_dir(ro.xi, c));
+            const T xi = src.at(x0, b0 + c, prod_dir(ro.xi, c));
             sink(c, xa[c] - (xi + hh * (f[c] + g[c])));
         }
     } else if constexpr (SC == SC_MIDPOINT) {
@@ -121,31 +160,31 @@ __device__ __forceinline__ void prod_step_rows(const ProdParams& pp, const Src& 
             // x_next = x_i + h_i f(t_s, x_s, U_i^j), j = 1..cs, h_i = h / cs, the same (t_s, x_s) for every control
             const T hi = (tip1 - ti) / (double)L.cs, ts = 0.5 * (ti + tip1);
 #pragma unroll
-            for (int c = 0; c < n; ++c) xa[c] = 0.5 * (src.at(b0 + c, prod_dir(ro.xi, c)) + src.at(b1 + c, prod_dir(ro.xn, c)));
+            for (int c = 0; c < n; ++c) xa[c] = 0.5 * (src.at(x0, b0 + c, prod_dir(ro.xi, c)) + src.at(x1, b1 + c, prod_dir(ro.xn, c)));
             T xn[n > 0 ? n : 1];
 #pragma unroll
-            for (int c = 0; c < n; ++c) xn[c] = src.at(b0 + c, prod_dir(ro.xi, c));
+            for (int c = 0; c < n; ++c) xn[c] = src.at(x0, b0 + c, prod_dir(ro.xi, c));
             for (int j = 0; j < L.cs; ++j) {
 #pragma unroll
-                for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + j * m + c, prod_dir(ro.bi, j * m + c));
+                for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + j * m + c, prod_dir(ro.bi, j * m + c));
                 P::template dynamics<T>(f, ts, xa, u, V);
 #pragma unroll
                 for (int c = 0; c < n; ++c) xn[c] = xn[c] + hi * f[c];
             }
 #pragma unroll
-            for (int c = 0; c < n; ++c) sink(c, src.at(b1 + c, prod_dir(ro.xn, c)) - xn[c]);
+            for (int c = 0; c < n; ++c) sink(c, src.at(x1, b1 + c, prod_dir(ro.xn, c)) - xn[c]);
         } else {
             // explicit: f(t_i, X_i, U_i); implicit: f(t_{i+1}, X_{i+1}, U_i)
             const T hi = tip1 - ti;
             const bool expl = L.euler == 1;
 #pragma unroll
-            for (int c = 0; c < n; ++c) xa[c] = expl ? src.at(b0 + c, prod_dir(ro.xi, c)) : src.at(b1 + c, prod_dir(ro.xn, c));
+            for (int c = 0; c < n; ++c) xa[c] = expl ? src.at(x0, b0 + c, prod_dir(ro.xi, c)) : src.at(x1, b1 + c, prod_dir(ro.xn, c));
 #pragma unroll
-            for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + c, prod_dir(ro.bi, c));
+            for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + c, prod_dir(ro.bi, c));
             P::template dynamics<T>(f, expl ? ti : tip1, xa, u, V);
 #pragma unroll
             for (int c = 0; c < n; ++c)
-                sink(c, src.at(b1 + c, prod_dir(ro.xn, c)) - (src.at(b0 + c, prod_dir(ro.xi, c)) + hi * f[c]));
+                sink(c, src.at(x1, b1 + c, prod_dir(ro.xn, c)) - (src.at(x0, b0 + c, prod_dir(ro.xi, c)) + hi * f[c]));
         }
     } else {
         // stage j: K_j - f(t_i + c_j h, X_i + h sum_l a_jl K_l, U_j); state row: X_{i+1} - (X_i + h sum_j b_j K_j)
@@ -156,24 +195,24 @@ __device__ __forceinline__ void prod_step_rows(const ProdParams& pp, const Src& 
             const T tij = ti + L.c[j] * hi;
 #pragma unroll
             for (int c = 0; c < n; ++c) {
-                T xc = src.at(b0 + c, prod_dir(ro.xi, c));
+                T xc = src.at(x0, b0 + c, prod_dir(ro.xi, c));
 #pragma unroll
-                for (int l = 0; l < S; ++l) xc = xc + hi * L.a[3 * j + l] * src.at(b0 + ko + l * n + c, prod_dir(ro.bi, L.cu + l * n + c));
+                for (int l = 0; l < S; ++l) xc = xc + hi * L.a[3 * j + l] * src.at(x0, b0 + ko + l * n + c, prod_dir(ro.bi, L.cu + l * n + c));
                 xa[c] = xc;
             }
             const int uo = L.stagewise ? j * m : 0;
 #pragma unroll
-            for (int c = 0; c < m; ++c) u[c] = src.at(b0 + n + uo + c, prod_dir(ro.bi, uo + c));
+            for (int c = 0; c < m; ++c) u[c] = src.at(x0, b0 + n + uo + c, prod_dir(ro.bi, uo + c));
             P::template dynamics<T>(f, tij, xa, u, V);
 #pragma unroll
-            for (int c = 0; c < n; ++c) sink(n + j * n + c, src.at(b0 + ko + j * n + c, prod_dir(ro.bi, L.cu + j * n + c)) - f[c]);
+            for (int c = 0; c < n; ++c) sink(n + j * n + c, src.at(x0, b0 + ko + j * n + c, prod_dir(ro.bi, L.cu + j * n + c)) - f[c]);
         }
 #pragma unroll
         for (int c = 0; c < n; ++c) {
-            T sb = L.b[0] * src.at(b0 + ko + c, prod_dir(ro.bi, L.cu + c));
+            T sb = L.b[0] * src.at(x0, b0 + ko + c, prod_dir(ro.bi, L.cu + c));
 #pragma unroll
-            for (int j = 1; j < S; ++j) sb = sb + L.b[j] * src.at(b0 + ko + j * n + c, prod_dir(ro.bi, L.cu + j * n + c));
-            sink(c, src.at(b1 + c, prod_dir(ro.xn, c)) - (src.at(b0 + c, prod_dir(ro.xi, c)) + hi * sb));
+            for (int j = 1; j < S; ++j) sb = sb + L.b[j] * src.at(x0, b0 + ko + j * n + c, prod_dir(ro.bi, L.cu + j * n + c));
+            sink(c, src.at(x1, b1 + c, prod_dir(ro.xn, c)) - (src.at(x0, b0 + c, prod_dir(ro.xi, c)) + hi * sb));
         }
     }
 }
@@ -188,20 +227,22 @@ __device__ __forceinline__ void prod_path_rows(const ProdParams& pp, const Src& 
         T V[nv > 0 ? nv : 1], x[n > 0 ? n : 1], u[m > 0 ? m : 1], r[p];
 #pragma unroll
         for (int j = 0; j < nv; ++j) V[j] = src.at(L.v_off + j, prod_dir(vd, j));
+        const double* xk = src.buf(k * (int64_t)L.blk);
 #pragma unroll
-        for (int c = 0; c < n; ++c) x[c] = src.at(k * (int64_t)L.blk + c, prod_dir(xd, c));
+        for (int c = 0; c < n; ++c) x[c] = src.at(xk, k * (int64_t)L.blk + c, prod_dir(xd, c));
         const int64_t ub = path_ctrl_node(L, k) * (int64_t)L.blk + n;
+        const double* xc = src.buf(ub);
         if (SC == SC_IRK && L.stagewise) {          // b-weighted stage average (irk_stagewise.jl:197-205)
 #pragma unroll
             for (int c = 0; c < m; ++c) {
-                T uc = L.b[0] * src.at(ub + c, prod_dir(ud, c));
+                T uc = L.b[0] * src.at(xc, ub + c, prod_dir(ud, c));
 #pragma unroll
-                for (int j = 1; j < S; ++j) uc = uc + L.b[j] * src.at(ub + j * m + c, prod_dir(ud, j * m + c));
+                for (int j = 1; j < S; ++j) uc = uc + L.b[j] * src.at(xc, ub + j * m + c, prod_dir(ud, j * m + c));
                 u[c] = uc;
             }
         } else {
 #pragma unroll
-            for (int c = 0; c < m; ++c) u[c] = src.at(ub + c, prod_dir(ud, c));
+            for (int c = 0; c < m; ++c) u[c] = src.at(xc, ub + c, prod_dir(ud, c));
         }
         const T t = prod_time<P, T>(pp, V, prod_tau(pp, k));
         P::template path<T>(r, t, x, u, V);
@@ -218,8 +259,9 @@ __device__ __forceinline__ void prod_boundary_rows(const ProdParams& pp, const S
         const Layout& L = pp.L;
         T x0[n > 0 ? n : 1], xf[n > 0 ? n : 1], V[nv > 0 ? nv : 1], r[nb];
         const int64_t gf = L.N * (int64_t)L.blk;
+        const double *xa = src.buf(0), *xb = src.buf(gf);
 #pragma unroll
-        for (int c = 0; c < n; ++c) { x0[c] = src.at(c, seeded ? c : -1); xf[c] = src.at(gf + c, seeded ? n + c : -1); }
+        for (int c = 0; c < n; ++c) { x0[c] = src.at(xa, c, seeded ? c : -1); xf[c] = src.at(xb, gf + c, seeded ? n + c : -1); }
 #pragma unroll
         for (int j = 0; j < nv; ++j) V[j] = src.at(L.v_off + j, seeded ? 2 * n + j : -1);
         P::template boundary<T>(r, x0, xf, V);
@@ -258,10 +300,10 @@ template <int JC, int NV> __device__ __forceinline__ void prod_write_out(const d
 }
 
 // ---- jprod ----------------------------------------------------------------------------------------------------------------
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __device__ __forceinline__ void jprod_unit_body(const ProdParams& pp, const double* __restrict__ xu, int64_t k) {
     const Layout& L = pp.L;
-    const FwdSrc src{xu, pp.dir};
+    const FwdSrc src{xu, pp.dir, prod_where<SH>(pp, k)};
     double* out = pp.out;
     if (k < L.N) {
         const int64_t r0 = k * (int64_t)L.cb;
@@ -278,10 +320,12 @@ __device__ __forceinline__ void jprod_unit_body(const ProdParams& pp, const doub
     }
 }
 
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __global__ void __launch_bounds__(256) jprod_kernel(const ProdParams pp, const double* __restrict__ xu) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k <= pp.L.N) jprod_unit_body<P, SC, S>(pp, xu, k);
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (SH) {
+        if (pp.unit_begin + id < pp.unit_end) jprod_unit_body<P, SC, S, true>(pp, xu, pp.unit_begin + id);
+    } else if (id <= pp.L.N) jprod_unit_body<P, SC, S>(pp, xu, id);
 }
 
 // ---- jtprod ---------------------------------------------------------------------------------------------------------------
@@ -388,7 +432,9 @@ CTD_HD int prod_dirs_per_node(const Layout& L) { return L.sc == SC_IRK ? L.n + L
 
 // lane (node k, chunk q): the JC entries of w'J in directions [q JC, (q + 1) JC) of node k's variables -- its block
 // (X_k, then controls / stage variables: bk entries) and v [bk, bk + nv).  Block entries go to Jtw, v entries to gv.
-template <class P, int SC, int S>
+// On a shard (SH): the Gauss-Legendre lanes read their own step's block, v and, on the last shard, node N only -- nothing of
+// another shard, so they never look at the table; the other schemes' first and last lanes do (step k-1's block, node k+1).
+template <class P, int SC, int S, bool SH = false>
 __device__ __forceinline__ void jtprod_unit_body(const ProdParams& pp, const double* __restrict__ xu, int64_t k, int q, double* gv) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV, JC = ProdDirs<P>::JC;
     const Layout& L = pp.L;
@@ -398,7 +444,7 @@ __device__ __forceinline__ void jtprod_unit_body(const ProdParams& pp, const dou
     const int bk = (k < L.N || SC == SC_TRAPEZE) ? L.blk : n;         // the last node of the other schemes owns X_{N+1} only
     const int g0 = q * JC;
     if (g0 >= bk + nv) return;
-    const SeedSrc<JC> src{xu, g0};
+    const SeedSrc<JC> src{xu, g0, prod_where<SH && SC != SC_IRK>(pp, k)};
     const double* w = pp.dir;
     double acc[JC];
 #pragma unroll
@@ -440,28 +486,35 @@ __device__ __forceinline__ void jtprod_unit_body(const ProdParams& pp, const dou
 // the unit pass of a transposed product for workgroup `block` (wsum: 4 * kMaxNV doubles of LDS): thread id = (node k, chunk q),
 // lane(k, q, gv) writes the entries of its own block and leaves its d/dv entries in gv; their sum over the workgroup becomes row
 // `block` of pp.partial (block_partial_sums, ctd_common.hpp)
-template <int NV, class Lane>
+// SH: node k counts from the shard's first node and stops at its last
+template <int NV, bool SH = false, class Lane>
 __device__ __forceinline__ void prod_units_body(const ProdParams& pp, int block, double (*wsum)[kMaxNV], Lane&& lane) {
     double gv[NV > 0 ? NV : 1];
 #pragma unroll
     for (int j = 0; j < NV; ++j) gv[j] = 0.0;
     const int64_t id = (int64_t)block * blockDim.x + threadIdx.x;
     const int64_t k = id / pp.nch;
-    if (k <= pp.L.N) lane(k, (int)(id - k * pp.nch), gv);
+    if constexpr (SH) {
+        if (pp.unit_begin + k < pp.unit_end) lane(pp.unit_begin + k, (int)(id - k * pp.nch), gv);
+    } else if (k <= pp.L.N) lane(k, (int)(id - k * pp.nch), gv);
     if constexpr (NV > 0) block_partial_sums<NV, kMaxNV>(gv, &wsum[0][0], pp.partial + (int64_t)block * kMaxNV);
 }
 
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __global__ void __launch_bounds__(256) jtprod_units_kernel(const ProdParams pp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    prod_units_body<P::NV>(pp, (int)blockIdx.x, wsum, [&](int64_t k, int q, double* gv) { jtprod_unit_body<P, SC, S>(pp, xu, k, q, gv); });
+    prod_units_body<P::NV, SH>(pp, (int)blockIdx.x, wsum,
+                               [&](int64_t k, int q, double* gv) { jtprod_unit_body<P, SC, S, SH>(pp, xu, k, q, gv); });
 }
 
 // the finish of a transposed product, one wave: the boundary rows (and, SECOND order: the Mayer term, weight sigma) -- lane l
 // differentiates chunks l, l + 64, ... of (X_1, X_{N+1}, v), JC directions each, on the numbers make_src(g0) seeds, and adds to the
 // entries it owns -- then the v partials in block order (ordered_rows_sum, ctd_common.hpp).  First order (jtprod): pp.dir is never
 // null and the objective has no part in it; second order (hprod): the rows only with multipliers.
-template <class P, int JC, bool SECOND, class MakeSrc>
+// On a shard (SH): the chunks are evaluated by the shards that own X_1 or X_{N+1} only (X_1, X_{N+1} read through the table when
+// the iterate is in place), a direction's entry is added where the shard owns it -- X_1 on the first shard, X_{N+1} and v on the
+// last -- and pp.partial holds the shard's own blocks: the nv entries of pp.out are the shard's partial sums.
+template <class P, int JC, bool SECOND, bool SH = false, class MakeSrc>
 __device__ __forceinline__ void prod_finish_body(const ProdParams& pp, double* bv, MakeSrc&& make_src, double sigma = 0.0) {
     constexpr int n = P::NX, nv = P::NV, nb = P::NBC;
     constexpr bool MAYER = SECOND && P::HAS_MAYER;
@@ -470,7 +523,8 @@ __device__ __forceinline__ void prod_finish_body(const ProdParams& pp, double* b
     if (lane < kMaxNV) bv[lane] = 0.0;
     __syncthreads();
     const bool rows = nb > 0 && (!SECOND || pp.dir != nullptr);
-    if (rows || MAYER) {
+    const bool first = !SH || pp.owns_first, last = !SH || pp.owns_last;
+    if ((rows || MAYER) && (first || last)) {
         const int64_t gf = L.N * (int64_t)L.blk;
         for (int g0 = lane * JC; g0 < 2 * n + nv; g0 += 64 * JC) {
             const auto src = make_src(g0);
@@ -484,8 +538,9 @@ __device__ __forceinline__ void prod_finish_body(const ProdParams& pp, double* b
             }
             if constexpr (MAYER) {        // src/DOCP_functions.jl:35-48; directions as the boundary rows'
                 T x0[n > 0 ? n : 1], xf[n > 0 ? n : 1], V[nv > 0 ? nv : 1];
+                const double *xa = src.buf(0), *xb = src.buf(gf);
 #pragma unroll
-                for (int c = 0; c < n; ++c) { x0[c] = src.at(c, c); xf[c] = src.at(gf + c, n + c); }
+                for (int c = 0; c < n; ++c) { x0[c] = src.at(xa, c, c); xf[c] = src.at(xb, gf + c, n + c); }
 #pragma unroll
                 for (int j = 0; j < nv; ++j) V[j] = src.at(L.v_off + j, 2 * n + j);
                 const T r = P::template mayer<T>(x0, xf, V);
@@ -495,9 +550,9 @@ __device__ __forceinline__ void prod_finish_body(const ProdParams& pp, double* b
 #pragma unroll
             for (int d = 0; d < JC; ++d) {
                 const int g = g0 + d;
-                if (g < n) pp.out[g] += acc[d];
-                else if (g < 2 * n) pp.out[gf + g - n] += acc[d];
-                else if (g < 2 * n + nv) bv[g - 2 * n] = acc[d];
+                if (g < n) { if (first) pp.out[g] += acc[d]; }
+                else if (g < 2 * n) { if (last) pp.out[gf + g - n] += acc[d]; }
+                else if (g < 2 * n + nv) { if (last) bv[g - 2 * n] = acc[d]; }
             }
         }
     }
@@ -510,19 +565,25 @@ __device__ __forceinline__ void prod_finish_body(const ProdParams& pp, double* b
     }
 }
 
-template <class P>
+// the finish's sources: every lane may look at the table (X_1 and X_{N+1} are the only blocks it reads)
+template <bool SH> CTD_HD XWhere finish_where(const ProdParams& pp) {
+    if constexpr (SH) return XWhere{&pp.near, pp.halo != nullptr};
+    else return XWhere{};
+}
+template <class P, bool SH = false>
 __global__ void __launch_bounds__(64) jtprod_finish_kernel(const ProdParams pp, const double* __restrict__ xu) {
     __shared__ double bv[kMaxNV];
     constexpr int JC = ProdDirs<P>::JC;
-    prod_finish_body<P, JC, false>(pp, bv, [&](int g0) { return SeedSrc<JC>{xu, g0}; });
+    prod_finish_body<P, JC, false, SH>(pp, bv, [&](int g0) { return SeedSrc<JC>{xu, g0, finish_where<SH>(pp)}; });
 }
 
 #if !defined(__HIPCC_RTC__)
 // ---- launchers (instantiated per registry problem in ctd_pkern_*.hip) ---------------------------------------------------
-template <class P>
+// SH: the shard form of the kernels (ctd_*prod_shard_dev_async); the grid covers the nodes [unit_begin, unit_end)
+template <class P, bool SH = false>
 hipError_t launch_jprod(const ProdParams& pp, const double* xu, hipStream_t st) {
-    const unsigned grid = (unsigned)((pp.L.N + 1 + 255) / 256);
-    for_scheme<false>(pp.L, [&](auto t) { jprod_kernel<P, t.sc, t.s><<<grid, 256, 0, st>>>(pp, xu); });
+    const unsigned grid = (unsigned)(((SH ? pp.unit_end - pp.unit_begin : pp.L.N + 1) + 255) / 256);
+    for_scheme<false>(pp.L, [&](auto t) { jprod_kernel<P, t.sc, t.s, SH><<<grid, 256, 0, st>>>(pp, xu); });
     return hipGetLastError();
 }
 // A transposed product: K names its argument struct (Params; prod(a): the ProdParams inside) and its two kernels.  The units
@@ -532,23 +593,24 @@ struct JtprodKernels {
     using Params = ProdParams;
     static ProdParams& prod(Params& a) { return a; }
     static const ProdParams& prod(const Params& a) { return a; }
-    template <class P, int SC, int S> static constexpr auto units = &jtprod_units_kernel<P, SC, S>;
-    template <class P> static constexpr auto finish = &jtprod_finish_kernel<P>;
+    template <class P, int SC, int S, bool SH> static constexpr auto units = &jtprod_units_kernel<P, SC, S, SH>;
+    template <class P, bool SH> static constexpr auto finish = &jtprod_finish_kernel<P, SH>;
 };
-template <class P, class K>
+template <class P, class K, bool SH = false>
 hipError_t launch_prod_units(const typename K::Params& a, const double* xu, hipStream_t st) {
     const ProdParams& pp = K::prod(a);
-    for_scheme<false>(pp.L, [&](auto t) { K::template units<P, t.sc, t.s><<<(unsigned)pp.nblocks, 256, 0, st>>>(a, xu); });
-    K::template finish<P><<<1, 64, 0, st>>>(a, xu);
+    for_scheme<false>(pp.L, [&](auto t) { K::template units<P, t.sc, t.s, SH><<<(unsigned)pp.nblocks, 256, 0, st>>>(a, xu); });
+    K::template finish<P, SH><<<1, 64, 0, st>>>(a, xu);
     return hipGetLastError();
 }
 
-#define CTD_INSTANTIATE_PROD(P)                                                     \
-    template hipError_t launch_jprod<P>(const ProdParams&, const double*, hipStream_t);  \
-    template hipError_t launch_prod_units<P, JtprodKernels>(const ProdParams&, const double*, hipStream_t);
-#define CTD_EXTERN_PROD(P)                                                                 \
-    extern template hipError_t launch_jprod<P>(const ProdParams&, const double*, hipStream_t);  \
-    extern template hipError_t launch_prod_units<P, JtprodKernels>(const ProdParams&, const double*, hipStream_t);
+#define CTD_PROD_LAUNCHERS(X, P)                                                                          \
+    X template hipError_t launch_jprod<P, false>(const ProdParams&, const double*, hipStream_t);          \
+    X template hipError_t launch_jprod<P, true>(const ProdParams&, const double*, hipStream_t);           \
+    X template hipError_t launch_prod_units<P, JtprodKernels, false>(const ProdParams&, const double*, hipStream_t);  \
+    X template hipError_t launch_prod_units<P, JtprodKernels, true>(const ProdParams&, const double*, hipStream_t);
+#define CTD_INSTANTIATE_PROD(P) CTD_PROD_LAUNCHERS(, P)
+#define CTD_EXTERN_PROD(P) CTD_PROD_LAUNCHERS(extern, P)
 #endif  // !__HIPCC_RTC__
 
 }  // namespace ctd

@@ -19,6 +19,10 @@ its own rows c[(i-1)(eqs+p)+1 : i(eqs+p)] and the Jacobian entries of those rows
   * outputs stay ROW-SHARDED: rank r holds its rows of c and, for the Jacobian values, one contiguous range of the global
     CSC value array (its step columns) plus its slice of every V column -- what a distributed KKT consumer wants;
     `DOCP.shard` gives the ranges.  The evaluation itself needs no collective;
+  * the matrix-free products (`ShardedDOCP.jprod` / `jtprod` / `hprod`) keep their directions and results sharded the same
+    way: a rank fetches the few halo entries of a direction with one small all-gather (`exchange_product_halo` for a
+    variable-layout vector, `exchange_product_rows` for a constraint-layout one) and a transposed product adds the nv
+    entries of d/dv with one all-reduce;
   * a consumer that wants the residual vector whole on every rank asks for it (`stitch=True`): ONE all-gather of the row
     blocks per evaluation (in place when the blocks are equal, through a padded buffer + one index kernel when ragged).
 
@@ -168,6 +172,7 @@ class ShardedDOCP:
         self._stitch = None
         self._halo = None
         self._yhalo = None
+        self._phalo = {}                    # (layout, device) -> index sets and buffers of exchange_product_halo / _rows
         self._vv = None
         self._f = None
         self._peer = None                   # data_ptr of the x buffer the peer table is ACTIVE for (enable_peer_x), None: off
@@ -271,6 +276,71 @@ class ShardedDOCP:
         if dst.numel():
             y.index_copy_(0, dst, recv.index_select(0, src))
         return y
+
+    def _exchange(self, t, key, build):
+        """One all-gather of a few entries per rank: every rank packs `pack` of its own entries of the full-length t, and copies
+        the entries `src` of the gathered buffer to the positions `dst` of t.  build() -> (pack, dst, src) as index lists, made
+        once per (key, device) and kept with the send / receive buffers."""
+        if self.world == 1 and not _FORCE:
+            return t
+        ent = self._phalo.get((key, t.device))
+        if ent is None:
+            pack, dst, src = build()
+            cat = lambda parts: (torch.cat(parts) if parts else torch.zeros(0, dtype=torch.long)).to(t.device)      # noqa: E731
+            n = sum(int(q.numel()) for q in pack)
+            ent = self._phalo[(key, t.device)] = (cat(pack), cat(dst), cat(src), torch.zeros(n, dtype=torch.float64, device=t.device),
+                                                  torch.zeros(self.world * n, dtype=torch.float64, device=t.device))
+        pack, dst, src, send, recv = ent
+        torch.index_select(t, 0, pack, out=send)
+        _all_gather_into(recv, send, self.group)
+        if dst.numel():
+            t.index_copy_(0, dst, recv.index_select(0, src))
+        return t
+
+    def exchange_product_halo(self, t):
+        """Matrix-free products on a shard: fills, inside this rank's full-length VARIABLE-layout tensor t (a direction v, or the
+        iterate x when it is not read in place), the entries other ranks own that `jprod` / `jtprod` / `hprod` read (the read set of
+        ctd_*prod_shard_dev_async, include/ctdirect_hip.h): the previous rank's whole last block, the next rank's first node (X, + U
+        for trapeze), X_1 and X_{N+1} -- with ONE all-gather of (halo_w + blk + n) doubles per rank.  The nv tail is replicated and
+        not touched."""
+        def build():
+            w, n, blk, N = self.halo_w, self.n, self.blk, self.N
+            L = w + blk + n
+            (b, e), r, G, ar = self.steps, self.rank, self.world, torch.arange
+            pack = [b * blk + ar(w), (e - 1) * blk + ar(blk), N * blk + ar(n)]        # my first node | last block | final state
+            dst, src = [], []
+            if r > 0:
+                # (rank 1 of one-step-first shards: block b - 1 is block 0 and holds X_1 too -- index_copy_ then gets those n
+                # positions twice, with the same values from the same rank)
+                dst += [ar(n), (b - 1) * blk + ar(blk)]
+                src += [ar(n), (r - 1) * L + w + ar(blk)]
+            if r + 1 < G:
+                dst += [e * blk + ar(w), N * blk + ar(n)]
+                src += [(r + 1) * L + ar(w), (G - 1) * L + w + blk + ar(n)]
+            return pack, dst, src
+        return self._exchange(t, "var", build)
+
+    def exchange_product_rows(self, w):
+        """The same for a CONSTRAINT-layout tensor (w of `jtprod`, y of `hprod`): the state / stage rows of the previous rank's last
+        step, the path rows of the next rank's first node and the tail rows (final path + boundary rows, owned by the last rank) --
+        ONE all-gather of (cb + tail) doubles per rank."""
+        def build():
+            cb, N = self.cb, self.N
+            eqs = self.docp.discretization._state_stage_eqs_block
+            p = cb - eqs
+            tail = self.docp.dim_NLP_constraints - N * cb
+            Ly = p + eqs + tail
+            (b, e), r, G, ar = self.steps, self.rank, self.world, torch.arange
+            pack = [b * cb + eqs + ar(p), (e - 1) * cb + ar(eqs), N * cb + ar(tail)]  # my first node's path rows | last step | tail
+            dst, src = [], []
+            if r > 0:
+                dst.append((b - 1) * cb + ar(eqs))
+                src.append((r - 1) * Ly + p + ar(eqs))
+            if r + 1 < G:
+                dst += [e * cb + eqs + ar(p), N * cb + ar(tail)]
+                src += [(r + 1) * Ly + ar(p), (G - 1) * Ly + p + eqs + ar(tail)]
+            return pack, dst, src
+        return self._exchange(w, "con", build)
 
     def enable_peer_x(self, x):
         """Sharded iterate read IN PLACE (`ctd_set_x_shards`): every rank exports its full-length x buffer once (IPC handle,
@@ -435,6 +505,55 @@ class ShardedDOCP:
             tail = g[g.numel() - nv:]
             dist.all_reduce(tail, op=dist.ReduceOp.SUM, group=self.group)
         return g
+
+    def _product_x(self, x, what, x_halo_valid):
+        """the iterate of a product: read in place when the peer table is active for it; otherwise its halo entries are copied
+        INTO the caller's x (one all-gather), unless the caller says they are already there"""
+        self._rebind()
+        self._check_peer(x, what)
+        if self._peer is None and not x_halo_valid:
+            self.exchange_product_halo(x)
+
+    def _reduce_tail(self, out):
+        nv = self.docp.dims.NLP_v
+        if nv and (self.world > 1 or _FORCE):
+            dist.all_reduce(out[out.numel() - nv:], op=dist.ReduceOp.SUM, group=self.group)
+        return out
+
+    def jprod(self, x, v, out, stitch=False, x_halo_valid=False):
+        """jprod!(nlp, x, v, Jv) of the sharded transcription: this rank's rows of J(x) v (its step rows; the last rank also the tail
+        rows) into the full-length `out`, other rows untouched.  x, v: full-length tensors of which this rank holds its own entries
+        and the nv tail; the halo of v (and of x, unless x is read in place: `enable_peer_x`) is exchanged here -- one small
+        all-gather each -- and written INTO v and x: both are modified outside the rank's own entries.  x does not change between
+        the products of one outer iteration: after the first product (or one `exchange_product_halo(x)`) pass
+        `x_halo_valid=True` to skip its all-gather.  `stitch`: all-gather the row blocks so that every rank holds the whole Jv."""
+        self._product_x(x, "jprod", x_halo_valid)
+        self.exchange_product_halo(v)
+        self.docp.jprod_shard(x, v, out)
+        if stitch:
+            self._stitcher(out)(out)
+        return out
+
+    def jtprod(self, x, w, out, x_halo_valid=False):
+        """jtprod!(nlp, x, w, Jtw) of the sharded transcription: the entries of J(x)' w of this rank's own variables into the
+        full-length `out`, plus the d/dv entries all-reduced (nv doubles) on every rank.  w: full-length, this rank's own rows
+        valid; its halo rows are exchanged here (one small all-gather, written into w), and x's as in `jprod`
+        (`x_halo_valid`)."""
+        self._product_x(x, "jtprod", x_halo_valid)
+        self.exchange_product_rows(w)
+        self.docp.jtprod_shard(x, w, out)
+        return self._reduce_tail(out)
+
+    def hprod(self, x, y, v, obj_weight, out, x_halo_valid=False):
+        """hprod!(nlp, x, y, v, Hv; obj_weight) of the sharded transcription (y = None: objective only): the entries of Hv of this
+        rank's own variables into the full-length `out`, plus the d/dv entries all-reduced on every rank.  Exchanges the halos of v
+        and y (two small all-gathers, written into v and y), and of x as in `jprod` (`x_halo_valid`)."""
+        self._product_x(x, "hprod", x_halo_valid)
+        self.exchange_product_halo(v)
+        if y is not None:
+            self.exchange_product_rows(y)
+        self.docp.hprod_shard(x, y, v, obj_weight, out)
+        return self._reduce_tail(out)
 
     def obj(self, x, as_tensor=False):
         """Objective of the whole transcription: the shards' partial sums added with one all-reduce of one double that never

@@ -523,6 +523,46 @@ class DOCP:
             self.sync()
         return g
 
+    def _prod_shard(self, x, d, out, sync, transpose):
+        nin, nout = ((self.dim_NLP_constraints, self.dim_NLP_variables) if transpose
+                     else (self.dim_NLP_variables, self.dim_NLP_constraints))
+        L = _lib.lib()
+        self._check_x(x)
+        fn = L.ctd_jtprod_shard_dev_async if transpose else L.ctd_jprod_shard_dev_async
+        self._ck(fn(self._h, self._dev_ptr(x, self.dim_NLP_variables, "x"), self._dev_ptr(d, nin, "w" if transpose else "v"),
+                    self._dev_ptr(out, nout, "out")))
+        if sync:
+            self.sync()
+        return out
+
+    def jprod_shard(self, x, v, out, sync=False):
+        """`ctd_jprod_shard_dev_async`: THIS shard's rows of J(x) v -- the rows of its own steps; the last shard also the final path
+        and boundary rows -- into the full-length device tensor `out`; nothing else of `out` is touched.  x is read through the
+        table of `set_x_shards` when one is set, otherwise from x itself (halos copied in); v is always read from the tensor
+        passed.  include/ctdirect_hip.h lists the entries read."""
+        return self._prod_shard(x, v, out, sync, False)
+
+    def jtprod_shard(self, x, w, out, sync=False):
+        """`ctd_jtprod_shard_dev_async`: the entries of J(x)' w of THIS shard's own variables into the full-length device tensor
+        `out`, + the shard's partial sums of d/dv in the nv tail entries (the caller adds them over the shards); see `jprod_shard`."""
+        return self._prod_shard(x, w, out, sync, True)
+
+    def hprod_shard(self, x, y, v, obj_weight=1.0, out=None, sync=False):
+        """`ctd_hprod_shard_dev_async`: the entries of (obj_weight d2 f + sum_i y_i d2 c_i)(x) v of THIS shard's own variables into
+        the full-length device tensor `out` (allocated, uninitialised elsewhere, when None), + the shard's partial sums of d/dv in
+        the nv tail entries.  y = None: objective only.  See `jprod_shard`."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        self._check_x(x)
+        if out is None:
+            import torch
+            out = torch.empty(nvar, dtype=torch.float64, device=x.device)
+        py = None if y is None else self._dev_ptr(y, ncon, "y")
+        self._ck(_lib.lib().ctd_hprod_shard_dev_async(self._h, self._dev_ptr(x, nvar, "x"), py, float(obj_weight),
+                                                      self._dev_ptr(v, nvar, "v"), self._dev_ptr(out, nvar, "out")))
+        if sync:
+            self.sync()
+        return out
+
     def eval_all(self, x, y=None, obj_weight=1.0, f=None, g=None, c=None, vals=None, hvals=None, sync=False):
         """One solver iteration in one call (`ctd_eval_all_dev_async`): objective -> f[0], gradient -> g, constraints -> c,
         Jacobian values -> vals, Hessian values of the Lagrangian -> hvals, for device tensors; outputs left None are skipped.

@@ -379,8 +379,8 @@ int32_t ctd_hess_coord_batch_dev_async(ctd_handle* h, int32_t batch, const doubl
  * per workgroup; the host calls stage x, the direction and the result).
  * Run-time OCPs (ctd_register_ocp) compile their product kernels on the first call: make one call before capturing a graph.
  * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle (step_begin / step_end not
- * the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (sharded products are not supported); null pointers or an output
- * that equals an input -> CTD_EINVAL. */
+ * the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (a shard handle calls ctd_jprod_shard_dev_async /
+ * ctd_jtprod_shard_dev_async below); null pointers or an output that equals an input -> CTD_EINVAL. */
 /* host pointers: return when the result is in the caller's buffer */
 int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv);
 int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw);
@@ -402,12 +402,44 @@ int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w
  * of kMaxNV partial sums per workgroup; the host call stages x, y, v and the result).
  * Run-time OCPs (ctd_register_ocp) compile their hprod kernels on the first hprod call: make one call before capturing a graph.
  * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle (step_begin / step_end not
- * the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL; null x, v or Hv, or Hv equal to x, y or v -> CTD_EINVAL. */
+ * the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (a shard handle calls ctd_hprod_shard_dev_async below); null x, v
+ * or Hv, or Hv equal to x, y or v -> CTD_EINVAL. */
 /* host pointers: return when the result is in the caller's buffer */
 int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* v, double* Hv);
 /* device pointers on the handle's device: enqueue-only on the handle's stream (ctd_sync waits), capturable after one warm call */
 int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
                             double* Hv_dev);
+
+/* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
+ * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
+ * ctd_sharded_handle included), modelled on ctd_grad_shard_dev_async: enqueue-only on the handle's stream, capturable after one
+ * warm call, reproducible bit for bit; run-time OCPs compile the shard form of their product kernels at the first shard call (a
+ * family of its own: the whole-grid calls compile nothing more than before).  Every buffer is full-length with global indexing
+ * (nvar or ncon entries).  "First" shard: sb == 0; "last" shard: se == N.  blk: variables per step block, cb: rows per step,
+ * eqs: state + stage rows per step, p: path rows per node, v_off = nvar - nv.
+ * WRITES -- nothing else of the output is touched:
+ *   jprod   the rows [sb cb, se cb); the last shard also the tail rows [N cb, ncon) (final path rows and boundary rows): the row
+ *           ownership of ctd_stitch_c;
+ *   jtprod, hprod   the variable entries [sb blk, se blk), the last shard up to v_off (node N included), and the nv entries
+ *           [v_off, nvar) with the shard's PARTIAL sums of d/dv: the caller adds them over the shards (one all-reduce of nv
+ *           doubles).  The boundary rows' and the Mayer term's contributions go to X_1 on the first shard, to X_{N+1} and to v on
+ *           the last one (the convention of ctd_grad_shard_dev_async).
+ * On a whole-grid handle each call is bit-identical to its *_dev_async counterpart.
+ * READS of x: through the table of ctd_set_x_shards when one is set (the call contains no exchange); otherwise from x_dev, whose
+ * halo entries must have been copied in.  The directions v, w and y are ALWAYS read from the pointer passed: their halo entries
+ * are the caller's to fill (as for y of the sharded ctd_hess_coord).  Upper bounds of what a call reads -- nothing outside them is
+ * read, so those entries need not be valid:
+ *   variable layout (x without a table, v):  the shard's own entries (as in the write set above); [v_off, nvar); the whole block
+ *     sb - 1 if sb > 0; if se < N the first n entries of block se, plus the m controls behind them on the trapeze; [0, n) and
+ *     [N blk, N blk + n);
+ *   constraint layout (w, y):  the shard's own rows (the tail included on the last shard); the eqs state / stage rows of step
+ *     sb - 1 if sb > 0; the p path rows of node se, [se cb + eqs, (se + 1) cb), if se < N; the tail [N cb, ncon).
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; null pointers (y_dev may be NULL: objective
+ * only) -> CTD_EINVAL; an output that equals an input -> CTD_EINVAL. */
+int32_t ctd_jprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev);
+int32_t ctd_jtprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev);
+int32_t ctd_hprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                                  double* Hv_dev);
 
 /* 1-based (rows[k], cols[k]), k < nnzh, CSC order */
 int32_t ctd_hess_structure(const ctd_handle* h, int64_t* rows, int64_t* cols);
