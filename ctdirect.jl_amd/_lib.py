@@ -105,6 +105,8 @@ SYMBOLS = {
     "ctd_jtprod_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp, _dp]),
     "ctd_hprod_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "ctd_kktprod": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ctd_kktprod_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctd_jprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

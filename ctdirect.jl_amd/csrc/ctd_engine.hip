@@ -25,6 +25,7 @@
 #include "ctd_iter_kernels.hpp"
 #include "ctd_prod_kernels.hpp"
 #include "ctd_hprod_kernels.hpp"
+#include "ctd_kkt_kernels.hpp"
 #include "ctd_jit.hpp"
 
 using namespace ctd;
@@ -32,7 +33,7 @@ using namespace ctd;
 namespace ctd {
 // the instantiations live in the per-problem translation units
 #define CTD_EXTERN_ALL(ID, P) \
-    CTD_EXTERN_LAUNCHERS(P) CTD_EXTERN_HESS(P) CTD_EXTERN_HESS_STEP(P) CTD_EXTERN_ITER(P) CTD_EXTERN_PROD(P) CTD_EXTERN_HPROD(P)
+    CTD_EXTERN_LAUNCHERS(P) CTD_EXTERN_HESS(P) CTD_EXTERN_HESS_STEP(P) CTD_EXTERN_ITER(P) CTD_EXTERN_PROD(P) CTD_EXTERN_HPROD(P) CTD_EXTERN_KKT(P)
 CTD_REGISTRY(CTD_EXTERN_ALL)
 }  // namespace ctd
 
@@ -58,7 +59,7 @@ template <class T = double> struct DevBuf {
 };
 
 // the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each, loaded at first use (jit_load)
-enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, kJitFamilies };
+enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, JIT_KKT, kJitFamilies };
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t f[5] = {};        // in the order of the family's name expressions (kJit)
@@ -125,6 +126,9 @@ struct ctd_handle {
     // matrix-free Hessian products (ctd_hprod*): their own partial sums (a graph captured over jtprod keeps its buffer), host-call
     // staging of v and Hv in d_pdir / d_pout and of y in d_y
     DevBuf<> d_hppartial;
+    // matrix-free KKT products (ctd_kktprod*): their own partial sums again; the host call stages x, y, dx and rx as ctd_hprod does
+    // and dy, sx, sc and rc here (nvar / ncon entries)
+    DevBuf<> d_kktpartial, d_kdy, d_ksx, d_ksc, d_krc;
     std::string err;
 };
 
@@ -325,6 +329,10 @@ std::vector<std::string> hprod_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
     return {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::hprod_finish_kernel<ctd::UserOCP" + sh + ">"};
 }
+std::vector<std::string> jit_kkt_exprs(int sc, int s) {
+    const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
+    return {"ctd::kktprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">", "ctd::kktprod_finish_kernel<ctd::UserOCP>"};
+}
 std::vector<std::string> jit_prod_exprs(int sc, int s) { return prod_exprs(sc, s, ""); }
 std::vector<std::string> jit_hprod_exprs(int sc, int s) { return hprod_exprs(sc, s, ""); }
 std::vector<std::string> jit_prod_shard_exprs(int sc, int s) { return prod_exprs(sc, s, ", true"); }
@@ -339,6 +347,7 @@ const struct { const char* header; const char* fp_contract; std::vector<std::str
     {"ctd_hess_kernels.hpp", "fast", jit_hess_exprs},       // hess, hess_finish
     {"ctd_prod_kernels.hpp", "off", jit_prod_shard_exprs},  // the shard forms of jprod, jtprod_units, jtprod_finish
     {"ctd_hprod_kernels.hpp", "off", jit_hprod_shard_exprs},    // ... and of hprod_units, hprod_finish
+    {"ctd_kkt_kernels.hpp", "off", jit_kkt_exprs},          // kktprod_units, kktprod_finish (whole grid only)
 };
 
 // batch: the grid's second dimension (members of a batched launch)
@@ -411,7 +420,9 @@ static int32_t enqueue_prod_units(ctd_handle* h, const char* fn, typename K::Par
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = shard ? launch_prod_units<P, K, true>(a, x_dev, h->stream) : launch_prod_units<P, K, false>(a, x_dev, h->stream);
+        if constexpr (K::kShardForm)
+            e = shard ? launch_prod_units<P, K, true>(a, x_dev, h->stream) : launch_prod_units<P, K, false>(a, x_dev, h->stream);
+        else e = launch_prod_units<P, K, false>(a, x_dev, h->stream);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
     return CTD_OK;
@@ -1433,6 +1444,69 @@ int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_we
     return host_call(h, {{x, h->d_x, L.nvar}, {v, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}},
                      [&] { return enqueue_hprod(h, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_pout.p); },
                      {{Hv, h->d_pout, L.nvar}});
+}
+
+// ---- matrix-free KKT products: rx = (sigma H_f + sum y_r H_{c_r}) dx + J' dy + sx o dx, rc = J dx - sc o dy ------------------
+// ctd_kkt_kernels.hpp.  Checks in the order of prod_check: handle, device, whole-grid handle (there is no shard form), the
+// required pointers, then the outputs against every input and against each other.
+static int32_t kktprod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* y, const double* dx,
+                             const double* dy, const double* sx, const double* sc, const double* rx, const double* rc) {
+    if (on.st) return on.st;
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; the shard form of the KKT product "
+                                   "(step_begin / step_end, ctd_set_x_shards) is out of scope");
+    if (!x || !dx || !dy || !rx || !rc) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (x, dx, dy, rx and rc are required)");
+    for (const double* in : {x, y, dx, dy, sx, sc})
+        if (in && (in == rx || in == rc)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
+    if (rx == rc) return fail(h, CTD_EINVAL, std::string(fn) + ": rx and rc must be different buffers");
+    return CTD_OK;
+}
+
+static int32_t enqueue_kktprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                               const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
+    const char* fn = "ctd_kktprod";
+    if (const int32_t st = jit_load(h, JIT_KKT)) return st;
+    const Layout& L = h->model.L;
+    KktParams kp;
+    std::memset(&kp, 0, sizeof(kp));
+    kp.h.p.L = L;
+    kp.h.p.tau = h->d_tau.p;
+    kp.h.p.dir = y_dev;
+    kp.h.p.out = rx_dev;
+    kp.h.vt = dx_dev;
+    kp.h.sigma = obj_weight;
+    kp.dy = dy_dev;
+    kp.sx = sx_dev;
+    kp.sc = sc_dev;
+    kp.rc = rc_dev;
+    prod_units(h, kp.h.p, false);
+    int jc = 1;         // the fused lanes keep the hprod chunk rule (profiles/kktprod_resources.md)
+    if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
+    for_problem(h->model.problem, [&](auto tag) { jc = HProdDirs<typename decltype(tag)::type>::JC; });
+    return enqueue_prod_units<KktKernels>(h, fn, kp, hprod_dirs_per_node(L), jc, h->d_kktpartial, h->jit[JIT_KKT], 0, x_dev, false);
+}
+
+int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                              const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
+    const OnDevice on(h, "ctd_kktprod_dev_async");
+    const int32_t st = kktprod_check(on, h, "ctd_kktprod_dev_async", x_dev, y_dev, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
+    return st ? st : enqueue_kktprod(h, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
+}
+
+// host pointers: x, y, dx and rx staged as for ctd_hprod; dy, sx, sc and rc through buffers of their own
+int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* dx, const double* dy,
+                    const double* sx, const double* sc, double* rx, double* rc) {
+    const OnDevice on(h, "ctd_kktprod");
+    const int32_t st = kktprod_check(on, h, "ctd_kktprod", x, y, dx, dy, sx, sc, rx, rc);
+    if (st) return st;
+    const Layout& L = h->model.L;
+    return host_call(h, {{x, h->d_x, L.nvar}, {dx, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}, {dy, h->d_kdy, L.ncon},
+                         {sx, h->d_ksx, L.nvar}, {sc, h->d_ksc, L.ncon}},
+                     [&] {
+                         return enqueue_kktprod(h, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_kdy.p,
+                                                sx ? h->d_ksx.p : nullptr, sc ? h->d_ksc.p : nullptr, h->d_pout.p, h->d_krc.p);
+                     },
+                     {{rx, h->d_pout, L.nvar}, {rc, h->d_krc, L.ncon}});
 }
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {

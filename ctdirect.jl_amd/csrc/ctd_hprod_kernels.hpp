@@ -208,6 +208,7 @@ __global__ void __launch_bounds__(64) hprod_finish_kernel(const HProdParams hp, 
 // ---- launcher (launch_prod_units, instantiated per registry problem in ctd_pkern_*.hip) ----------------------------------
 struct HprodKernels {
     using Params = HProdParams;
+    static constexpr bool kShardForm = true;
     static ProdParams& prod(Params& a) { return a.p; }
     static const ProdParams& prod(const Params& a) { return a.p; }
     template <class P, int SC, int S, bool SH> static constexpr auto units = &hprod_units_kernel<P, SC, S, SH>;

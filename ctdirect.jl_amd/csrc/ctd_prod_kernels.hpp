@@ -591,6 +591,7 @@ hipError_t launch_jprod(const ProdParams& pp, const double* xu, hipStream_t st) 
 // (enqueue_prod_units, ctd_engine.hip)
 struct JtprodKernels {
     using Params = ProdParams;
+    static constexpr bool kShardForm = true;        // (the SH = true kernels exist: enqueue_prod_units, ctd_engine.hip)
     static ProdParams& prod(Params& a) { return a; }
     static const ProdParams& prod(const Params& a) { return a; }
     template <class P, int SC, int S, bool SH> static constexpr auto units = &jtprod_units_kernel<P, SC, S, SH>;

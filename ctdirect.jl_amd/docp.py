@@ -513,6 +513,48 @@ class DOCP:
         self._ck(L.ctd_hprod(self._h, _dp(x), _dp(y), float(obj_weight), _dp(v), _dp(out)))
         return out
 
+    def kktprod(self, x, y, dx, dy, obj_weight=1.0, sx=None, sc=None, out=None, sync=True):
+        """The regularised KKT operator of an interior-point / SQP step applied to (dx, dy), matrix-free:
+            rx = (obj_weight d2 f + sum_i y_i d2 c_i)(x) dx + J(x)' dy + sx * dx      (nvar entries)
+            rc = J(x) dx - sc * dy                                                    (ncon entries; note the sign of sc)
+        in two kernel launches (`ctd_kktprod*`).  y = None: all multipliers zero; sx / sc = None: no diagonal term.  Returns
+        (rx, rc); `out` is a pair (rx, rc), which may be two slices of one tensor, as may dx and dy.  The Hessian and the Jacobian
+        are the structural ones (see `hprod`, `jprod`).  NumPy inputs use the host entry point; device tensors are enqueued on
+        the handle's stream (`ctd_kktprod_dev_async`), followed by a sync when `sync`.  Whole-grid handles only."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        L = _lib.lib()
+        self._check_x(x)
+        sizes = (("y", y, ncon), ("dx", dx, nvar), ("dy", dy, ncon), ("sx", sx, nvar), ("sc", sc, ncon))
+        for name, a, n in sizes:
+            if a is None and name in ("dx", "dy"):
+                raise ValueError(f"{name} is required")
+        rx, rc = (None, None) if out is None else out
+        if _is_tensor(x):
+            import torch
+            if rx is None:
+                rx = torch.empty(nvar, dtype=torch.float64, device=x.device)
+            if rc is None:
+                rc = torch.empty(ncon, dtype=torch.float64, device=x.device)
+            p = {name: None if a is None else self._dev_ptr(a, n, name) for name, a, n in sizes}
+            self._ck(L.ctd_kktprod_dev_async(self._h, self._dev_ptr(x, nvar, "x"), p["y"], float(obj_weight), p["dx"], p["dy"],
+                                             p["sx"], p["sc"], self._dev_ptr(rx, nvar, "out[0]"), self._dev_ptr(rc, ncon, "out[1]")))
+            if sync:
+                self.sync()
+            return rx, rc
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        h = {}
+        for name, a, n in sizes:
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != n:
+                    raise ValueError(f"{name} has {a.size} entries, expected {n}")
+            h[name] = a
+        rx = np.empty(nvar) if rx is None else _host_out(rx, nvar, "out[0]")
+        rc = np.empty(ncon) if rc is None else _host_out(rc, ncon, "out[1]")
+        self._ck(L.ctd_kktprod(self._h, _dp(x), _dp(h["y"]), float(obj_weight), _dp(h["dx"]), _dp(h["dy"]), _dp(h["sx"]),
+                               _dp(h["sc"]), _dp(rx), _dp(rc)))
+        return rx, rc
+
     def grad_shard(self, x, g, sync=False):
         """`ctd_grad_shard_dev_async`: the gradient entries of THIS shard's own variables into the full-length device tensor g
         (+ the shard's partial sums of d/dv in the nv tail entries), from a sharded iterate read in place -- no all-gathered x."""

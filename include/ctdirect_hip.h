@@ -410,6 +410,40 @@ int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_we
 int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
                             double* Hv_dev);
 
+/* Matrix-free product with the regularised augmented (KKT) matrix at (x, y): the operator a Krylov solver applies once per inner
+ * iteration of an interior-point or SQP step.  There is no NLPModels counterpart.
+ *   rx = (obj_weight H_f(x) + sum_r y_r H_{c_r}(x)) dx + J(x)' dy + sx o dx   (nvar entries)
+ *   rc = J(x) dx - sc o dy                                                    (ncon entries)
+ * NOTE THE SIGN of sc: the bottom block is J dx MINUS sc o dy, the quasi-definite form that Ipopt and MadNLP regularise to
+ * (sx, sc >= 0 make K symmetric quasi-definite).  x, dx, sx and rx have nvar entries; y, dy, sc and rc have ncon entries in the row
+ * order of ctd_cons.  H and J are the structural ones, exactly as documented for ctd_hprod and ctd_jprod above: the exact
+ * derivatives of what ctd_obj / ctd_cons compute whatever the handle's pattern_mode or value_order, kinks by the conventions of
+ * ctd_hess_coord, second-order terms through a free t0 / tf included.
+ * y == NULL: every multiplier is zero.  sx == NULL or sc == NULL: that diagonal term is absent.  Each gives results value-equal to
+ * passing a vector of zeros.  dy is required.
+ * rx / rc, and dx / dy, may be the two halves of one (nvar + ncon)-long buffer (a Krylov vector): no pointer needs more than
+ * 8-byte alignment.
+ * Two kernel launches per call (a unit pass and a finish, like ctd_hprod) instead of the seven dispatches of hprod + jtprod +
+ * jprod + two element-wise updates: the second-order lanes of hprod already hold the first derivatives of every row along their
+ * own directions (J' dy) and along dx (J dx).  The results differ from that composition by rounding only; they are NOT its bits.
+ * Results are reproducible bit for bit (fixed summation order, no floating-point atomics) and equal for every pattern_mode /
+ * value_order of one transcription.  No device memory proportional to nnzj or nnzh is allocated; the partial-sum buffer (one row of
+ * kMaxNV doubles per workgroup) is this call's own, so a graph captured over ctd_hprod or ctd_jtprod keeps its buffer; the host call
+ * stages its eight vectors through buffers the handle owns.
+ * Run-time OCPs (ctd_register_ocp) compile their KKT kernels on the first ctd_kktprod* call: make one call before capturing a
+ * graph.
+ * OUT OF SCOPE: the shard form (a shard handle is refused; there is no ShardedDOCP.kktprod), a batched form, several right-hand
+ * sides per call, and any preconditioner.
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE, whatever the other arguments; shard handle
+ * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL; null x, dx, dy, rx or rc -> CTD_EINVAL;
+ * an output equal to any input, or rx == rc -> CTD_EINVAL.  ctd_last_error names the reason. */
+/* host pointers: returns when rx, rc are in the caller's buffers */
+int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* dx, const double* dy,
+                    const double* sx, const double* sc, double* rx, double* rc);
+/* device pointers on the handle's device: enqueue-only on the handle's stream (ctd_sync waits), capturable after one warm call */
+int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                              const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev);
+
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
  * ctd_sharded_handle included), modelled on ctd_grad_shard_dev_async: enqueue-only on the handle's stream, capturable after one
