@@ -72,6 +72,7 @@ struct ctd_handle {
     bool own_stream = false;
     int64_t step_begin = 0, step_end = 0;
     int tile = 0, block = 256;
+    int lean_ok = 1;            // registry OCPs: the lean variant of the constraint / Jacobian kernel may be launched (env CTD_LEAN=0: never)
     KParams kp;                 // device pointers filled in, outputs set per call
     size_t lds_bytes = 0;
     int grid = 0;
@@ -465,6 +466,18 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     }
     if (st) return fail(nullptr, st, err);
     const Model& mo = h->model;
+    // The lean variant of the constraint / Jacobian kernel reads its block sizes, counts and Butcher tables from the static layout
+    // of its instantiation (StaticLayout, ctd_kernel_body.hpp), not from the kernel arguments: a handle whose built layout differs
+    // from it is refused here -- every handle, host-only ones included -- so a wrong constant never becomes a wrong Jacobian.
+    // (Run-time OCPs have no registry instantiation; midpoint with more than 3 controls per step has no kernel at all.)
+    if (!runtime_ocp(mo.problem)) {
+        const char* bad = nullptr;
+        for_problem(mo.problem, [&](auto tag) {
+            using P = typename decltype(tag)::type;
+            for_scheme<true>(mo.L, [&](auto t) { bad = static_layout_mismatch<P, t.sc, t.s>(mo.L); });
+        });
+        if (bad) return fail(nullptr, CTD_EINVAL, std::string("ctd_create: the static layout of the kernel instantiation differs from the model's layout in field '") + bad + "'");
+    }
     if (mo.L.cs > 3 && desc->device >= 0 && !runtime_ocp(mo.problem))      // (host-only handles -- sizes, bounds, patterns -- take any)
         return fail(nullptr, CTD_EINVAL, "ctd_create: control_steps > 3 needs an OCP registered at run time (ctd_register_ocp); the compiled registry holds the midpoint kernels for 1, 2 and 3 controls per step");
     h->step_begin = desc->step_begin;
@@ -473,6 +486,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     if (h->step_begin < 0 || h->step_end > mo.L.N || h->step_begin >= h->step_end)
         return fail(nullptr, CTD_EINVAL, "ctd_create: shard [step_begin, step_end) is not inside [0, N)");
     h->tile = env_int("CTD_TILE", 0);
+    h->lean_ok = env_int("CTD_LEAN", 1) ? 1 : 0;
     if (h->tile <= 0) h->tile = default_tile(mo, h->step_end - h->step_begin);
     int maxb = 256;
     for_problem(mo.problem, [&](auto tag) { maxb = decltype(tag)::type::MAXB; });
@@ -1068,7 +1082,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_cons_jac<P>(kp, x_dev, h->grid, h->block, h->lds_bytes, h->stream, te0, te1);
+        e = launch_cons_jac<P>(kp, x_dev, h->grid, h->block, h->lds_bytes, h->stream, te0, te1, h->lean_ok);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;

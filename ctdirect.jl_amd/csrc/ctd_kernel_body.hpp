@@ -84,7 +84,12 @@ struct BlockCtx {
 };
 
 // blocks of a shard whose reads leave the shard's own variables (kp.halo set): the tiles at either end, the edge block
+// LEAN (here and in every phase template below): the variant of the kernel for handles whose iterate is whole (kp.halo null) and
+// that emit everything behind the barrier (kp.n_early 0) -- launch_cons_jac picks it per launch.  It reads none of kp.halo,
+// kp.near, kp.pos, kp.n_early, kp.c_early, kp.vr_early, kp.n_late, kp.div_late: their branches and scalar registers are compiled out.
+template <bool LEAN = false>
 CTD_HD const XHalo* block_halo(const KParams& kp, const BlockCtx& cx) {
+    if constexpr (LEAN) return nullptr;
     if (!kp.halo) return nullptr;
     if (cx.is_edge) return kp.halo;
     return (cx.lo < kp.step_begin || cx.b + kp.HH >= kp.step_end) ? kp.halo : nullptr;
@@ -99,12 +104,25 @@ inline int wgs_per_cu(int64_t lds_bytes) {
     const int64_t g = (lds_bytes + 1279) / 1280 * 1280;
     return g > 0 ? (int)((160 * 1024) / g) : 32;
 }
-CTD_HD int code_doubles(const KParams& kp) { return codes_staged(kp) ? (kp.Lseg + kp.L.nv * kp.vr + 1) / 2 : 0; }
+// (nv >= 0: the caller knows the count of optimisation variables at compile time -- the lean variant)
+CTD_HD int code_doubles(const KParams& kp, int nv = -1) { return codes_staged(kp) ? (kp.Lseg + (nv < 0 ? kp.L.nv : nv) * kp.vr + 1) / 2 : 0; }
 
-CTD_HD int64_t slot_index(const KParams& kp, const BlockCtx& cx, int k) {
-    return cx.is_edge ? kp.edge_steps[k] : cx.lo + k;
+// step held by slot k of the edge block.  The slot differs between the lanes of a wave, so kp.edge_steps[k] is a vector load from
+// the kernel-argument segment: a memory round trip in front of the loads of x, which need its result.  The lean variant selects the
+// step from the (at most six) uniform values instead, which sit in scalar registers -- the same value.
+template <bool LEAN = false> CTD_HD int64_t edge_step(const KParams& kp, int k) {
+    if constexpr (LEAN) {
+        int64_t st = kp.edge_steps[0];
+#pragma unroll
+        for (int e = 1; e < kMaxEdgeSlots; ++e) st = (k == e) ? kp.edge_steps[e] : st;
+        return st;
+    } else return kp.edge_steps[k];
+}
+template <bool LEAN = false> CTD_HD int64_t slot_index(const KParams& kp, const BlockCtx& cx, int k) {
+    return cx.is_edge ? edge_step<LEAN>(kp, k) : cx.lo + k;
 }
 
+template <bool LEAN = false>
 CTD_HD BlockCtx make_ctx(const KParams& kp, int block, double* lds) {
     BlockCtx cx;
     cx.direct = 0;
@@ -138,7 +156,7 @@ CTD_HD BlockCtx make_ctx(const KParams& kp, int block, double* lds) {
         cx.rec = cx.tau + cap + 2;
     }
     cx.xu = nullptr;
-    cx.halo = block_halo(kp, cx);
+    cx.halo = block_halo<LEAN>(kp, cx);
     return cx;
 }
 
@@ -148,16 +166,18 @@ CTD_HD BlockCtx make_ctx(const KParams& kp, int block, double* lds) {
 // evaluate hop of the staged driver disappears; the only workgroup barrier left sits between the evaluation and the emission.
 // `in`, `v` point into xu (global address space: this context is built on a code path of its own so the compiler emits
 // global loads, not flat ones), `tau` is null: slot_tau computes the times of the lane's own grid points.
-CTD_HD BlockCtx make_direct_ctx(const KParams& kp, int block, double* lds, const double* xu) {
+template <bool LEAN = false>
+CTD_HD BlockCtx make_direct_ctx(const KParams& kp, int block, double* lds, const double* xu, int blk = -1, int nv = -1) {
     BlockCtx cx;
     const Layout& L = kp.L;
+    if (blk < 0) blk = L.blk;          // (the lean variant passes the block size of its static layout)
     cx.direct = 1;
     cx.codes = kp.tmpl;
     cx.vcodes = kp.vtmpl;
-    cx.in_stride = L.blk;
+    cx.in_stride = blk;
     cx.v = const_cast<double*>(xu) + L.v_off;
     cx.tau = nullptr;
-    cx.rec = lds + code_doubles(kp);
+    cx.rec = lds + code_doubles(kp, nv);
     cx.xu = xu;
     cx.halo = nullptr;
     cx.edge_part = 0;
@@ -169,7 +189,7 @@ CTD_HD BlockCtx make_direct_ctx(const KParams& kp, int block, double* lds, const
         cx.nslots = kp.n_edge_slots;
         cx.a = cx.b = cx.lo = 0;
         cx.in = const_cast<double*>(xu);
-        cx.halo = kp.halo;
+        if constexpr (!LEAN) cx.halo = kp.halo;
         return cx;
     }
     const int tile = block - kp.has_edge;      // (the XCD-aware tile order of the staged driver measured neutral: not offered here)
@@ -178,37 +198,41 @@ CTD_HD BlockCtx make_direct_ctx(const KParams& kp, int block, double* lds, const
     cx.b = cx.a + kp.T < kp.step_end ? cx.a + kp.T : kp.step_end;
     cx.lo = cx.a - kp.HL;
     cx.nslots = (int)(cx.b - cx.a) + kp.HL + kp.HH;
-    cx.in = const_cast<double*>(xu) + cx.lo * (int64_t)L.blk;
-    cx.halo = block_halo(kp, cx);
+    cx.in = const_cast<double*>(xu) + cx.lo * (int64_t)blk;
+    cx.halo = block_halo<LEAN>(kp, cx);
     return cx;
 }
 
 // inputs of slot k: staged copy in LDS, or (direct) the step's own block of xu -- of the owner's buffer when the iterate is
 // sharded and the step belongs to a neighbour
-CTD_HD const double* slot_base(const KParams& kp, const BlockCtx& cx, int k) {
+template <bool LEAN = false> CTD_HD const double* slot_base(const KParams& kp, const BlockCtx& cx, int k) {
     if (cx.direct && cx.halo) {
         const int64_t g = slot_index(kp, cx, k) * (int64_t)cx.in_stride;
         return xnear(kp.near, cx.xu, g) + g;
     }
-    if (cx.direct && cx.is_edge) return cx.in + kp.edge_steps[k] * (int64_t)cx.in_stride;
+    if (cx.direct && cx.is_edge) return cx.in + edge_step<LEAN>(kp, k) * (int64_t)cx.in_stride;
     return cx.in + k * cx.in_stride;
 }
 // X_{i+1} (and U_{i+1}) of slot k: behind the step's block, in the staged copy and in every buffer that holds both -- the
 // next shard's buffer for the last step of a shard
+template <bool LEAN = false>
 CTD_HD const double* slot_next(const KParams& kp, const BlockCtx& cx, int k) {
+    if constexpr (LEAN) { if (cx.direct) return slot_base<LEAN>(kp, cx, k) + cx.in_stride; }      // (direct blocks: in_stride is the block size)
     if (cx.direct && cx.halo) {
         const int64_t g = (slot_index(kp, cx, k) + 1) * (int64_t)cx.in_stride;
         return xnear(kp.near, cx.xu, g) + g;
     }
-    return slot_base(kp, cx, k) + ((cx.direct || cx.is_edge) ? kp.L.blk : cx.in_stride);     // (staged tile: the next slot)
+    return slot_base<LEAN>(kp, cx, k) + ((cx.direct || cx.is_edge) ? kp.L.blk : cx.in_stride);     // (staged tile: the next slot)
 }
 // block of step i - 1 (implicit Euler's path control U_{i-1}); direct blocks only
+template <bool LEAN = false>
 CTD_HD const double* slot_prev(const KParams& kp, const BlockCtx& cx, int k) {
+    if constexpr (LEAN) { if (cx.direct) return slot_base<LEAN>(kp, cx, k) - cx.in_stride; }
     if (cx.direct && cx.halo) {
         const int64_t g = (slot_index(kp, cx, k) - 1) * (int64_t)cx.in_stride;
         return xnear(kp.near, cx.xu, g) + g;
     }
-    return slot_base(kp, cx, k) - ((cx.direct || cx.is_edge) ? kp.L.blk : cx.in_stride);
+    return slot_base<LEAN>(kp, cx, k) - ((cx.direct || cx.is_edge) ? kp.L.blk : cx.in_stride);
 }
 
 // LDS doubles a block needs (host uses this to size the launch)
@@ -229,8 +253,8 @@ CTD_HD double tau_global(const KParams& kp, int64_t i) {
     return kp.tau ? kp.tau[i] : (double)i / (double)kp.L.N;
 }
 // direct blocks hold no staged times: the lane reads (or computes) tau of its own grid points
-CTD_HD double slot_tau(const KParams& kp, const BlockCtx& cx, int k, int d) {
-    if (cx.direct) return tau_global(kp, slot_index(kp, cx, k) + d);
+template <bool LEAN = false> CTD_HD double slot_tau(const KParams& kp, const BlockCtx& cx, int k, int d) {
+    if (cx.direct) return tau_global(kp, slot_index<LEAN>(kp, cx, k) + d);
     return cx.is_edge ? cx.tau[2 * k + d] : cx.tau[k + d];
 }
 CTD_HD double final_tau(const KParams& kp, const BlockCtx& cx) {       // edge block only
@@ -298,6 +322,89 @@ template <class P> struct Dirs {
 // nodes (phase_fin2) and keeps the staged one
 template <class P, int SC> struct DirectTile { static constexpr bool value = Dirs<P>::FUSED && SC != SC_TRAPEZE; };
 
+// What build_layout (ctd_host.cpp) fixes of `Layout` for a registry instantiation <P, SC, S> (S: stages of a Gauss-Legendre scheme,
+// controls per step of the midpoint class, 1 for trapeze): the counts, the block sizes and the Butcher tables.  The lean variant of
+// the kernel reads these constants instead of the kernel arguments -- they cost no scalar register and no scalar load, and the
+// divisions by cb are divisions by a constant.  The one flag that makes a block size two-valued stays a run-time value: `stagewise`
+// (Gauss-Legendre: one control per stage) selects between two constants.  ctd_create compares this description with the Layout
+// the model builder produced (static_layout_mismatch) and refuses the handle when they differ.
+constexpr double kSqrt3 = 1.7320508075688772, kSqrt15 = 3.872983346207417;      // correctly rounded: what std::sqrt gives build_layout
+template <class P, int SC, int S> struct StaticLayout {
+    static constexpr int n = P::NX, m = P::NU, nv = P::NV, p = P::NPATH, bc = P::NBC;
+    static constexpr int s = SC == SC_IRK ? S : 0;
+    static constexpr int eqs = SC == SC_IRK ? n * (1 + S) : n;
+    static constexpr int cb = eqs + p;
+    CTD_HD static constexpr int cu(bool stagewise) { return SC == SC_TRAPEZE ? m : ((SC == SC_MIDPOINT || stagewise) ? m * S : m); }
+    CTD_HD static constexpr int blk(bool stagewise) { return n + cu(stagewise) + (SC == SC_IRK ? S * n : 0); }
+    // Butcher tables of the Gauss-Legendre schemes, the Float64 expressions of set_butcher (ctd_host.cpp); 0 outside the table
+    CTD_HD static constexpr double a(int j, int l) {
+        if (SC != SC_IRK || j >= S || l >= S) return 0.0;
+        if (S == 1) return 0.5;
+        if (S == 2) return j == l ? 0.25 : (j == 0 ? 0.25 - kSqrt3 / 6 : 0.25 + kSqrt3 / 6);
+        switch (3 * j + l) {
+            case 0: return 5.0 / 36.0;                case 1: return 2.0 / 9 - kSqrt15 / 15;   case 2: return 5.0 / 36 - kSqrt15 / 30;
+            case 3: return 5.0 / 36.0 + kSqrt15 / 24; case 4: return 2.0 / 9.0;                case 5: return 5.0 / 36.0 - kSqrt15 / 24;
+            case 6: return 5.0 / 36 + kSqrt15 / 30;   case 7: return 2.0 / 9 + kSqrt15 / 15;   default: return 5.0 / 36.0;
+        }
+    }
+    CTD_HD static constexpr double b(int j) {
+        if (SC != SC_IRK || j >= S) return 0.0;
+        if (S == 1) return 1.0;
+        if (S == 2) return 0.5;
+        return j == 1 ? 4.0 / 9.0 : 5.0 / 18.0;
+    }
+    CTD_HD static constexpr double c(int j) {
+        if (SC != SC_IRK || j >= S) return 0.0;
+        if (S == 1) return 0.5;
+        if (S == 2) return j == 0 ? 0.5 - kSqrt3 / 6 : 0.5 + kSqrt3 / 6;
+        return j == 0 ? 0.5 - 0.1 * kSqrt15 : (j == 1 ? 0.5 : 0.5 + 0.1 * kSqrt15);
+    }
+};
+// name of the first field of L that differs from the static description of <P, SC, S>, or null: they agree (host: ctd_create)
+template <class P, int SC, int S> inline const char* static_layout_mismatch(const Layout& L) {
+    using SL = StaticLayout<P, SC, S>;
+    if (L.sc != SC) return "sc";
+    if (L.s != SL::s) return "s";
+    if (L.n != SL::n) return "n";
+    if (L.m != SL::m) return "m";
+    if (L.nv != SL::nv) return "nv";
+    if (L.p != SL::p) return "p";
+    if (L.bc != SL::bc) return "bc";
+    if (L.cu != SL::cu(L.stagewise != 0)) return "cu";
+    if (L.blk != SL::blk(L.stagewise != 0)) return "blk";
+    if (L.eqs != SL::eqs) return "eqs";
+    if (L.cb != SL::cb) return "cb";
+    for (int j = 0; j < 3; ++j) {
+        for (int l = 0; l < 3; ++l)
+            if (!(L.a[3 * j + l] == SL::a(j, l))) return "a";
+        if (!(L.b[j] == SL::b(j))) return "b";
+        if (!(L.c[j] == SL::c(j))) return "c";
+    }
+    return nullptr;
+}
+// The fields above as the kernels read them: the kernel argument (general variant), or the constant (LEAN)
+template <class P, int SC, int S, bool LEAN> struct LV {
+    using SL = StaticLayout<P, SC, S>;
+    CTD_HD static int cu(const KParams& kp) { if constexpr (LEAN) return kp.L.stagewise ? SL::cu(true) : SL::cu(false); else return kp.L.cu; }
+    CTD_HD static int blk(const KParams& kp) { if constexpr (LEAN) return kp.L.stagewise ? SL::blk(true) : SL::blk(false); else return kp.L.blk; }
+    CTD_HD static int cb(const KParams& kp) { if constexpr (LEAN) return SL::cb; else return kp.L.cb; }
+    CTD_HD static int eqs(const KParams& kp) { if constexpr (LEAN) return SL::eqs; else return kp.L.eqs; }
+    // x / cb for the small operands of the emit loops (fast_div with kp.div_cb: the same quotient)
+    CTD_HD static uint32_t div_cb(const KParams& kp, uint32_t x) { if constexpr (LEAN) return x / (uint32_t)SL::cb; else return fast_div(x, kp.div_cb); }
+    // Butcher entries at compile-time indices ...
+    CTD_HD static double a(const KParams& kp, int j, int l) { if constexpr (LEAN) return SL::a(j, l); else return kp.L.a[3 * j + l]; }
+    CTD_HD static double b(const KParams& kp, int j) { if constexpr (LEAN) return SL::b(j); else return kp.L.b[j]; }
+    // ... and for a stage index j that differs between the lanes of a wave (butcher_pick: selected from the S uniform values)
+    CTD_HD static double a_pick(const KParams& kp, int j, int l) {
+        if constexpr (LEAN) { const double t[3] = {SL::a(0, l), SL::a(S > 1 ? 1 : 0, l), SL::a(S > 2 ? 2 : 0, l)}; return butcher_pick<S>(t, j, 1, 0); }
+        else return butcher_a<S>(kp.L, j, l);
+    }
+    CTD_HD static double c_pick(const KParams& kp, int j) {
+        if constexpr (LEAN) { const double t[3] = {SL::c(0), SL::c(S > 1 ? 1 : 0), SL::c(S > 2 ? 2 : 0)}; return butcher_pick<S>(t, j, 1, 0); }
+        else return butcher_c<S>(kp.L, j);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------
 // phase: load
 // ------------------------------------------------------------------------------------------------------
@@ -311,7 +418,7 @@ CTD_HD void load_codes(const KParams& kp, const BlockCtx& cx, int tid, int nthr)
     for (int e = tid; e < nvc; e += nthr) dst[kp.Lseg + e] = kp.vtmpl[e];
 }
 
-template <class P, int SC, int S, bool LOAD_V = true>
+template <class P, int SC, int S, bool LOAD_V = true, bool LEAN = false>
 CTD_HD void phase_load(const KParams& kp, const BlockCtx& cx, const double* __restrict__ xu, int tid, int nthr) {
     const Layout& L = kp.L;
     if (cx.is_edge) {
@@ -321,7 +428,7 @@ CTD_HD void phase_load(const KParams& kp, const BlockCtx& cx, const double* __re
             int64_t g = kp.edge_steps[k] * L.blk + o;
             if (o >= L.blk + L.n + L.m)        // control of the previous step (own step for step 0): implicit Euler's path control
                 g = (kp.edge_steps[k] >= 1 ? kp.edge_steps[k] - 1 : 0) * (int64_t)L.blk + L.n + (o - (L.blk + L.n + L.m));
-            cx.in[e] = (g < L.v_off) ? (cx.halo ? xnear(kp.near, xu, g) : xu)[g] : 0.0;
+            cx.in[e] = (g < L.v_off) ? ((!LEAN && cx.halo) ? xnear(kp.near, xu, g) : xu)[g] : 0.0;
         }
         for (int e = tid; e <= 2 * cx.nslots; e += nthr)
             cx.tau[e] = (e == 2 * cx.nslots) ? tau_global(kp, L.N) : tau_global(kp, kp.edge_steps[e >> 1] + (e & 1));
@@ -339,7 +446,7 @@ CTD_HD void phase_load(const KParams& kp, const BlockCtx& cx, const double* __re
         // share of the emit templates), then stores them to LDS: one exposed memory latency instead of one per copy loop
         const bool codes = LOAD_V && codes_staged(kp);
         const int nvc = kp.L.nv * kp.vr;
-        if (cx.halo) {
+        if (!LEAN && cx.halo) {
             // first / last tile of a shard with the iterate sharded: every element from the buffer of the shard that owns it
             for (int e = tid; e < cnt; e += nthr) at(e) = xnear(kp.near, xu, g0 + e)[g0 + e];
             if (LOAD_V && tid < kMaxNV) cx.v[tid] = (tid < P::NV) ? xu[L.v_off + tid] : 0.0;
@@ -416,46 +523,47 @@ CTD_HD void load_commit(const KParams& kp, const BlockCtx& cx, const double* __r
 // ------------------------------------------------------------------------------------------------------
 // finishing pieces (called from the eval lanes when Dirs<P>::FUSED, from phase_fin otherwise)
 // ------------------------------------------------------------------------------------------------------
-template <class P> CTD_HD void fill_const_coefs(const KParams& kp, double* C) {
+template <class P, int SC = SC_TRAPEZE, int S = 1, bool LEAN = false> CTD_HD void fill_const_coefs(const KParams& kp, double* C) {
 #pragma unroll
     for (int e = 0; e < kNC; ++e) C[e] = 0.0;
     C[C_ONE] = 1.0; C[C_NEG1] = -1.0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) C[C_B + j] = kp.L.b[j];
+    for (int j = 0; j < 3; ++j) C[C_B + j] = LV<P, SC, S, LEAN>::b(kp, j);
 }
 
 // per-record coefficients + (IRK) the state-equation rows, which depend on the inputs only
 // `row` < 0: the whole lead role of slot k; `row` = r >= 0 (Gauss-Legendre schemes, wide states): state row r only, the
 // coefficients with row 0 -- one lane per (step, row) instead of a serial walk over the n rows
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool LEAN = false>
 CTD_HD void fin_lead(const KParams& kp, const BlockCtx& cx, int k, int row = -1) {
+    using V = LV<P, SC, S, LEAN>;
     constexpr int n = P::NX, nv = P::NV;
     const Layout& L = kp.L;
     constexpr RecLayout R = RL<P, SC, S>::R;
-    const int64_t i = slot_index(kp, cx, k);
+    const int64_t i = slot_index<LEAN>(kp, cx, k);
     double* rec = cx.rec + k * R.stride;
     double* C = rec + R.oC;
-    if (row <= 0) fill_const_coefs<P>(kp, C);
+    if (row <= 0) fill_const_coefs<P, SC, S, LEAN>(kp, C);
     if (i < 0 || i >= L.N) return;
-    const double tau0 = slot_tau(kp, cx, k, 0), tau1 = slot_tau(kp, cx, k, 1);
+    const double tau0 = slot_tau<LEAN>(kp, cx, k, 0), tau1 = slot_tau<LEAN>(kp, cx, k, 1);
     const double h = time_of<P>(kp, cx.v, tau1) - time_of<P>(kp, cx.v, tau0);
     if (SC == SC_IRK) {
-        const double* base = slot_base(kp, cx, k);
-        const double* nxt = slot_next(kp, cx, k);
-        const double* K = base + n + L.cu;
+        const double* base = slot_base<LEAN>(kp, cx, k);
+        const double* nxt = slot_next<LEAN>(kp, cx, k);
+        const double* K = base + n + V::cu(kp);
         if (row <= 0) {
 #pragma unroll
             for (int j = 0; j < S; ++j) {
 #pragma unroll
-                for (int l = 0; l < S; ++l) C[C_HA + 3 * j + l] = -(h * L.a[3 * j + l]);
-                C[C_HB + j] = -(h * L.b[j]);
+                for (int l = 0; l < S; ++l) C[C_HA + 3 * j + l] = -(h * V::a(kp, j, l));
+                C[C_HB + j] = -(h * V::b(kp, j));
             }
         }
         if (row >= 0) {          // one state row, r a runtime value (addresses only)
             const int r = row;
-            double sumbk = L.b[0] * K[r];
+            double sumbk = V::b(kp, 0) * K[r];
 #pragma unroll
-            for (int j = 1; j < S; ++j) sumbk = sumbk + L.b[j] * K[j * n + r];
+            for (int j = 1; j < S; ++j) sumbk = sumbk + V::b(kp, j) * K[j * n + r];
             rec[R.oR + r] = nxt[r] - (base[r] + h * sumbk);
 #pragma unroll
             for (int kk = 0; kk < nv; ++kk) {
@@ -467,9 +575,9 @@ CTD_HD void fin_lead(const KParams& kp, const BlockCtx& cx, int k, int row = -1)
         // state rows: X_{i+1} - (X_i + h sum_j b_j K^j)   (irk_stagewise.jl:456-457, irk.jl:304-306)
 #pragma unroll
         for (int r = 0; r < n; ++r) {
-            double sumbk = L.b[0] * K[r];
+            double sumbk = V::b(kp, 0) * K[r];
 #pragma unroll
-            for (int j = 1; j < S; ++j) sumbk = sumbk + L.b[j] * K[j * n + r];
+            for (int j = 1; j < S; ++j) sumbk = sumbk + V::b(kp, j) * K[j * n + r];
             rec[R.oR + r] = nxt[r] - (base[r] + h * sumbk);
 #pragma unroll
             for (int kk = 0; kk < nv; ++kk) {
@@ -489,19 +597,20 @@ CTD_HD void fin_lead(const KParams& kp, const BlockCtx& cx, int k, int row = -1)
 // `ev`: the eval block of (slot k, point j) -- its place in the LDS record, or a register copy the caller stores afterwards
 // (r0, rstep): the rows r0, r0 + rstep, ... only -- the lane that evaluated those rows of the dynamics (split evaluation: one
 // part per wave, so the row tests are wave-uniform branches) finishes them itself
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool LEAN = false>
 CTD_HD void fin_stage(const KParams& kp, const BlockCtx& cx, int k, int j, double* ev, int r0 = 0, int rstep = 1) {
+    using V = LV<P, SC, S, LEAN>;
     constexpr int n = P::NX, nv = P::NV;
     auto mine = [&](int r) { return rstep == 1 || (r % rstep) == r0; };
     constexpr bool FREE = Dirs<P>::FREE;
     const Layout& L = kp.L;
     constexpr RecLayout R = RL<P, SC, S>::R;
-    const int64_t i = slot_index(kp, cx, k);
+    const int64_t i = slot_index<LEAN>(kp, cx, k);
     if (i < 0) return;
     if (SC == SC_TRAPEZE ? (i > L.N) : (i >= L.N)) return;
     double* rec = cx.rec + k * R.stride;
-    const double* base = slot_base(kp, cx, k);
-    const double tau0 = slot_tau(kp, cx, k, 0), tau1 = slot_tau(kp, cx, k, 1);
+    const double* base = slot_base<LEAN>(kp, cx, k);
+    const double tau0 = slot_tau<LEAN>(kp, cx, k, 0), tau1 = slot_tau<LEAN>(kp, cx, k, 1);
     double dti[nv > 0 ? nv : 1], dh[nv > 0 ? nv : 1];
 #pragma unroll
     for (int kk = 0; kk < nv; ++kk) {
@@ -509,7 +618,7 @@ CTD_HD void fin_stage(const KParams& kp, const BlockCtx& cx, int k, int j, doubl
         dh[kk] = FREE ? dtime_of<P>(tau1, kk) - dti[kk] : 0.0;
     }
     if (SC == SC_IRK) {
-        const double* K = base + n + L.cu;
+        const double* K = base + n + V::cu(kp);
         // stage rows: K_i^j - f(...)   (irk_stagewise.jl:448-451)
 #pragma unroll
         for (int r = 0; r < n; ++r)
@@ -522,10 +631,10 @@ CTD_HD void fin_stage(const KParams& kp, const BlockCtx& cx, int k, int j, doubl
             for (int c = 0; c < n; ++c) {
                 double acc = 0.0;
 #pragma unroll
-                for (int l = 0; l < S; ++l) acc = acc + (dh[kk] * butcher_a<S>(L, j, l)) * K[l * n + c];
+                for (int l = 0; l < S; ++l) acc = acc + (dh[kk] * V::a_pick(kp, j, l)) * K[l * n + c];
                 dx[c] = acc;
             }
-            const double dtij = dti[kk] + butcher_c<S>(L, j) * dh[kk];
+            const double dtij = dti[kk] + V::c_pick(kp, j) * dh[kk];
 #pragma unroll
             for (int r = 0; r < n; ++r) {
                 if (!mine(r)) continue;
@@ -543,7 +652,7 @@ CTD_HD void fin_stage(const KParams& kp, const BlockCtx& cx, int k, int j, doubl
         // S = control_steps: f, W, ft hold the sums over the sub-steps (same t_s, x_s for all of them, midpoint.jl:53-69), so
         // x_{i+1} - (x_i + h_i sum_j f_j) with h_i = (t_{i+1} - t_i) / S  (:134-153; S = 1: :139)
         const double h = (time_of<P>(kp, cx.v, tau1) - time_of<P>(kp, cx.v, tau0)) / (double)S;
-        const double* nxt = slot_next(kp, cx, k);
+        const double* nxt = slot_next<LEAN>(kp, cx, k);
 #pragma unroll
         for (int r = 0; r < n; ++r) {
             if (!mine(r)) continue;
@@ -655,15 +764,16 @@ CTD_HD void fin_trapeze_step(const KParams& kp, const BlockCtx& cx, int k) {
 // ------------------------------------------------------------------------------------------------------
 // the control seen by path constraints: U_i, or for stagewise schemes the b-weighted stage average
 // (get_OCP_control_at_time_step, src/ode/common.jl:140-155 / irk_stagewise.jl:197-205)
-template <class P, int S> CTD_HD void node_control(const KParams& kp, const double* base, double* u) {
+template <class P, int S, int SC = SC_IRK, bool LEAN = false> CTD_HD void node_control(const KParams& kp, const double* base, double* u) {
     const Layout& L = kp.L;
+    using V = LV<P, SC, S, LEAN>;
     if (L.stagewise) {
 #pragma unroll
-        for (int c = 0; c < P::NU; ++c) u[c] = L.b[0] * base[P::NX + c];
+        for (int c = 0; c < P::NU; ++c) u[c] = V::b(kp, 0) * base[P::NX + c];
 #pragma unroll
         for (int j = 1; j < S; ++j)
 #pragma unroll
-            for (int c = 0; c < P::NU; ++c) u[c] = u[c] + L.b[j] * base[P::NX + j * P::NU + c];
+            for (int c = 0; c < P::NU; ++c) u[c] = u[c] + V::b(kp, j) * base[P::NX + j * P::NU + c];
     } else {
 #pragma unroll
         for (int c = 0; c < P::NU; ++c) u[c] = base[P::NX + c];
@@ -672,15 +782,15 @@ template <class P, int S> CTD_HD void node_control(const KParams& kp, const doub
 
 // control of the path constraints of node i held by slot k: node_control, except for implicit Euler where
 // u(t_i) = U_{i-1} for i >= 1 (get_OCP_control_at_time_step, euler.jl:59-72): previous block of a tile / extra field of an edge input
-template <class P, int S> CTD_HD void path_control(const KParams& kp, const BlockCtx& cx, int k, int64_t i, double* u) {
+template <class P, int S, int SC = SC_IRK, bool LEAN = false> CTD_HD void path_control(const KParams& kp, const BlockCtx& cx, int k, int64_t i, double* u) {
     const Layout& L = kp.L;
-    const double* base = slot_base(kp, cx, k);
+    const double* base = slot_base<LEAN>(kp, cx, k);
     if (L.euler == 2 && i >= 1 && (cx.is_edge || k >= 1)) {
-        const double* up = (cx.is_edge && !cx.direct) ? base + L.blk + P::NX + P::NU : slot_prev(kp, cx, k) + P::NX;
+        const double* up = (cx.is_edge && !cx.direct) ? base + L.blk + P::NX + P::NU : slot_prev<LEAN>(kp, cx, k) + P::NX;
 #pragma unroll
         for (int c = 0; c < P::NU; ++c) u[c] = up[c];
     } else {
-        node_control<P, S>(kp, base, u);
+        node_control<P, S, SC, LEAN>(kp, base, u);
     }
 }
 
@@ -789,16 +899,17 @@ CTD_HD void eval_point(const KParams& kp, const double* vv, int q, double t, con
 }
 
 // one dynamics evaluation on duals: slot k (step or node i), eval point j, direction chunk q
-template <class P, int SC, int S, bool SPLIT = false>
+template <class P, int SC, int S, bool SPLIT = false, bool LEAN = false>
 CTD_HD void eval_dynamics(const KParams& kp, const BlockCtx& cx, int k, int j, int q, double* ev) {
+    using V = LV<P, SC, S, LEAN>;
     constexpr int n = P::NX, m = P::NU, nv = P::NV;
     const Layout& L = kp.L;
     constexpr RecLayout R = RL<P, SC, S>::R;
-    const int64_t i = slot_index(kp, cx, k);
+    const int64_t i = slot_index<LEAN>(kp, cx, k);
     if (i < 0) return;
     if (SC == SC_TRAPEZE ? (i > L.N) : (i >= L.N)) return;
-    const double* base = slot_base(kp, cx, k);
-    const double ti = time_of<P>(kp, cx.v, slot_tau(kp, cx, k, 0));
+    const double* base = slot_base<LEAN>(kp, cx, k);
+    const double ti = time_of<P>(kp, cx.v, slot_tau<LEAN>(kp, cx, k, 0));
     double xv[n > 0 ? n : 1], uv[m > 0 ? m : 1];
     double t;
     if (SC == SC_TRAPEZE) {                       // f(t_i, X_i, U_i, v): trapeze.jl:60-69
@@ -808,8 +919,8 @@ CTD_HD void eval_dynamics(const KParams& kp, const BlockCtx& cx, int k, int j, i
 #pragma unroll
         for (int c = 0; c < m; ++c) uv[c] = base[n + c];
     } else if (SC == SC_MIDPOINT) {               // f(0.5(t_i+t_{i+1}), 0.5(X_i+X_{i+1}), U_i, v): midpoint.jl:53-66
-        const double tip1 = time_of<P>(kp, cx.v, slot_tau(kp, cx, k, 1));
-        const double* nxt = slot_next(kp, cx, k);
+        const double tip1 = time_of<P>(kp, cx.v, slot_tau<LEAN>(kp, cx, k, 1));
+        const double* nxt = slot_next<LEAN>(kp, cx, k);
         if (L.euler == 0) {
             t = 0.5 * (ti + tip1);
 #pragma unroll
@@ -822,14 +933,14 @@ CTD_HD void eval_dynamics(const KParams& kp, const BlockCtx& cx, int k, int j, i
 #pragma unroll
         for (int c = 0; c < m; ++c) uv[c] = base[n + c];
     } else {                                      // f(t_i + c_j h, X_i + h sum_l a_jl K^l, U_i^j | U_i, v): irk_stagewise.jl:424-446
-        const double h = time_of<P>(kp, cx.v, slot_tau(kp, cx, k, 1)) - ti;
-        t = ti + butcher_c<S>(L, j) * h;
-        const double* K = base + n + L.cu;
+        const double h = time_of<P>(kp, cx.v, slot_tau<LEAN>(kp, cx, k, 1)) - ti;
+        t = ti + V::c_pick(kp, j) * h;
+        const double* K = base + n + V::cu(kp);
 #pragma unroll
         for (int c = 0; c < n; ++c) {
             double x = base[c];
 #pragma unroll
-            for (int l = 0; l < S; ++l) x = x + h * butcher_a<S>(L, j, l) * K[l * n + c];
+            for (int l = 0; l < S; ++l) x = x + h * V::a_pick(kp, j, l) * K[l * n + c];
             xv[c] = x;
         }
         const double* U = base + n + (L.stagewise ? j * m : 0);
@@ -949,22 +1060,22 @@ CTD_HD void eval_path(const KParams& kp, double* rec, double t, const double* xv
     }
 }
 
-template <class P, int SC, int S, bool REG = false>
+template <class P, int SC, int S, bool REG = false, bool LEAN = false>
 CTD_HD void eval_step_path(const KParams& kp, const BlockCtx& cx, int k, int q) {
     constexpr int n = P::NX, m = P::NU, np = P::NPATH;
     constexpr RecLayout R = RL<P, SC, S>::R;
     constexpr int eqs = RL<P, SC, S>::cb - P::NPATH;      // = L.eqs
     const Layout& L = kp.L;
-    const int64_t i = slot_index(kp, cx, k);
+    const int64_t i = slot_index<LEAN>(kp, cx, k);
     if (i < 0 || i >= L.N) return;
-    const double* base = slot_base(kp, cx, k);
+    const double* base = slot_base<LEAN>(kp, cx, k);
     double uv[m > 0 ? m : 1];
-    path_control<P, S>(kp, cx, k, i, uv);
+    path_control<P, S, SC, LEAN>(kp, cx, k, i, uv);
     double xv[n > 0 ? n : 1];
 #pragma unroll
     for (int c = 0; c < n; ++c) xv[c] = base[c];
     double* rec = cx.rec + k * R.stride;
-    const double tau = slot_tau(kp, cx, k, 0);
+    const double tau = slot_tau<LEAN>(kp, cx, k, 0);
     if constexpr (REG) {
         // the path block and the path values are composed in registers (a private copy of the record's fields, every index a
         // compile-time constant) and stored once: no read-modify-write through LDS
@@ -978,7 +1089,7 @@ CTD_HD void eval_step_path(const KParams& kp, const BlockCtx& cx, int k, int q) 
 #pragma unroll
         for (int r = 0; r < np; ++r) rec[R.oR + eqs + r] = lrec[R.oR + eqs + r];
     } else {
-        eval_path<P, SC, S>(kp, rec, time_of<P>(kp, cx.v, tau), xv, uv, cx.v, q, R.oR + L.eqs);
+        eval_path<P, SC, S>(kp, rec, time_of<P>(kp, cx.v, tau), xv, uv, cx.v, q, R.oR + LV<P, SC, S, LEAN>::eqs(kp));
         if (Dirs<P>::FUSED) fin_path<P, SC, S>(kp, rec, tau);
     }
 }
@@ -1195,7 +1306,7 @@ template <class P, int SC, int S> CTD_HD int early_leadbase(const KParams& kp) {
     return (((r_dyn + r_path) << lgT) + 63) & ~63;
 }
 
-template <class P, int SC, int S, bool REG = false, int NB = 1, bool B = false>
+template <class P, int SC, int S, bool REG = false, int NB = 1, bool B = false, bool LEAN = false>
 CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* epre = nullptr,
                        const BatchLd bl = BatchLd{}) {
     constexpr bool FUSED = Dirs<P>::FUSED;
@@ -1223,21 +1334,21 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
                     if (k < ns) {
                         double* ev = cx.rec + k * R.stride + R.oEval + j * R.eval_sz;
                         if constexpr (parts) {
-                            eval_dynamics<P, SC, S, true>(kp, cx, k, j, wave, ev);
-                            fin_stage<P, SC, S>(kp, cx, k, j, ev, wave, NP);
+                            eval_dynamics<P, SC, S, true, LEAN>(kp, cx, k, j, wave, ev);
+                            fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev, wave, NP);
                         } else {
-                            eval_dynamics<P, SC, S>(kp, cx, k, j, 0, ev);
-                            fin_stage<P, SC, S>(kp, cx, k, j, ev);
+                            eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, 0, ev);
+                            fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev);
                         }
                     }
                 } else if (l >= 32) {
                     // aux kinds on lanes 32.. : path passes | final-time path passes + coefficient records | boundary passes, on the
                     // waves 0, 1, 2 when the dynamics parts fill the first lanes of all waves, else on the waves 1, 2, 3
                     const int a = wave - (parts ? 0 : 1), t = l - 32;
-                    if (a == 0) { if (t < r_path * 8 && (t & 7) < ns) eval_step_path<P, SC, S>(kp, cx, t & 7, t >> 3); }
+                    if (a == 0) { if (t < r_path * 8 && (t & 7) < ns) eval_step_path<P, SC, S, false, LEAN>(kp, cx, t & 7, t >> 3); }
                     else if (a == 1) {
                         if (t < n_fp) eval_final_path<P, SC, S>(kp, cx, t);
-                        else if (t >= 8 && t < 10) fill_const_coefs<P>(kp, cx.rec + (t == 8 ? kp.edge_fp : kp.edge_b) * R.stride + R.oC);
+                        else if (t >= 8 && t < 10) fill_const_coefs<P, SC, S, LEAN>(kp, cx.rec + (t == 8 ? kp.edge_fp : kp.edge_b) * R.stride + R.oC);
                     } else if (a == 2) { if (t < n_b) eval_boundary<P, SC, S>(kp, cx, t); }
                 }
                 for (int k = tid; k < ns + 2; k += nthr) cx.rec[k * R.stride] = 1.0;
@@ -1279,13 +1390,13 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
             if (kind == 0) {
                 const int j = role / Dirs<P>::NCH_DYN, q = role % Dirs<P>::NCH_DYN;
                 double* ev = cx.rec + k * R.stride + R.oEval + j * R.eval_sz;
-                eval_dynamics<P, SC, S>(kp, cx, k, j, q, ev);
-                if (FUSED) fin_stage<P, SC, S>(kp, cx, k, j, ev);
-            } else if (kind == 1) eval_step_path<P, SC, S>(kp, cx, k, role);
-            else if (kind == 2) fin_lead<P, SC, S>(kp, cx, k);
+                eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, ev);
+                if (FUSED) fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev);
+            } else if (kind == 1) eval_step_path<P, SC, S, false, LEAN>(kp, cx, k, role);
+            else if (kind == 2) fin_lead<P, SC, S, LEAN>(kp, cx, k);
             else if (kind == 3) eval_final_path<P, SC, S>(kp, cx, role);
             else if (kind == 4) eval_boundary<P, SC, S>(kp, cx, role);
-            else fill_const_coefs<P>(kp, cx.rec + (role == 0 ? kp.edge_fp : kp.edge_b) * R.stride + R.oC);
+            else fill_const_coefs<P, SC, S, LEAN>(kp, cx.rec + (role == 0 ? kp.edge_fp : kp.edge_b) * R.stride + R.oC);
         }
         for (int k = tid; k < ns + 2; k += nthr) cx.rec[k * R.stride] = 1.0;
         return;
@@ -1301,16 +1412,16 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
             const int wave = tid >> 6, l = tid & 63;
             const bool fold = fin_folded<P, SC, S>(cx);
             auto fin_path_slot = [&](int k) {          // total d/dv of the path rows of slot k (phase_fin's path task)
-                const int64_t i = slot_index(kp, cx, k);
-                if (i >= 0 && i < kp.L.N) fin_path<P, SC, S>(kp, cx.rec + k * R.stride, slot_tau(kp, cx, k, 0));
+                const int64_t i = slot_index<LEAN>(kp, cx, k);
+                if (i >= 0 && i < kp.L.N) fin_path<P, SC, S>(kp, cx.rec + k * R.stride, slot_tau<LEAN>(kp, cx, k, 0));
             };
             if (wave < NP) {
 #if !defined(CTD_ABL) || CTD_ABL != 2          /* (ablation builds, never shipped: 1 no path rows, 2 no dynamics, 3 no lead) */
                 if (l < nd) {
                     const int j = l / ns, k = l - j * ns;
                     double* ev = cx.rec + k * R.stride + R.oEval + j * R.eval_sz;
-                    eval_dynamics<P, SC, S, true>(kp, cx, k, j, wave, ev);
-                    if (fold) fin_stage<P, SC, S>(kp, cx, k, j, ev, wave, NP);      // the rows this wave's part evaluated
+                    eval_dynamics<P, SC, S, true, LEAN>(kp, cx, k, j, wave, ev);
+                    if (fold) fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev, wave, NP);      // the rows this wave's part evaluated
                 }
 #endif
                 CTD_SUB(kp, 2);
@@ -1319,9 +1430,9 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
                 // (step, state row) over the dynamics lanes of all waves, one-point schemes one task per step on the last wave
                 if (SC == SC_IRK) {
                     if (l < nd)
-                        for (int t = l * NP + wave; t < ns * P::NX; t += nd * NP) fin_lead<P, SC, S>(kp, cx, t / P::NX, t % P::NX);
+                        for (int t = l * NP + wave; t < ns * P::NX; t += nd * NP) fin_lead<P, SC, S, LEAN>(kp, cx, t / P::NX, t % P::NX);
                 } else if (l < ns && wave == NP - 1) {
-                    fin_lead<P, SC, S>(kp, cx, l);
+                    fin_lead<P, SC, S, LEAN>(kp, cx, l);
                 }
 #endif
                 CTD_SUB(kp, 3);
@@ -1331,7 +1442,7 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
                     // (part 1 of the 12-state quadrotor: 4100 cycles against 5100; the pass costs 3000); forward duals: chunk q on wave q
                     constexpr int PW = NP > 1 ? 1 : 0;
                     if (SymPath<P>::value ? wave == PW : wave < r_path) {
-                        eval_step_path<P, SC, S>(kp, cx, l - nd, SymPath<P>::value ? 0 : wave);
+                        eval_step_path<P, SC, S, false, LEAN>(kp, cx, l - nd, SymPath<P>::value ? 0 : wave);
                         if (fold) fin_path_slot(l - nd);
                     }
                 }
@@ -1345,7 +1456,7 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
     }
     const int lg = ns <= 1 ? 0 : 32 - __builtin_clz((unsigned)(ns - 1));
     const int mask = (1 << lg) - 1;
-    if constexpr (FUSED && SC == SC_IRK) {
+    if constexpr (FUSED && SC == SC_IRK && !LEAN) {
         if (kp.n_early > 0 && epre != nullptr) {
             // EARLY EMISSION: the lead tasks sit in a wave of their own (behind the dynamics / path lanes, at a wave boundary); that
             // wave then stores the outputs which only read its records while the other waves still evaluate
@@ -1363,25 +1474,25 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
                             double evr[R.eval_sz];
 #pragma unroll
                             for (int e = 0; e < R.eval_sz; ++e) evr[e] = 0.0;
-                            eval_dynamics<P, SC, S>(kp, cx, k, j, q, evr);
-                            fin_stage<P, SC, S>(kp, cx, k, j, evr);
-                            const int64_t i = slot_index(kp, cx, k);
+                            eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, evr);
+                            fin_stage<P, SC, S, LEAN>(kp, cx, k, j, evr);
+                            const int64_t i = slot_index<LEAN>(kp, cx, k);
                             if (i >= 0 && i < kp.L.N) {
 #pragma unroll
                                 for (int e = 0; e < R.eval_sz; ++e) ev[e] = evr[e];
                             }
                         } else {
-                            eval_dynamics<P, SC, S>(kp, cx, k, j, q, ev);
-                            fin_stage<P, SC, S>(kp, cx, k, j, ev);
+                            eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, ev);
+                            fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev);
                         }
                     } else {
-                        eval_step_path<P, SC, S, REG>(kp, cx, k, role - r_dyn);
+                        eval_step_path<P, SC, S, REG, LEAN>(kp, cx, k, role - r_dyn);
                     }
                 }
             } else if ((tid >> 6) == (leadbase >> 6)) {
                 const int k = tid - leadbase;
                 if (k < ns) {
-                    fin_lead<P, SC, S>(kp, cx, k);
+                    fin_lead<P, SC, S, LEAN>(kp, cx, k);
                     cx.rec[k * R.stride] = 1.0;
                 }
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1410,30 +1521,30 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
 #pragma unroll
                 for (int e = 0; e < R.eval_sz; ++e) evr[e] = 0.0;
                 CTD_SUB(kp, 1);
-                eval_dynamics<P, SC, S>(kp, cx, k, j, q, evr);
+                eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, evr);
                 CTD_SUB(kp, 2);
-                fin_stage<P, SC, S>(kp, cx, k, j, evr);
+                fin_stage<P, SC, S, LEAN>(kp, cx, k, j, evr);
                 CTD_SUB(kp, 3);
-                const int64_t i = slot_index(kp, cx, k);
+                const int64_t i = slot_index<LEAN>(kp, cx, k);
                 if (i >= 0 && i < kp.L.N) {
 #pragma unroll
                     for (int e = 0; e < R.eval_sz; ++e) ev[e] = evr[e];
                 }
                 CTD_SUB(kp, 4);
             } else {
-                eval_dynamics<P, SC, S>(kp, cx, k, j, q, ev);
+                eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, ev);
                 // (folded fin: the generated code put every partial of the point on the lane of chunk 0)
-                if (FUSED || (fold_g && q == 0)) fin_stage<P, SC, S>(kp, cx, k, j, ev);
+                if (FUSED || (fold_g && q == 0)) fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev);
             }
         } else if (role < r_dyn + r_path) {
-            eval_step_path<P, SC, S, REG>(kp, cx, k, role - r_dyn);
+            eval_step_path<P, SC, S, REG, LEAN>(kp, cx, k, role - r_dyn);
             if (fold_g) {
-                const int64_t i = slot_index(kp, cx, k);
-                if (i >= 0 && i < kp.L.N) fin_path<P, SC, S>(kp, cx.rec + k * R.stride, slot_tau(kp, cx, k, 0));
+                const int64_t i = slot_index<LEAN>(kp, cx, k);
+                if (i >= 0 && i < kp.L.N) fin_path<P, SC, S>(kp, cx.rec + k * R.stride, slot_tau<LEAN>(kp, cx, k, 0));
             }
         } else {
             CTD_SUB(kp, 1);
-            fin_lead<P, SC, S>(kp, cx, k);
+            fin_lead<P, SC, S, LEAN>(kp, cx, k);
             CTD_SUB(kp, 4);
         }
     }
@@ -1528,7 +1639,7 @@ template <class P, int SC, int S> struct EmitN {
 #endif
     static constexpr int value = (seg + 255) / 256 < 1 ? 1 : ((seg + 255) / 256 > CTD_PRE_MAX ? CTD_PRE_MAX : (seg + 255) / 256);
 };
-template <class P, int NB = 1>
+template <class P, int NB = 1, bool LEAN = false>
 CTD_HD EmitPreT<NB> emit_prefetch(const KParams& kp, const BlockCtx& cx, int tid, int nthr) {
     EmitPreT<NB> pre;
     pre.b = 0u;
@@ -1551,7 +1662,7 @@ CTD_HD EmitPreT<NB> emit_prefetch(const KParams& kp, const BlockCtx& cx, int tid
     }
     const int Ls = kp.Lseg;
     pre.kpos = 0; pre.eb = 0u; pre.ek = 0;
-    if (kp.n_early > 0) {
+    if (!LEAN && kp.n_early > 0) {
         // early emission: the lane's late position (two dependent loads, hidden behind the evaluation) and, for the lead wave, the
         // early output of lane l = tid & 63: [n_early positions | c_early rows of c | nv * vr_early V entries]
         const int q = tid - (int)fast_div((uint32_t)tid, kp.div_late) * kp.n_late;
@@ -1586,7 +1697,7 @@ CTD_HD EmitPreT<NB> emit_prefetch(const KParams& kp, const BlockCtx& cx, int tid
     return pre;
 }
 
-template <class P, int SC, int S, int NB = 1, bool B = false>
+template <class P, int SC, int S, int NB = 1, bool B = false, bool LEAN = false>
 CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB> pre_v, const bool hp,
                             const BatchLd bl = BatchLd{}) {
     const Layout& L = kp.L;
@@ -1628,14 +1739,15 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
     // inside each pass (fully coalesced 8-byte stores); with period > nthr a lane owns positions k, k + nthr, ...
     // (A) constraint rows of the tile: c[a*cb .. b*cb)
     if (kp.c) {
-        const int cb = L.cb;
+        using V = LV<P, SC, S, LEAN>;
+        const int cb = V::cb(kp);
         double* out = out_c<B>(kp, bl) + cx.a * (int64_t)cb;
-        const int par = (int)fast_div((uint32_t)nthr, kp.div_cb);
+        const int par = (int)V::div_cb(kp, (uint32_t)nthr);
         if (par >= 1) {
             if (tid < par * cb) {
-                const int g = (int)fast_div((uint32_t)tid, kp.div_cb), r = tid - g * cb;
+                const int g = (int)V::div_cb(kp, (uint32_t)tid), r = tid - g * cb;
                 const double* src = cx.rec + (slot0 + g) * stride + R.oR + r;
-                if (r >= kp.c_early)          // (early emission: the leading rows were stored by the lead wave)
+                if (LEAN || r >= kp.c_early)          // (early emission: the leading rows were stored by the lead wave)
                     for (int s = g; s < nsteps; s += par, src += par * stride) emit_store(&out[s * cb + r], *src, kp.wt_store);
             }
         } else {
@@ -1657,7 +1769,7 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
             double* out = out_vals<B>(kp, bl) + kp.seg_base + (ra - kp.reg_first) * (int64_t)Ls;
             const int sl0 = (int)(ra - cx.lo);
             // early emission: only the late positions are left (kp.pos[0 .. n_late)), more steps in flight per pass
-            const bool late_only = kp.n_early > 0;
+            const bool late_only = !LEAN && kp.n_early > 0;
             const int Lw = late_only ? kp.n_late : Ls;          // positions walked here
             const int par = (int)fast_div((uint32_t)nthr, late_only ? kp.div_late : kp.div_Lseg);
             // inner loops: uniform trip count and batches of 4 steps, so the 8 LDS reads of a batch are independent
@@ -1743,7 +1855,7 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
                     const double* pc = cx.rec + (slot0 + g) * stride + R.oC + code_ci(code);
                     const double* pd = cx.rec + (slot0 + g) * stride + code_di(code);
                     const int adv = par * stride;
-                    if (k >= kp.vr_early)      // (early emission: the leading entries were stored by the lead wave)
+                    if (LEAN || k >= kp.vr_early)      // (early emission: the leading entries were stored by the lead wave)
                         for (int s = g; s < nsteps; s += par, pc += adv, pd += adv) emit_store(&out[s * vr + k], (*pc) * (*pd), kp.wt_store);
                 }
             } else {
@@ -1759,11 +1871,11 @@ CTD_HD void phase_emit_impl(const KParams& kp, const BlockCtx& cx, int tid, int 
     CTD_SUBE(kp, 3);
 }
 // (pointer form: the drivers that always prefetch, and the emulator)
-template <class P, int SC, int S, int NB = 1, bool B = false>
+template <class P, int SC, int S, int NB = 1, bool B = false, bool LEAN = false>
 CTD_HD void phase_emit(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* pre = nullptr,
                        const BatchLd bl = BatchLd{}) {
-    if (pre != nullptr) phase_emit_impl<P, SC, S, NB, B>(kp, cx, tid, nthr, *pre, pre->have != 0, bl);
-    else phase_emit_impl<P, SC, S, NB, B>(kp, cx, tid, nthr, EmitPreT<NB>{}, false, bl);
+    if (pre != nullptr) phase_emit_impl<P, SC, S, NB, B, LEAN>(kp, cx, tid, nthr, *pre, pre->have != 0, bl);
+    else phase_emit_impl<P, SC, S, NB, B, LEAN>(kp, cx, tid, nthr, EmitPreT<NB>{}, false, bl);
 }
 
 }  // namespace ctd

@@ -38,9 +38,20 @@ __device__ __forceinline__ void ctd_stamp(const KParams& kp, int slot) {
 // scalar-cache miss after the other (nine rounds in the first version of this kernel, ~1 us before the first load of x was
 // issued).  Naming every field the tile path needs as an input of one empty asm statement makes the compiler issue all their
 // loads back to back at the top of the kernel: one miss latency, then everything sits in scalar registers.
-template <int S>
+template <int S, bool LEAN = false>
 __device__ __forceinline__ void ctd_pin_kernargs(const KParams& kp, const double* xu) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LEAN) {
+        // the lean variant: neither the shard table nor the early-emission fields, and none of what its static layout fixes (block
+        // sizes, counts, Butcher tables, the divisor cb)
+        asm volatile("" ::"s"(kp.has_edge), "s"(kp.ntiles), "s"(kp.T), "s"(kp.HL), "s"(kp.HH), "s"(kp.step_begin),
+                     "s"(kp.step_end), "s"(kp.L.N), "s"(kp.L.v_off), "s"(kp.L.stagewise), "s"(kp.L.euler), "s"(kp.tau), "s"(kp.L.t0),
+                     "s"(kp.L.tf), "s"(xu), "s"(blockDim.x));
+        asm volatile("" ::"s"(kp.tmpl), "s"(kp.vtmpl), "s"(kp.Lseg), "s"(kp.vr), "s"(kp.div_Lseg.M), "s"(kp.div_vr.M),
+                     "s"(kp.div_Lseg.d), "s"(kp.div_vr.d), "s"(kp.seg_base), "s"(kp.reg_first), "s"(kp.reg_last),
+                     "s"(kp.vcol_base[0]), "s"(kp.c), "s"(kp.vals));
+        return;
+    }
     asm volatile("" ::"s"(kp.has_edge), "s"(kp.ntiles), "s"(kp.T), "s"(kp.HL), "s"(kp.HH), "s"(kp.step_begin),
                  "s"(kp.step_end), "s"(kp.L.blk), "s"(kp.L.N), "s"(kp.L.v_off), "s"(kp.L.cu), "s"(kp.L.stagewise), "s"(kp.L.nv),
                  "s"(kp.L.cb), "s"(kp.L.eqs), "s"(kp.L.euler), "s"(kp.tau), "s"(kp.L.t0), "s"(kp.L.tf), "s"(xu), "s"(blockDim.x));
@@ -57,11 +68,17 @@ __device__ __forceinline__ void ctd_pin_kernargs(const KParams& kp, const double
 // kernel do not survive it: the compiler re-loads each kernel argument where the emit phase first uses it -- behind a branch
 // each, i.e. one scalar-cache round trip after the other again (a dozen `s_load; s_waitcnt lgkmcnt(0)` pairs on the critical path
 // of a 1.4 us phase).  Named once more in front of the barrier, they arrive together while the waves wait for each other.
+template <bool LEAN = false>
 __device__ __forceinline__ void ctd_pin_emit_kernargs(const KParams& kp) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" ::"s"(kp.c), "s"(kp.vals), "s"(kp.L.cb), "s"(kp.Lseg), "s"(kp.vr), "s"(kp.div_cb.M), "s"(kp.div_Lseg.M), "s"(kp.div_vr.M),
-                 "s"(kp.div_cb.d), "s"(kp.div_Lseg.d), "s"(kp.div_vr.d), "s"(kp.seg_base), "s"(kp.reg_first), "s"(kp.reg_last),
-                 "s"(kp.vcol_base[0]), "s"(kp.n_early), "s"(kp.c_early), "s"(kp.vr_early), "s"(kp.n_late), "s"(kp.div_late.M), "s"(kp.div_late.d));
+    if constexpr (LEAN)
+        asm volatile("" ::"s"(kp.c), "s"(kp.vals), "s"(kp.Lseg), "s"(kp.vr), "s"(kp.div_Lseg.M), "s"(kp.div_vr.M),
+                     "s"(kp.div_Lseg.d), "s"(kp.div_vr.d), "s"(kp.seg_base), "s"(kp.reg_first), "s"(kp.reg_last),
+                     "s"(kp.vcol_base[0]));
+    else
+        asm volatile("" ::"s"(kp.c), "s"(kp.vals), "s"(kp.L.cb), "s"(kp.Lseg), "s"(kp.vr), "s"(kp.div_cb.M), "s"(kp.div_Lseg.M), "s"(kp.div_vr.M),
+                     "s"(kp.div_cb.d), "s"(kp.div_Lseg.d), "s"(kp.div_vr.d), "s"(kp.seg_base), "s"(kp.reg_first), "s"(kp.reg_last),
+                     "s"(kp.vcol_base[0]), "s"(kp.n_early), "s"(kp.c_early), "s"(kp.vr_early), "s"(kp.n_late), "s"(kp.div_late.M), "s"(kp.div_late.d));
 #endif
 }
 
@@ -69,26 +86,27 @@ __device__ __forceinline__ void ctd_pin_emit_kernargs(const KParams& kp) {
 // B = true: the batched kernel (cons_jac_batch_kernel) -- the workgroup evaluates member blockIdx.y of the batch: its iterate at
 // xu + blockIdx.y * ldx, its outputs at c + blockIdx.y * ldc, vals + blockIdx.y * ldv (BatchLd, member_out); the tiles, edge
 // blocks and every table are the handle's, shared by the members.  B = false compiles none of it.
-template <class P, int SC, int S, bool DBG, bool B = false>
+// LEAN = true: the lean variant (block_halo, ctd_kernel_body.hpp) -- whole iterate, no early emission; picked by launch_cons_jac.
+template <class P, int SC, int S, bool DBG, bool B = false, bool LEAN = false>
 __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* __restrict__ xu, int block, double* ctd_lds,
                                               const BatchLd bl = BatchLd{}) {
     if constexpr (B) xu += batch_member() * bl.ldx;
-    ctd_pin_kernargs<SC == SC_IRK ? S : 0>(kp, xu);
+    ctd_pin_kernargs<SC == SC_IRK ? S : 0, LEAN>(kp, xu);
     ctd_stamp<DBG>(kp, 0);
     if (DBG && kp.debug_stop == 1) return;
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
     if constexpr (DirectTile<P, SC>::value) {
         // direct driver: no staging of xu, one barrier (see make_direct_ctx); the staged phases below are not instantiated
-        const BlockCtx cx = make_direct_ctx(kp, block, ctd_lds, xu);
-        const EmitPre pre = emit_prefetch<P>(kp, cx, tid, nthr);
+        const BlockCtx cx = make_direct_ctx<LEAN>(kp, block, ctd_lds, xu, LV<P, SC, S, LEAN>::blk(kp), LEAN ? P::NV : -1);
+        const EmitPre pre = emit_prefetch<P, 1, LEAN>(kp, cx, tid, nthr);
         ctd_stamp<DBG>(kp, 1);
-        phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1, B>(kp, cx, tid, nthr, &pre, bl);
-        ctd_pin_emit_kernargs(kp);
+        phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1, B, LEAN>(kp, cx, tid, nthr, &pre, bl);
+        ctd_pin_emit_kernargs<LEAN>(kp);
         __syncthreads();
         ctd_stamp<DBG>(kp, 2);
         ctd_stamp<DBG>(kp, 3);
         if (DBG && kp.debug_stop >= 2 && kp.debug_stop <= 4) return;
-        phase_emit<P, SC, S, 1, B>(kp, cx, tid, nthr, &pre, bl);
+        phase_emit<P, SC, S, 1, B, LEAN>(kp, cx, tid, nthr, &pre, bl);
         ctd_stamp<DBG>(kp, 4);
         if (DBG && kp.stamps) {
             __builtin_amdgcn_s_waitcnt(0);
@@ -97,13 +115,13 @@ __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* _
         }
         return;
     }
-    BlockCtx cx = make_ctx(kp, block, ctd_lds);
+    BlockCtx cx = make_ctx<LEAN>(kp, block, ctd_lds);
     // codes not staged in LDS (long periods): every code the lane will need is fetched now, the latency hidden behind load + eval
     constexpr int NB = EmitN<P, SC, S>::value;
     EmitPreT<NB> pre = {};
     const bool use_pre = !cx.is_edge && !codes_staged(kp);
-    if (use_pre) pre = emit_prefetch<P, NB>(kp, cx, tid, nthr);
-    phase_load<P, SC, S>(kp, cx, xu, tid, nthr);
+    if (use_pre) pre = emit_prefetch<P, NB, LEAN>(kp, cx, tid, nthr);
+    phase_load<P, SC, S, true, LEAN>(kp, cx, xu, tid, nthr);
     // multi-tile workgroups (kp.wg_stride > 0; EXPERIMENT, compiled with -DCTD_MULTI_TILE_LOOP=1 only): this workgroup goes on with
     // block + wg_stride, ... -- the templates, v and the lane's codes stay where they are (the period of the tables is the step:
     // the same for every tile), the x slice of the next tile travels while this one is emitted.  One barrier per tile boundary: it
@@ -117,8 +135,8 @@ __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* _
         __syncthreads();
         ctd_stamp<DBG>(kp, 1);
         if (DBG && kp.debug_stop == 2) return;
-        phase_eval<P, SC, S, false, 1, B>(kp, cx, tid, nthr, nullptr, bl);
-        ctd_pin_emit_kernargs(kp);
+        phase_eval<P, SC, S, false, 1, B, LEAN>(kp, cx, tid, nthr, nullptr, bl);
+        ctd_pin_emit_kernargs<LEAN>(kp);
         __syncthreads();
         ctd_stamp<DBG>(kp, 2);
         if (DBG && kp.debug_stop == 3) return;
@@ -137,10 +155,10 @@ __device__ __forceinline__ void cons_jac_body(const KParams& kp, const double* _
         BlockCtx nx = cx;
         TileIn tin{0.0, 0.0, 0.0};
         if (more) {
-            nx = make_ctx(kp, block, ctd_lds);
+            nx = make_ctx<LEAN>(kp, block, ctd_lds);
             tin = load_issue<P>(kp, nx, xu, tid, nthr);
         }
-        phase_emit_impl<P, SC, S, NB, B>(kp, cx, tid, nthr, pre, use_pre, bl);
+        phase_emit_impl<P, SC, S, NB, B, LEAN>(kp, cx, tid, nthr, pre, use_pre, bl);
         ctd_stamp<DBG>(kp, 4);
         if (!more) break;
         load_commit<P, SC, S>(kp, nx, xu, tin, tid, nthr);
@@ -161,10 +179,10 @@ template <class P, int SC, int S> struct MinWaves {
     static constexpr int value = (P::NX <= 12 && !(SC == SC_MIDPOINT && S > 1)) ? 4 : 1;
 };
 
-template <class P, int SC, int S, bool DBG>
+template <class P, int SC, int S, bool DBG, bool LEAN = false>
 __global__ void __launch_bounds__(P::MAXB, (MinWaves<P, SC, S>::value)) cons_jac_kernel(const KParams kp, const double* __restrict__ xu) {
     extern __shared__ double ctd_lds[];
-    cons_jac_body<P, SC, S, DBG>(kp, xu, (int)blockIdx.x, ctd_lds);
+    cons_jac_body<P, SC, S, DBG, false, LEAN>(kp, xu, (int)blockIdx.x, ctd_lds);
 }
 // K iterates per launch (ctd_cons_jac_batch_dev_async): grid (tiles, members), the same bodies with B = true
 template <class P, int SC, int S>
@@ -681,32 +699,46 @@ hipError_t launch_grad(const GradParams& gp, const double* xu, int grid, hipStre
 // OCP so the registry compiles in parallel, and ctd_engine.hip only sees `extern template` declarations.
 // Five kernel variants per OCP: (trapeze), (midpoint), (Gauss-Legendre s = 1, 2, 3); the stage count is a template
 // parameter so every loop over stages unrolls.
-template <class P, int SC, int S, bool DBG>
+template <class P, int SC, int S, bool DBG, bool LEAN>
 hipError_t launch_variant_dbg(const KParams& kp, const double* xu, int grid, int block, size_t lds_bytes, hipStream_t st,
                               hipEvent_t e0, hipEvent_t e1) {
     if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)cons_jac_kernel<P, SC, S, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute((const void*)cons_jac_kernel<P, SC, S, DBG, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
     // e0/e1 (optional): events recorded by the dispatch itself right before / after THIS kernel, so
     // hipEventElapsedTime(e0, e1) is the kernel's own duration on the stream it was launched on
-    if (e0 || e1) hipExtLaunchKernelGGL((cons_jac_kernel<P, SC, S, DBG>), dim3(grid), dim3(block), lds_bytes, st, e0, e1, 0, kp, xu);
-    else cons_jac_kernel<P, SC, S, DBG><<<grid, block, lds_bytes, st>>>(kp, xu);
+    if (e0 || e1) hipExtLaunchKernelGGL((cons_jac_kernel<P, SC, S, DBG, LEAN>), dim3(grid), dim3(block), lds_bytes, st, e0, e1, 0, kp, xu);
+    else cons_jac_kernel<P, SC, S, DBG, LEAN><<<grid, block, lds_bytes, st>>>(kp, xu);
     return hipGetLastError();
 }
+// Two variants of every instantiation: GENERAL (every mode of the handle) and LEAN (ctd_kernel_body.hpp: block_halo) for the
+// launches that read the whole iterate from one buffer and emit everything behind the barrier -- every single-GPU evaluation
+// unless early emission was asked for.  `lean_ok`: the handle allows the lean variant (env CTD_LEAN=0 at ctd_create forbids it).
 template <class P, int SC, int S>
 hipError_t launch_variant(const KParams& kp, const double* xu, int grid, int block, size_t lds_bytes, hipStream_t st,
-                          hipEvent_t e0, hipEvent_t e1) {
-    if (kp.stamps || kp.debug_stop) return launch_variant_dbg<P, SC, S, true>(kp, xu, grid, block, lds_bytes, st, e0, e1);
-    return launch_variant_dbg<P, SC, S, false>(kp, xu, grid, block, lds_bytes, st, e0, e1);
+                          hipEvent_t e0, hipEvent_t e1, int lean_ok) {
+    const bool dbg = kp.stamps || kp.debug_stop;
+    // The lean variant exists for the direct tiles and for the staged tiles of the Gauss-Legendre schemes, where it measured faster
+    // (profiles/lean_kernel.md).  The staged tiles of the one-point schemes keep the general kernel: the 12-state quadrotor on
+    // midpoint, N = 20 000, measured 15.74 us lean against 15.50; trapeze was not measured.
+    constexpr bool kHasLean = DirectTile<P, SC>::value || SC == SC_IRK;
+    if constexpr (kHasLean) {
+        if (lean_ok && kp.halo == nullptr && kp.n_early == 0) {
+            if (dbg) return launch_variant_dbg<P, SC, S, true, true>(kp, xu, grid, block, lds_bytes, st, e0, e1);
+            return launch_variant_dbg<P, SC, S, false, true>(kp, xu, grid, block, lds_bytes, st, e0, e1);
+        }
+    }
+    if (dbg) return launch_variant_dbg<P, SC, S, true, false>(kp, xu, grid, block, lds_bytes, st, e0, e1);
+    return launch_variant_dbg<P, SC, S, false, false>(kp, xu, grid, block, lds_bytes, st, e0, e1);
 }
 
 template <class P>
 hipError_t launch_cons_jac(const KParams& kp, const double* xu, int grid, int block, size_t lds_bytes, hipStream_t st,
-                           hipEvent_t e0, hipEvent_t e1) {
+                           hipEvent_t e0, hipEvent_t e1, int lean_ok) {
     hipError_t e = hipErrorInvalidValue;       // (midpoint: the template's stage count is control_steps -- 1 in collocation, up to 3 compiled in)
-    for_scheme<true>(kp.L, [&](auto t) { e = launch_variant<P, t.sc, t.s>(kp, xu, grid, block, lds_bytes, st, e0, e1); });
+    for_scheme<true>(kp.L, [&](auto t) { e = launch_variant<P, t.sc, t.s>(kp, xu, grid, block, lds_bytes, st, e0, e1, lean_ok); });
     return e;
 }
 
@@ -759,14 +791,14 @@ hipError_t launch_obj(const ObjParams& op, const double* xu, int grid, int block
 
 #define CTD_INSTANTIATE_LAUNCHERS(P)                                                                                       \
     template hipError_t launch_cons_jac<P>(const KParams&, const double*, int, int, size_t, hipStream_t, hipEvent_t, \
-                                           hipEvent_t);                                                                    \
+                                           hipEvent_t, int);                                                                 \
     template hipError_t launch_cons_jac_batch<P>(const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, int); \
     template hipError_t launch_obj<P>(const ObjParams&, const double*, int, int, hipStream_t, int);                  \
     template int occupancy_cons_jac<P>(const KParams&, int, size_t);                                                 \
     template hipError_t launch_grad<P>(const GradParams&, const double*, int, hipStream_t, int);
 #define CTD_EXTERN_LAUNCHERS(P)                                                                                            \
     extern template hipError_t launch_cons_jac<P>(const KParams&, const double*, int, int, size_t, hipStream_t,      \
-                                                  hipEvent_t, hipEvent_t);                                                 \
+                                                  hipEvent_t, hipEvent_t, int);                                              \
     extern template hipError_t launch_cons_jac_batch<P>(const KParams&, const double*, const BatchLd&, int, int, size_t, hipStream_t, \
                                                         int);                                                                      \
     extern template hipError_t launch_obj<P>(const ObjParams&, const double*, int, int, hipStream_t, int);          \

@@ -243,6 +243,10 @@ inline XNear make_xnear(const XHalo& t, int64_t blk, int64_t N, int64_t v_off) {
 }
 
 // ---- kernel parameters (passed by value) ---------------------------------------------------------------
+// GENERAL-ONLY fields: the lean variant of the constraint / Jacobian kernel (ctd_kernel_body.hpp: block_halo, StaticLayout) never
+// reads halo, near, pos, n_late, n_early, c_early, vr_early, div_late, div_cb, nor -- on its direct-tile path -- L.cu, L.blk,
+// L.cb, L.eqs, L.a, L.b, L.c: it takes those from the static layout of its instantiation.  They stay in the argument block (one
+// layout for both variants, for the batched and iteration kernels and for the run-time OCPs' kernels).
 struct KParams {
     Layout L;
     RecLayout R;
