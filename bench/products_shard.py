@@ -1,7 +1,8 @@
-"""One shard call of the matrix-free products (ctd_*prod_shard_dev_async) of a two-shard split next to the whole-grid call, on one
+"""One shard call of the matrix-free products (ctd_*prod_shard_dev_async, the fused KKT product included) of a two-shard split next to the whole-grid call, on one
 GPU: the first shard's handle (steps [0, N/2), halo entries copied: the buffers hold the whole vectors) against the handle of the
 whole grid, for bench configs 2 and 5.  Context only -- one card says nothing about multi-GPU scaling: the figure to read is how
-close a shard call comes to half the whole-grid time.  Timing as in bench/products.py (median over --rounds of the mean over a
+close a shard call comes to half the whole-grid time.  A library without ctd_kktprod_shard_dev_async (CTD_LIB_PATH: an A/B run
+against an earlier build) gives no kktprod_shard_us.  Timing as in bench/products.py (median over --rounds of the mean over a
 window of at least --window seconds).  Prints one JSON line (and writes it to --out when given).
 
     python bench/products_shard.py [--window 0.2] [--rounds 3] [--out FILE]
@@ -43,6 +44,9 @@ def workload(name, prob, sch, N, window, rounds):
     w = torch.from_numpy(r.uniform(-1, 1, ncon)).cuda()
     oc = torch.empty(ncon, dtype=torch.float64, device="cuda")
     ov = torch.empty(nvar, dtype=torch.float64, device="cuda")
+    sx = torch.from_numpy(r.uniform(0, 1, nvar)).cuda()
+    sc = torch.from_numpy(r.uniform(0, 1e-2, ncon)).cuda()
+    dy = torch.from_numpy(r.uniform(-1, 1, ncon)).cuda()
     fns = {
         "jprod_us": lambda: d.jprod(x, v, out=oc, sync=False),
         "jprod_shard_us": lambda: s.jprod_shard(x, v, oc),
@@ -50,13 +54,16 @@ def workload(name, prob, sch, N, window, rounds):
         "jtprod_shard_us": lambda: s.jtprod_shard(x, w, ov),
         "hprod_us": lambda: d.hprod(x, w, v, 0.7, out=ov, sync=False),
         "hprod_shard_us": lambda: s.hprod_shard(x, w, v, 0.7, ov),
+        "kktprod_us": lambda: d.kktprod(x, w, v, dy, obj_weight=0.7, sx=sx, sc=sc, out=(ov, oc), sync=False),
     }
+    if hasattr(ct._lib.lib(), "ctd_kktprod_shard_dev_async"):
+        fns["kktprod_shard_us"] = lambda: s.kktprod_shard(x, w, v, dy, obj_weight=0.7, sx=sx, sc=sc, out=(ov, oc))
     res = {k: [] for k in fns}
     for _ in range(rounds):
         for k, fn in fns.items():
             res[k].append(1e3 * timed(fn, stream, window))
     out = {k: round(statistics.median(t), 2) for k, t in res.items()}
-    for op in ("jprod", "jtprod", "hprod"):
+    for op in ("jprod", "jtprod", "hprod", "kktprod"):
         out[op + "_half_us"] = round(out[op + "_us"] / 2, 2)
     out.update(name=name, problem=prob, scheme=sch, N=N, shard_steps=[0, N // 2])
     return out

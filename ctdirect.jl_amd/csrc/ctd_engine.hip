@@ -59,7 +59,7 @@ template <class T = double> struct DevBuf {
 };
 
 // the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each, loaded at first use (jit_load)
-enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, JIT_KKT, kJitFamilies };
+enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, JIT_KKT, JIT_KKT_SHARD, kJitFamilies };
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t f[5] = {};        // in the order of the family's name expressions (kJit)
@@ -127,7 +127,7 @@ struct ctd_handle {
     // matrix-free Hessian products (ctd_hprod*): their own partial sums (a graph captured over jtprod keeps its buffer), host-call
     // staging of v and Hv in d_pdir / d_pout and of y in d_y
     DevBuf<> d_hppartial;
-    // matrix-free KKT products (ctd_kktprod*): their own partial sums again; the host call stages x, y, dx and rx as ctd_hprod does
+    // matrix-free KKT products (ctd_kktprod*, the shard call included): their own partial sums again; the host call stages x, y, dx and rx as ctd_hprod does
     // and dy, sx, sc and rc here (nvar / ncon entries)
     DevBuf<> d_kktpartial, d_kdy, d_ksx, d_ksc, d_krc;
     std::string err;
@@ -330,14 +330,16 @@ std::vector<std::string> hprod_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
     return {"ctd::hprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::hprod_finish_kernel<ctd::UserOCP" + sh + ">"};
 }
-std::vector<std::string> jit_kkt_exprs(int sc, int s) {
+std::vector<std::string> kkt_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
-    return {"ctd::kktprod_units_kernel<ctd::UserOCP, " + a + ", " + b + ">", "ctd::kktprod_finish_kernel<ctd::UserOCP>"};
+    return {"ctd::kktprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::kktprod_finish_kernel<ctd::UserOCP" + sh + ">"};
 }
 std::vector<std::string> jit_prod_exprs(int sc, int s) { return prod_exprs(sc, s, ""); }
 std::vector<std::string> jit_hprod_exprs(int sc, int s) { return hprod_exprs(sc, s, ""); }
 std::vector<std::string> jit_prod_shard_exprs(int sc, int s) { return prod_exprs(sc, s, ", true"); }
 std::vector<std::string> jit_hprod_shard_exprs(int sc, int s) { return hprod_exprs(sc, s, ", true"); }
+std::vector<std::string> jit_kkt_exprs(int sc, int s) { return kkt_exprs(sc, s, ""); }
+std::vector<std::string> jit_kkt_shard_exprs(int sc, int s) { return kkt_exprs(sc, s, ", true"); }
 
 // one row per JitFamily: the header, -ffp-contract, the name expressions
 const struct { const char* header; const char* fp_contract; std::vector<std::string> (*exprs)(int sc, int s); } kJit[kJitFamilies] = {
@@ -348,7 +350,8 @@ const struct { const char* header; const char* fp_contract; std::vector<std::str
     {"ctd_hess_kernels.hpp", "fast", jit_hess_exprs},       // hess, hess_finish
     {"ctd_prod_kernels.hpp", "off", jit_prod_shard_exprs},  // the shard forms of jprod, jtprod_units, jtprod_finish
     {"ctd_hprod_kernels.hpp", "off", jit_hprod_shard_exprs},    // ... and of hprod_units, hprod_finish
-    {"ctd_kkt_kernels.hpp", "off", jit_kkt_exprs},          // kktprod_units, kktprod_finish (whole grid only)
+    {"ctd_kkt_kernels.hpp", "off", jit_kkt_exprs},          // kktprod_units, kktprod_finish
+    {"ctd_kkt_kernels.hpp", "off", jit_kkt_shard_exprs},    // ... and their shard forms
 };
 
 // batch: the grid's second dimension (members of a batched launch)
@@ -1461,14 +1464,16 @@ int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_we
 }
 
 // ---- matrix-free KKT products: rx = (sigma H_f + sum y_r H_{c_r}) dx + J' dy + sx o dx, rc = J dx - sc o dy ------------------
-// ctd_kkt_kernels.hpp.  Checks in the order of prod_check: handle, device, whole-grid handle (there is no shard form), the
-// required pointers, then the outputs against every input and against each other.
+// ctd_kkt_kernels.hpp.  Checks in the order of prod_check: handle, device, whole-grid handle (not for the shard call, which takes
+// every handle), the required pointers, then the outputs against every input and against each other.
 static int32_t kktprod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* y, const double* dx,
-                             const double* dy, const double* sx, const double* sc, const double* rx, const double* rc) {
+                             const double* dy, const double* sx, const double* sc, const double* rx, const double* rc,
+                             bool shard = false) {
     if (on.st) return on.st;
-    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; the shard form of the KKT product "
-                                   "(step_begin / step_end, ctd_set_x_shards) is out of scope");
+    if (!shard && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
+                                   "step_end, ctd_set_x_shards) is out of scope for this call: a shard handle calls "
+                                   "ctd_kktprod_shard_dev_async");
     if (!x || !dx || !dy || !rx || !rc) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (x, dx, dy, rx and rc are required)");
     for (const double* in : {x, y, dx, dy, sx, sc})
         if (in && (in == rx || in == rc)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
@@ -1477,9 +1482,11 @@ static int32_t kktprod_check(const OnDevice& on, ctd_handle* h, const char* fn, 
 }
 
 static int32_t enqueue_kktprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
-                               const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
-    const char* fn = "ctd_kktprod";
-    if (const int32_t st = jit_load(h, JIT_KKT)) return st;
+                               const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev,
+                               bool shard = false) {
+    const char* fn = shard ? "ctd_kktprod_shard_dev_async" : "ctd_kktprod";
+    const JitFamily fam = shard ? JIT_KKT_SHARD : JIT_KKT;
+    if (const int32_t st = jit_load(h, fam)) return st;
     const Layout& L = h->model.L;
     KktParams kp;
     std::memset(&kp, 0, sizeof(kp));
@@ -1493,11 +1500,11 @@ static int32_t enqueue_kktprod(ctd_handle* h, const double* x_dev, const double*
     kp.sx = sx_dev;
     kp.sc = sc_dev;
     kp.rc = rc_dev;
-    prod_units(h, kp.h.p, false);
+    prod_units(h, kp.h.p, shard);
     int jc = 1;         // the fused lanes keep the hprod chunk rule (profiles/kktprod_resources.md)
     if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
     for_problem(h->model.problem, [&](auto tag) { jc = HProdDirs<typename decltype(tag)::type>::JC; });
-    return enqueue_prod_units<KktKernels>(h, fn, kp, hprod_dirs_per_node(L), jc, h->d_kktpartial, h->jit[JIT_KKT], 0, x_dev, false);
+    return enqueue_prod_units<KktKernels>(h, fn, kp, hprod_dirs_per_node(L), jc, h->d_kktpartial, h->jit[fam], 0, x_dev, shard);
 }
 
 int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
@@ -1505,6 +1512,15 @@ int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* 
     const OnDevice on(h, "ctd_kktprod_dev_async");
     const int32_t st = kktprod_check(on, h, "ctd_kktprod_dev_async", x_dev, y_dev, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
     return st ? st : enqueue_kktprod(h, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
+}
+
+// the shard's own entries of rx (+ its partial sums of d/dv) and its own rows of rc (see include/ctdirect_hip.h)
+int32_t ctd_kktprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                                    const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
+    const OnDevice on(h, "ctd_kktprod_shard_dev_async");
+    const int32_t st = kktprod_check(on, h, "ctd_kktprod_shard_dev_async", x_dev, y_dev, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev,
+                                     true);
+    return st ? st : enqueue_kktprod(h, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev, true);
 }
 
 // host pointers: x, y, dx and rx staged as for ctd_hprod; dy, sx, sc and rc through buffers of their own

@@ -342,6 +342,51 @@ class ShardedDOCP:
             return pack, dst, src
         return self._exchange(w, "con", build)
 
+    def exchange_kkt_halo(self, dx, dy):
+        """`exchange_product_halo(dx)` and `exchange_product_rows(dy)` in ONE all-gather of (halo_w + blk + n) + (cb + tail) doubles
+        per rank: the two halves of a Krylov vector -- usually one buffer -- need their halos at the same moment, once per inner
+        iteration, and a second collective would cost a second latency.  Fills exactly the read sets of
+        ctd_kktprod_shard_dev_async (include/ctdirect_hip.h) inside the full-length dx (variable layout) and dy (constraint
+        layout); returns (dx, dy)."""
+        if self.world == 1 and not _FORCE:
+            return dx, dy
+        ent = self._phalo.get(("kkt", dx.device))
+        if ent is None:
+            w, n, blk, N, cb = self.halo_w, self.n, self.blk, self.N, self.cb
+            eqs = self.docp.discretization._state_stage_eqs_block
+            p = cb - eqs
+            tail = self.docp.dim_NLP_constraints - N * cb
+            Lx = w + blk + n
+            L = Lx + p + eqs + tail
+            (b, e), r, G, ar = self.steps, self.rank, self.world, torch.arange
+            # my first node | last block | final state || my first node's path rows | last step's state / stage rows | tail
+            pack_x = [b * blk + ar(w), (e - 1) * blk + ar(blk), N * blk + ar(n)]
+            pack_c = [b * cb + eqs + ar(p), (e - 1) * cb + ar(eqs), N * cb + ar(tail)]
+            dst_x, src_x, dst_c, src_c = [], [], [], []
+            if r > 0:
+                dst_x += [ar(n), (b - 1) * blk + ar(blk)]
+                src_x += [ar(n), (r - 1) * L + w + ar(blk)]
+                dst_c.append((b - 1) * cb + ar(eqs))
+                src_c.append((r - 1) * L + Lx + p + ar(eqs))
+            if r + 1 < G:
+                dst_x += [e * blk + ar(w), N * blk + ar(n)]
+                src_x += [(r + 1) * L + ar(w), (G - 1) * L + w + blk + ar(n)]
+                dst_c += [e * cb + eqs + ar(p), N * cb + ar(tail)]
+                src_c += [(r + 1) * L + Lx + ar(p), (G - 1) * L + Lx + p + eqs + ar(tail)]
+            cat = lambda parts: (torch.cat(parts) if parts else torch.zeros(0, dtype=torch.long)).to(dx.device)      # noqa: E731
+            ent = self._phalo[("kkt", dx.device)] = (cat(pack_x), cat(pack_c), cat(dst_x), cat(src_x), cat(dst_c), cat(src_c), Lx,
+                                                     torch.zeros(L, dtype=torch.float64, device=dx.device),
+                                                     torch.zeros(G * L, dtype=torch.float64, device=dx.device))
+        pack_x, pack_c, dst_x, src_x, dst_c, src_c, Lx, send, recv = ent
+        torch.index_select(dx, 0, pack_x, out=send[:Lx])
+        torch.index_select(dy, 0, pack_c, out=send[Lx:])
+        _all_gather_into(recv, send, self.group)
+        if dst_x.numel():
+            dx.index_copy_(0, dst_x, recv.index_select(0, src_x))
+        if dst_c.numel():
+            dy.index_copy_(0, dst_c, recv.index_select(0, src_c))
+        return dx, dy
+
     def enable_peer_x(self, x):
         """Sharded iterate read IN PLACE (`ctd_set_x_shards`): every rank exports its full-length x buffer once (IPC handle,
         all-gathered as Python objects -- set-up, not the step), maps the other ranks' buffers, and from then on this rank's
@@ -554,6 +599,22 @@ class ShardedDOCP:
             self.exchange_product_rows(y)
         self.docp.hprod_shard(x, y, v, obj_weight, out)
         return self._reduce_tail(out)
+
+    def kktprod(self, x, y, dx, dy, obj_weight, sx, sc, out, x_halo_valid=False, y_halo_valid=False):
+        """The fused KKT product (`DOCP.kktprod`) of the sharded transcription: into the full-length pair `out` = (rx, rc) go the
+        entries of rx of this rank's own variables, the v entries all-reduced (nv doubles) on every rank, and this rank's rows of rc;
+        everything else is left untouched.  Every tensor is full-length with this rank's own entries valid (x, dx: + the nv tail; sx:
+        the nv tail on the last rank only; y, sx, sc may be None).  The halos of dx and dy are exchanged here with ONE all-gather
+        (`exchange_kkt_halo`) and written INTO them; x as in `jprod` (`x_halo_valid`); y's halo rows are exchanged
+        (`exchange_product_rows`) unless `y_halo_valid` -- y, like x, is fixed over the inner iterations of one outer step.  With x
+        read in place (or valid) and y valid, a Krylov iteration costs two launches, one all-gather and one all-reduce."""
+        self._product_x(x, "kktprod", x_halo_valid)
+        if y is not None and not y_halo_valid:
+            self.exchange_product_rows(y)
+        self.exchange_kkt_halo(dx, dy)
+        self.docp.kktprod_shard(x, y, dx, dy, obj_weight, sx, sc, out)
+        self._reduce_tail(out[0])
+        return out
 
     def obj(self, x, as_tensor=False):
         """Objective of the whole transcription: the shards' partial sums added with one all-reduce of one double that never

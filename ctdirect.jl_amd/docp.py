@@ -520,7 +520,8 @@ class DOCP:
         in two kernel launches (`ctd_kktprod*`).  y = None: all multipliers zero; sx / sc = None: no diagonal term.  Returns
         (rx, rc); `out` is a pair (rx, rc), which may be two slices of one tensor, as may dx and dy.  The Hessian and the Jacobian
         are the structural ones (see `hprod`, `jprod`).  NumPy inputs use the host entry point; device tensors are enqueued on
-        the handle's stream (`ctd_kktprod_dev_async`), followed by a sync when `sync`.  Whole-grid handles only."""
+        the handle's stream (`ctd_kktprod_dev_async`), followed by a sync when `sync`.  Whole-grid handles only: a shard handle
+        calls `kktprod_shard`."""
         nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
         L = _lib.lib()
         self._check_x(x)
@@ -604,6 +605,35 @@ class DOCP:
         if sync:
             self.sync()
         return out
+
+    def kktprod_shard(self, x, y, dx, dy, obj_weight=1.0, sx=None, sc=None, out=None, sync=False):
+        """`ctd_kktprod_shard_dev_async`: `kktprod` on THIS shard, device tensors only.  Into the full-length pair `out` = (rx, rc)
+        (allocated, uninitialised elsewhere, when None) go the entries of rx of the shard's own variables, + the shard's partial sums
+        in the nv tail entries (the caller adds them over the shards; sx * dx of those entries is in the last shard's), and the
+        shard's own rows of rc (the last shard: also the final path and boundary rows); nothing else is touched.  x is read through
+        the table of `set_x_shards` when one is set, otherwise from x itself (halos copied in); y, dx, dy, sx and sc are always read
+        from the tensors passed.  include/ctdirect_hip.h lists the entries read.  Returns (rx, rc)."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        self._check_x(x)
+        rx, rc = (None, None) if out is None else out
+        sizes = (("y", y, ncon), ("dx", dx, nvar), ("dy", dy, ncon), ("sx", sx, nvar), ("sc", sc, ncon), ("out[0]", rx, nvar),
+                 ("out[1]", rc, ncon))
+        for name, a, n in sizes:
+            if a is None and name in ("dx", "dy"):
+                raise ValueError(f"{name} is required")
+            if a is not None and a.numel() != n:
+                raise ValueError(f"{name} has {a.numel()} entries, expected {n}")
+        if rx is None or rc is None:
+            import torch
+            rx = torch.empty(nvar, dtype=torch.float64, device=x.device) if rx is None else rx
+            rc = torch.empty(ncon, dtype=torch.float64, device=x.device) if rc is None else rc
+        p = {name: None if a is None else self._dev_ptr(a, n, name) for name, a, n in sizes[:5]}
+        self._ck(_lib.lib().ctd_kktprod_shard_dev_async(self._h, self._dev_ptr(x, nvar, "x"), p["y"], float(obj_weight), p["dx"],
+                                                        p["dy"], p["sx"], p["sc"], self._dev_ptr(rx, nvar, "out[0]"),
+                                                        self._dev_ptr(rc, ncon, "out[1]")))
+        if sync:
+            self.sync()
+        return rx, rc
 
     def eval_all(self, x, y=None, obj_weight=1.0, f=None, g=None, c=None, vals=None, hvals=None, sync=False):
         """One solver iteration in one call (`ctd_eval_all_dev_async`): objective -> f[0], gradient -> g, constraints -> c,

@@ -432,10 +432,10 @@ int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_
  * stages its eight vectors through buffers the handle owns.
  * Run-time OCPs (ctd_register_ocp) compile their KKT kernels on the first ctd_kktprod* call: make one call before capturing a
  * graph.
- * OUT OF SCOPE: the shard form (a shard handle is refused; there is no ShardedDOCP.kktprod), a batched form, several right-hand
- * sides per call, and any preconditioner.
+ * OUT OF SCOPE: a batched form, several right-hand sides per call, and any preconditioner.
  * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE, whatever the other arguments; shard handle
- * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL; null x, dx, dy, rx or rc -> CTD_EINVAL;
+ * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (a shard handle calls
+ * ctd_kktprod_shard_dev_async below); null x, dx, dy, rx or rc -> CTD_EINVAL;
  * an output equal to any input, or rx == rc -> CTD_EINVAL.  ctd_last_error names the reason. */
 /* host pointers: returns when rx, rc are in the caller's buffers */
 int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* dx, const double* dy,
@@ -458,22 +458,34 @@ int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* 
  *           [v_off, nvar) with the shard's PARTIAL sums of d/dv: the caller adds them over the shards (one all-reduce of nv
  *           doubles).  The boundary rows' and the Mayer term's contributions go to X_1 on the first shard, to X_{N+1} and to v on
  *           the last one (the convention of ctd_grad_shard_dev_async).
- * On a whole-grid handle each call is bit-identical to its *_dev_async counterpart.
+ *   kktprod rx: the entries of jtprod / hprod above, the nv entries again the shard's PARTIAL sums, which the caller adds over the
+ *           shards (one all-reduce of nv doubles); sx o dx of the v entries is in the last shard's partial sum only.  rc: the rows
+ *           of jprod above.
+ * On a whole-grid handle each call is bit-identical to its *_dev_async counterpart (kktprod: the v entries included).
  * READS of x: through the table of ctd_set_x_shards when one is set (the call contains no exchange); otherwise from x_dev, whose
- * halo entries must have been copied in.  The directions v, w and y are ALWAYS read from the pointer passed: their halo entries
- * are the caller's to fill (as for y of the sharded ctd_hess_coord).  Upper bounds of what a call reads -- nothing outside them is
- * read, so those entries need not be valid:
- *   variable layout (x without a table, v):  the shard's own entries (as in the write set above); [v_off, nvar); the whole block
- *     sb - 1 if sb > 0; if se < N the first n entries of block se, plus the m controls behind them on the trapeze; [0, n) and
- *     [N blk, N blk + n);
- *   constraint layout (w, y):  the shard's own rows (the tail included on the last shard); the eqs state / stage rows of step
- *     sb - 1 if sb > 0; the p path rows of node se, [se cb + eqs, (se + 1) cb), if se < N; the tail [N cb, ncon).
+ * halo entries must have been copied in.  The directions v, w and y (kktprod: dx, dy, y, sx and sc) are ALWAYS read from the
+ * pointer passed: their halo entries are the caller's to fill (as for y of the sharded ctd_hess_coord).  Upper bounds of what a
+ * call reads -- nothing outside them is read, so those entries need not be valid:
+ *   variable layout (x without a table, v; kktprod: dx):  the shard's own entries (as in the write set above); [v_off, nvar); the
+ *     whole block sb - 1 if sb > 0; if se < N the first n entries of block se, plus the m controls behind them on the trapeze;
+ *     [0, n) and [N blk, N blk + n);
+ *   constraint layout (w, y; kktprod: dy):  the shard's own rows (the tail included on the last shard); the eqs state / stage rows
+ *     of step sb - 1 if sb > 0; the p path rows of node se, [se cb + eqs, (se + 1) cb), if se < N; the tail [N cb, ncon);
+ *   the diagonals of kktprod:  sx the shard's own variable entries, on the last shard also [v_off, nvar); sc the shard's own rows.
  * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; null pointers (y_dev may be NULL: objective
  * only) -> CTD_EINVAL; an output that equals an input -> CTD_EINVAL. */
 int32_t ctd_jprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev);
 int32_t ctd_jtprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev);
 int32_t ctd_hprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
                                   double* Hv_dev);
+/* ctd_kktprod_dev_async on a shard: the same arguments with the same meaning (y_dev, sx_dev, sc_dev may be NULL), two launches, the
+ * partial-sum buffer of ctd_kktprod* (not hprod's or jtprod's).  A Krylov iteration of a sharded solver costs these two launches, one exchange of the halos of
+ * (dx, dy) and one all-reduce of nv doubles; x (read in place or with its halo copied once) and y (its halo rows copied once) do not
+ * change over the inner iterations of one outer step.
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; null x, dx, dy, rx or rc -> CTD_EINVAL; an
+ * output equal to any input, or rx == rc -> CTD_EINVAL. */
+int32_t ctd_kktprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                                    const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev);
 
 /* 1-based (rows[k], cols[k]), k < nnzh, CSC order */
 int32_t ctd_hess_structure(const ctd_handle* h, int64_t* rows, int64_t* cols);

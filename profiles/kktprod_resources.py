@@ -1,11 +1,12 @@
 """Regenerates profiles/kktprod_resources.md: registers, scratch and occupancy of every kktprod_units_kernel instantiation of the
-registry beside the hprod_units_kernel of the same (problem, scheme), from the compiler's own remarks (no GPU needed).
+registry -- whole grid and shard form -- beside the hprod_units_kernel of the same (problem, scheme), from the compiler's own
+remarks (no GPU needed).
 
     python profiles/kktprod_resources.py [--jobs 8]
 
 Each csrc/ctd_pkern_<problem>.hip is compiled for the device only with -Rpass-analysis=kernel-resource-usage.  The hprod kernels'
 source is what it was before the fused product was added, and their figures are checked against profiles/hprod_resource_usage.log.
-The script fails if a fused instantiation uses scratch where the hprod instantiation uses none."""
+The script fails if a fused instantiation, of either form, uses scratch where the hprod instantiation uses none."""
 import argparse
 import os
 import re
@@ -27,7 +28,8 @@ FIELDS = (("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"S
 
 
 def remarks(stem):
-    """{(kernel, scheme class, stages): figures} of the whole-grid unit kernels of one problem"""
+    """{(kernel, scheme class, stages): figures} of the unit kernels of one problem; the shard form of the fused kernel is
+    "kktprod_shard", the shard form of hprod is left out"""
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
                         "-Rpass-analysis=kernel-resource-usage", "-c", f"ctd_pkern_{stem}.hip", "-o", os.devnull],
                        cwd=CSRC, capture_output=True, text=True)
@@ -41,7 +43,8 @@ def remarks(stem):
             k = re.search(r"\d+(kktprod|hprod)_units_kernel", name)
             t = re.search(r"ELi(\d+)ELi(\d+)E", name)
             shard = bool(re.search(r"Lb1EE+v", name))
-            cur = {"key": (k.group(1), int(t.group(1)), int(t.group(2)))} if k and t and not shard else None
+            kind = k.group(1) + ("_shard" if shard else "") if k else None
+            cur = {"key": (kind, int(t.group(1)), int(t.group(2)))} if k and t and kind != "hprod_shard" else None
             continue
         if cur is None:
             continue
@@ -78,18 +81,20 @@ def main():
     rows = []
     for stem, name in PROBLEMS:
         for i, (sc, s) in enumerate(sorted(SCHEMES)):
-            h, k = table[stem][("hprod", sc, s)], table[stem][("kktprod", sc, s)]
+            h, k, ks = table[stem][("hprod", sc, s)], table[stem][("kktprod", sc, s)], table[stem][("kktprod_shard", sc, s)]
             assert (h["vgpr"], h["agpr"], h["scratch"], h["waves"]) == log[name][i], (name, sc, s, h, log[name][i])
             assert k["scratch"] == 0 or h["scratch"] > 0, (name, sc, s, k)
-            rows.append(f"| {name} | {SCHEMES[(sc, s)]} | {fmt(k)} | {fmt(h)} |\n")
+            assert ks["scratch"] == 0 or h["scratch"] > 0, (name, sc, s, "shard form", ks)
+            rows.append(f"| {name} | {SCHEMES[(sc, s)]} | {fmt(k)} | {fmt(ks)} | {fmt(h)} |\n")
     path = os.path.join(ROOT, "profiles", "kktprod_resources.md")
     with open(path) as f:
         text = f.read()
     head = text[:text.index("| problem |")]
     with open(path, "w") as f:
         f.write(head)
-        f.write("| problem | scheme | kktprod VGPR + AGPR | scratch B/lane | waves/SIMD | hprod VGPR + AGPR | scratch B/lane | waves/SIMD |\n")
-        f.write("|---|---|---|---|---|---|---|---|\n")
+        f.write("| problem | scheme | kktprod VGPR + AGPR | scratch B/lane | waves/SIMD | shard form VGPR + AGPR | scratch B/lane | "
+                "waves/SIMD | hprod VGPR + AGPR | scratch B/lane | waves/SIMD |\n")
+        f.write("|---|---|---|---|---|---|---|---|---|---|---|\n")
         f.writelines(rows)
     print(path, len(rows), "instantiations")
 
