@@ -107,6 +107,13 @@ SYMBOLS = {
     "ctd_hprod_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),
     "ctd_kktprod": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ctd_kktprod_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # matrix-free KKT diagonals: diag(H), row sums and column sums of J o J
+    "ctd_hdiag": (C.c_int32, [_vp, _dp, _dp, C.c_double, _dp]),
+    "ctd_hdiag_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp]),
+    "ctd_jsq_rows": (C.c_int32, [_vp, _dp, _dp, _dp]),
+    "ctd_jsq_rows_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "ctd_jsq_cols": (C.c_int32, [_vp, _dp, _dp, _dp]),
+    "ctd_jsq_cols_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

@@ -1,0 +1,5 @@
+// Matrix-free KKT diagonal kernels (ctd_diag_kernels.hpp: hdiag, jsq_rows, jsq_cols) of one registry entry (GoddardAllOCP).
+#include "ctd_diag_kernels.hpp"
+namespace ctd {
+CTD_INSTANTIATE_DIAG(GoddardAllOCP)
+}

@@ -432,7 +432,8 @@ int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_
  * stages its eight vectors through buffers the handle owns.
  * Run-time OCPs (ctd_register_ocp) compile their KKT kernels on the first ctd_kktprod* call: make one call before capturing a
  * graph.
- * OUT OF SCOPE: a batched form, several right-hand sides per call, and any preconditioner.
+ * OUT OF SCOPE: a batched form and several right-hand sides per call.  The diagonals a scaling preconditioner of this operator
+ * is built from are ctd_hdiag, ctd_jsq_rows and ctd_jsq_cols below; block and Riccati-type preconditioners are not provided.
  * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE, whatever the other arguments; shard handle
  * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (a shard handle calls
  * ctd_kktprod_shard_dev_async below); null x, dx, dy, rx or rc -> CTD_EINVAL;
@@ -443,6 +444,37 @@ int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_
 /* device pointers on the handle's device: enqueue-only on the handle's stream (ctd_sync waits), capturable after one warm call */
 int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
                               const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev);
+
+/* Matrix-free diagonals of the blocks of the KKT matrix K = [[H + Sx, J'], [J, -Sc]] at (x, y): what a first-level (scaling)
+ * preconditioner of ctd_kktprod is built from, and the row / column norms of J that gradient-based NLP scaling uses.  There is no
+ * NLPModels counterpart; without them the only route is ctd_hess_coord + ctd_jac_coord, the assembly the products avoid.
+ *   ctd_hdiag:     Hd_j  = (obj_weight H_f(x) + sum_r y_r H_{c_r}(x))_jj     (nvar entries; y == NULL: objective only, bit-identical
+ *                                                                            to a zero vector)
+ *   ctd_jsq_rows:  out_r = sum_j wx_j J_rj^2 = diag(J diag(wx) J')_r          (ncon entries; wx: nvar weights, NULL = ones)
+ *   ctd_jsq_cols:  out_j = sum_r wc_r J_rj^2 = diag(J' diag(wc) J)_j          (nvar entries; wc: ncon weights, NULL = ones)
+ * NULL weights are bit-identical to a vector of ones.  H and J are the structural ones, exactly as documented for ctd_hprod and
+ * ctd_jprod above: entries a REFERENCE_MANUAL pattern drops and the terms through a free t0 / tf are included, kinks follow the
+ * conventions of ctd_hess_coord.  A scaling preconditioner of K: px = |Hd + sx|, pc = jsq_rows(x, 1 / px) + sc, M = diag(1/px, 1/pc)
+ * -- it needs |Hd_j + sx_j| away from zero, and it is no constraint preconditioner.
+ * hdiag and jsq_cols are two kernel launches (a unit pass and a finish), jsq_rows is one.  Results are reproducible bit for bit
+ * (fixed summation order, no floating-point atomics) and equal for every pattern_mode / value_order of one transcription.  No
+ * device memory proportional to nnzj or nnzh is allocated, nothing is assembled; hdiag and jsq_cols each have a partial-sum buffer
+ * of their own (one row of kMaxNV doubles per workgroup), so a graph captured over any other product keeps its buffer; the host
+ * calls stage x, y / the weights and the result through buffers the handle owns.
+ * Run-time OCPs (ctd_register_ocp) compile these kernels -- one family for the three calls -- on the first of these calls: make one
+ * call before capturing a graph.
+ * OUT OF SCOPE: the shard form, batched forms, row / column max-norms.
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE, whatever the other arguments; shard handle
+ * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL; null x or output -> CTD_EINVAL; an output
+ * equal to an input -> CTD_EINVAL.  ctd_last_error names the reason. */
+/* host pointers: return when the result is in the caller's buffer */
+int32_t ctd_hdiag(ctd_handle* h, const double* x, const double* y, double obj_weight, double* Hd);
+int32_t ctd_jsq_rows(ctd_handle* h, const double* x, const double* wx, double* out);
+int32_t ctd_jsq_cols(ctd_handle* h, const double* x, const double* wc, double* out);
+/* device pointers on the handle's device: enqueue-only on the handle's stream (ctd_sync waits), capturable after one warm call */
+int32_t ctd_hdiag_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev);
+int32_t ctd_jsq_rows_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev);
+int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev);
 
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
