@@ -62,6 +62,9 @@ def main():
     for n in names:
         a, b = sorted(res[libs[0]][n])[1], sorted(res[libs[1]][n])[1]
         print(f"{n:28s} {a:9.2f} {b:9.2f}   {b / a:5.3f}")
+    print("every repetition, in the order taken (us):")
+    for n in names:
+        print(f"{n:28s} A " + " ".join(f"{v:.2f}" for v in res[libs[0]][n]) + "   B " + " ".join(f"{v:.2f}" for v in res[libs[1]][n]))
 
 
 if __name__ == "__main__":

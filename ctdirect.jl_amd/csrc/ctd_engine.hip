@@ -490,6 +490,15 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
             for_scheme<true>(mo.L, [&](auto t) { bad = static_layout_mismatch<P, t.sc, t.s>(mo.L); });
         });
         if (bad) return fail(nullptr, CTD_EINVAL, std::string("ctd_create: the static layout of the kernel instantiation differs from the model's layout in field '") + bad + "'");
+        // The static-emit form of the lean kernel also takes the periods of the output streams (manual pattern, CSC order) from its
+        // instantiation (StaticEmit, ctd_emit_static.hpp): the same check, the same refusal.
+        if (mo.pattern_mode == 0 && mo.order == 0) {
+            for_problem(mo.problem, [&](auto tag) {
+                using P = typename decltype(tag)::type;
+                for_scheme<true>(mo.L, [&](auto t) { bad = static_emit_mismatch<P, t.sc, t.s>(mo.L, mo.Lseg, mo.vr); });
+            });
+            if (bad) return fail(nullptr, CTD_EINVAL, std::string("ctd_create: the static emit geometry of the kernel instantiation differs from the model's in '") + bad + "'");
+        }
     }
     if (mo.L.cs > 3 && desc->device >= 0 && !runtime_ocp(mo.problem))      // (host-only handles -- sizes, bounds, patterns -- take any)
         return fail(nullptr, CTD_EINVAL, "ctd_create: control_steps > 3 needs an OCP registered at run time (ctd_register_ocp); the compiled registry holds the midpoint kernels for 1, 2 and 3 controls per step");
@@ -500,6 +509,10 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
         return fail(nullptr, CTD_EINVAL, "ctd_create: shard [step_begin, step_end) is not inside [0, N)");
     h->tile = env_int("CTD_TILE", 0);
     h->lean_ok = env_int("CTD_LEAN", 1) ? 1 : 0;
+    // bit 1: the static-emit form of the lean kernel (launch_variant) -- registry OCPs, manual pattern in CSC order, the whole grid
+    if (h->lean_ok && env_int("CTD_STATIC_EMIT", 1) && !runtime_ocp(mo.problem) && mo.pattern_mode == 0 && mo.order == 0 &&
+        h->step_begin == 0 && h->step_end == mo.L.N)
+        h->lean_ok |= 2;
     if (h->tile <= 0) h->tile = default_tile(mo, h->step_end - h->step_begin);
     int maxb = 256;
     for_problem(mo.problem, [&](auto tag) { maxb = decltype(tag)::type::MAXB; });
@@ -590,6 +603,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     h->kp.debug_stop = debug_stop;
     h->out_mb = 8.0 * ((double)(h->step_end - h->step_begin) * (mo.L.cb + mo.Lseg + (double)mo.L.nv * mo.vr)) / 1.0e6;
     h->kp.wt_store = h->out_mb <= kWtMB ? 1 : 0;
+    if (const int wt = env_int("CTD_WT_STORE", -1); wt >= 0) h->kp.wt_store = wt ? 1 : 0;      // (tests: either store flavour on any grid)
     h->device = desc->device;
     if (h->device >= 0) {
         int ndev = 0;

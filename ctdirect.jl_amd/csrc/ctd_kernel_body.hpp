@@ -1880,6 +1880,9 @@ CTD_HD void phase_emit(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
 
 }  // namespace ctd
 
+// the tile's emit phase with a static geometry (manual pattern, CSC order: the static variant of the lean kernel)
+#include "ctd_emit_static.hpp"
+
 // symbolic functions of the registry problems (generated at build time; run-time OCPs carry theirs in the functor)
 #if !defined(__HIPCC_RTC__)
 #include "ctd_problems.hpp"

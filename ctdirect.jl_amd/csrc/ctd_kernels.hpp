@@ -184,6 +184,51 @@ __global__ void __launch_bounds__(P::MAXB, (MinWaves<P, SC, S>::value)) cons_jac
     extern __shared__ double ctd_lds[];
     cons_jac_body<P, SC, S, DBG, false, LEAN>(kp, xu, (int)blockIdx.x, ctd_lds);
 }
+// The STATIC-EMIT variant of the lean kernel (ctd_emit_static.hpp): direct tiles whose emit periods are the static ones of
+// <P, SC, S> (manual pattern, CSC order, whole grid), launched with NTHR lanes; WT: the emit phase's stores are write-through
+// (KParams::wt_store as a constant).  The body is chosen ONCE at entry: the edge workgroups run the lean body as it is, so the
+// tile's path -- pin, prefetch, evaluation, barrier, emit -- is one contiguous run of code with the workgroup size a constant.
+// Behind the barrier the tile reads no kernel argument that was not pinned in front of it.
+template <class P, int SC, int S, bool DBG, int NTHR, bool WT>
+__device__ __forceinline__ void cons_jac_static_body(const KParams& kp, const double* __restrict__ xu, int block, double* ctd_lds) {
+    if (__builtin_expect(block < kp.has_edge, 0)) {
+        cons_jac_body<P, SC, S, DBG, false, true>(kp, xu, block, ctd_lds);
+        return;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" ::"s"(kp.has_edge), "s"(kp.T), "s"(kp.HL), "s"(kp.HH), "s"(kp.step_begin), "s"(kp.step_end), "s"(kp.L.N),
+                 "s"(kp.L.v_off), "s"(kp.L.stagewise), "s"(kp.L.euler), "s"(kp.tau), "s"(kp.L.t0), "s"(kp.L.tf), "s"(xu),
+                 "s"(kp.tmpl), "s"(kp.vtmpl));
+#endif
+    ctd_stamp<DBG>(kp, 0);
+    if (DBG && kp.debug_stop == 1) return;
+    const int tid = (int)threadIdx.x;
+    BlockCtx cx = make_direct_ctx<true>(kp, block, ctd_lds, xu, LV<P, SC, S, true>::blk(kp), P::NV);
+    cx.is_edge = 0;          // (this arm)
+    cx.edge_part = 0;
+    const EmitPre pre = emit_prefetch_static<P, SC, S, NTHR>(kp, tid);
+    ctd_stamp<DBG>(kp, 1);
+    phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1, false, true>(kp, cx, tid, NTHR, &pre, BatchLd{});
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" ::"s"(kp.c), "s"(kp.vals), "s"(kp.seg_base), "s"(kp.reg_first), "s"(kp.reg_last), "s"(kp.vcol_base[0]));
+#endif
+    __syncthreads();
+    ctd_stamp<DBG>(kp, 2);
+    ctd_stamp<DBG>(kp, 3);
+    if (DBG && kp.debug_stop >= 2 && kp.debug_stop <= 4) return;
+    phase_emit_static<P, SC, S, NTHR, WT>(kp, cx, tid, pre);
+    ctd_stamp<DBG>(kp, 4);
+    if (DBG && kp.stamps) {
+        __builtin_amdgcn_s_waitcnt(0);
+        __syncthreads();
+        ctd_stamp<DBG>(kp, 5);
+    }
+}
+template <class P, int SC, int S, bool DBG, int NTHR, bool WT>
+__global__ void __launch_bounds__(NTHR, (MinWaves<P, SC, S>::value)) cons_jac_static_kernel(const KParams kp, const double* __restrict__ xu) {
+    extern __shared__ double ctd_lds[];
+    cons_jac_static_body<P, SC, S, DBG, NTHR, WT>(kp, xu, (int)blockIdx.x, ctd_lds);
+}
 // K iterates per launch (ctd_cons_jac_batch_dev_async): grid (tiles, members), the same bodies with B = true
 template <class P, int SC, int S>
 __global__ void __launch_bounds__(P::MAXB, (MinWaves<P, SC, S>::value)) cons_jac_batch_kernel(const KParams kp, const double* __restrict__ xu,
@@ -716,10 +761,43 @@ hipError_t launch_variant_dbg(const KParams& kp, const double* xu, int grid, int
 // Two variants of every instantiation: GENERAL (every mode of the handle) and LEAN (ctd_kernel_body.hpp: block_halo) for the
 // launches that read the whole iterate from one buffer and emit everything behind the barrier -- every single-GPU evaluation
 // unless early emission was asked for.  `lean_ok`: the handle allows the lean variant (env CTD_LEAN=0 at ctd_create forbids it).
+// The static-emit variant of the lean kernel for NTHR lanes, when <P, SC, S> has one (StaticEmit::built) and the handle's periods are
+// the static ones; `done`: it was launched (else the caller goes on with the lean / general kernel)
+template <class P, int SC, int S, int NTHR>
+hipError_t launch_static(const KParams& kp, const double* xu, int grid, size_t lds_bytes, hipStream_t st, hipEvent_t e0, hipEvent_t e1,
+                         bool dbg, bool& done) {
+    done = false;
+    if constexpr (StaticEmit<P, SC, S>::template built<NTHR>()) {
+        using SE = StaticEmit<P, SC, S>;
+        if (kp.Lseg != SE::Lseg || kp.vr != SE::vr || (SC == SC_IRK && S >= 2 && !kp.L.stagewise)) return hipSuccess;
+        done = true;
+        auto go = [&](auto kern) -> hipError_t {
+            if (lds_bytes > 64 * 1024) {
+                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+                if (e != hipSuccess) return e;
+            }
+            if (e0 || e1) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), lds_bytes, st, e0, e1, 0, kp, xu);
+            else kern<<<grid, NTHR, lds_bytes, st>>>(kp, xu);
+            return hipGetLastError();
+        };
+        if (dbg) return kp.wt_store ? go(cons_jac_static_kernel<P, SC, S, true, NTHR, true>) : go(cons_jac_static_kernel<P, SC, S, true, NTHR, false>);
+        return kp.wt_store ? go(cons_jac_static_kernel<P, SC, S, false, NTHR, true>) : go(cons_jac_static_kernel<P, SC, S, false, NTHR, false>);
+    }
+    return hipSuccess;
+}
+// lean_ok: bit 0 -- the handle allows the lean variant; bit 1 -- and its static-emit form (ctd_create: manual pattern, CSC order,
+// whole grid, periods checked against StaticEmit; env CTD_STATIC_EMIT=0 forbids it)
 template <class P, int SC, int S>
 hipError_t launch_variant(const KParams& kp, const double* xu, int grid, int block, size_t lds_bytes, hipStream_t st,
                           hipEvent_t e0, hipEvent_t e1, int lean_ok) {
     const bool dbg = kp.stamps || kp.debug_stop;
+    if ((lean_ok & 3) == 3 && kp.halo == nullptr && kp.n_early == 0 && (block == 256 || block == 320)) {
+        bool done = false;
+        const hipError_t e = block == 256 ? launch_static<P, SC, S, 256>(kp, xu, grid, lds_bytes, st, e0, e1, dbg, done)
+                                          : launch_static<P, SC, S, 320>(kp, xu, grid, lds_bytes, st, e0, e1, dbg, done);
+        if (done) return e;
+    }
+    lean_ok &= 1;
     // The lean variant exists for the direct tiles and for the staged tiles of the Gauss-Legendre schemes, where it measured faster
     // (profiles/lean_kernel.md).  The staged tiles of the one-point schemes keep the general kernel: the 12-state quadrotor on
     // midpoint, N = 20 000, measured 15.74 us lean against 15.50; trapeze was not measured.

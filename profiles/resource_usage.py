@@ -101,10 +101,102 @@ def write_diag(table):
     print(path, len(lines) - 2, "rows")
 
 
+# ---- constraint / Jacobian kernel: the lean variant and its static-emit form (profiles/static_emit.md) --------------------------
+# (file stem, OCP type, scheme class, stages, lanes the default rule launches) of bench/stamps.py's cfg2 / cfg3 / cfg4
+CONS_JAC = (("cfg2", "goddard", "GoddardOCP", 2, 2, 320), ("cfg3", "double_integrator_path", "DoubleIntegratorPathOCP", 1, 1, 256),
+            ("cfg4", "goddard", "GoddardOCP", 2, 3, 256))
+
+
+def cons_jac_counts(stem):
+    """{mangled kernel name: dict(resources..., code bytes, and the mnemonic-class counts of the section behind the tile's barrier)}
+    Section: from the FIRST workgroup barrier of the function to the end of program or to the next pin of kernel arguments,
+    whichever comes first -- the static-emit kernel places the tile's path first and the edge arm (which opens with a pin) behind
+    it, so this is the tile's emit alone, ALL its store cases counted although a tile runs one of them; in the lean kernel the
+    edge block's emit is inlined in the same run of code and is counted with it.  Classes: branch (s_branch / s_cbranch_*), scalar load (s_load_*), store (global_store_*)."""
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S",
+                        "-Rpass-analysis=kernel-resource-usage", f"ctd_kern_{stem}.hip", "-o", "-"], cwd=CSRC, capture_output=True, text=True)
+    if r.returncode:
+        raise SystemExit(r.stderr[-4000:])
+    res, cur = {}, None
+    pats = (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+            ("waves", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sgpr_spill", r"SGPRs Spill: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)"))
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = res.setdefault(m.group(1), {})
+            continue
+        if cur is not None:
+            for key, pat in pats:
+                m = re.search(pat, line)
+                if m:
+                    cur[key] = int(m.group(1))
+    name, body = None, []
+    for line in r.stdout.splitlines():
+        m = re.match(r"^(_ZN3ctd\w*cons_jac\w*):", line)
+        if m:
+            name, body = m.group(1), []
+            continue
+        if name is None:
+            continue
+        m = re.search(r"; codeLenInByte = (\d+)", line)
+        if m and name in res:
+            ins = [l.split()[0] for l in body if l.startswith("\t") and (l.lstrip().startswith(";;#ASMSTART") or not l.lstrip().startswith((".", ";")))]
+            b0 = next((i for i, x in enumerate(ins) if x == "s_barrier"), None)
+            sec = []
+            if b0 is not None:
+                # (the pins of the kernel arguments are empty asm statements: the first one behind the tile's barrier opens the edge arm)
+                e0 = next((i for i in range(b0, len(ins)) if ins[i] in ("s_endpgm", ";;#ASMSTART")), len(ins))
+                sec = ins[b0 + 1:e0]
+                if e0 < len(ins) and ins[e0] == ";;#ASMSTART":
+                    # the edge arm opens with the scalar loads its pin names: the run of loads that ends within a few instructions
+                    # of the pin belongs to it, not to the tile's emit
+                    hi = max((i for i, x in enumerate(sec) if x.startswith("s_load")), default=-1)
+                    lo, i, gap = hi, hi - 1, 0
+                    while i >= 0 and gap <= 3:          # (the run may be broken by an instruction or two)
+                        if sec[i].startswith("s_load"):
+                            lo, gap = i, 0
+                        else:
+                            gap += 1
+                        i -= 1
+                    if hi >= 0 and len(sec) - hi <= 4:
+                        sec = sec[:lo]
+            ins = [x for x in ins if x != ";;#ASMSTART"]
+            res[name].update(code_bytes=int(m.group(1)), instructions=len(ins), sec_instructions=len(sec),
+                             sec_branches=sum(x.startswith(("s_branch", "s_cbranch")) for x in sec),
+                             sec_scalar_loads=sum(x.startswith("s_load") for x in sec),
+                             sec_stores=sum(x.startswith("global_store") for x in sec))
+            name = None
+            continue
+        body.append(line)
+    return res
+
+
+def cons_jac_table():
+    print("| workload | kernel | code bytes | instructions | behind the barrier: instructions | branches | scalar loads | stores "
+          "| SGPRs | VGPRs | SGPR / VGPR spills | scratch | waves/SIMD |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    cache = {}
+    for cfg, stem, ocp, sc, s, lanes in CONS_JAC:
+        res = cache.setdefault(stem, cons_jac_counts(stem))
+        tag = f"{len(ocp)}{ocp}ELi{sc}ELi{s}E"
+        for label, suffix in (("lean", f"cons_jac_kernelINS_{tag}Lb0ELb1EEE"), (f"static, {lanes} lanes, write-through", f"cons_jac_static_kernelINS_{tag}Lb0ELi{lanes}ELb1EEE")):
+            k = [v for n, v in res.items() if suffix in n]
+            if not k:
+                print(f"| {cfg} | {label} | not built |")
+                continue
+            k = k[0]
+            assert k["scratch"] == 0, (cfg, label, k)
+            print(f"| {cfg} | {label} | {k['code_bytes']} | {k['instructions']} | {k['sec_instructions']} | {k['sec_branches']} | {k['sec_scalar_loads']} "
+                  f"| {k['sec_stores']} | {k['sgpr']} | {k['vgpr']} | {k['sgpr_spill']} / {k['vgpr_spill']} | {k['scratch']} | {k['waves']} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--cons-jac", action="store_true", help="print the table of profiles/static_emit.md (lean and static-emit kernels of cfg2 / cfg3 / cfg4) and stop")
     args = ap.parse_args()
+    if args.cons_jac:
+        return cons_jac_table()
     stems = [s for s, _ in PRODUCTS]
     with ThreadPoolExecutor(args.jobs) as ex:
         table = dict(zip(stems, ex.map(remarks, stems)))
