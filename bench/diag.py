@@ -4,13 +4,16 @@ are built from and the assembly kernels they replace, on one handle per workload
     hdiag, jsq_rows, jsq_cols     the three new calls (2, 1 and 2 launches)
     hprod, jtprod, jprod          their lane families' products (2, 2 and 1 launches)
     hess_coord, jac_coord         the assembly a consumer needed before to read the same diagonals off H and J
+    --shard: hdiag_shard, jsq_rows_shard, jsq_cols_shard on the FIRST shard of a two-shard split of the same grid (a second handle,
+                                  steps [0, N / 2), its halos copied: it reads the same full x), beside the whole-grid calls and half
+                                  of them.  One card: context for the launch floor and the per-node cost, no multi-GPU rate.
 
 The calls are alternated over --rounds rounds after a warm-up; each figure is the median over the rounds of the mean over a window
 of at least --window seconds (device events around the enqueues on the handle's stream); the per-round figures are kept so the
 run-to-run spread of each can be read (spread_us: max - min over the rounds).  --untouched-only times the calls that exist without
 the diagonals (for a run on another commit).  Prints one JSON line (and writes it to --out when given).
 
-    python bench/diag.py [--window 0.2] [--rounds 5] [--only cfg2,cfg3] [--untouched-only] [--out FILE]
+    python bench/diag.py [--window 0.2] [--rounds 5] [--only cfg2,cfg3] [--untouched-only] [--shard] [--out FILE]
 """
 import argparse
 import json
@@ -31,7 +34,7 @@ from helpers import bench_inputs, describe  # noqa: E402
 from products import WORKLOADS, timed  # noqa: E402
 
 
-def workload(name, prob, sch, N, pattern, window, rounds, untouched_only):
+def workload(name, prob, sch, N, pattern, window, rounds, untouched_only, shard=False):
     stream = torch.cuda.current_stream(0)
     d = ct.DOCP(prob, N, sch, device=0, pattern=pattern)
     d.set_stream(stream)
@@ -47,6 +50,13 @@ def workload(name, prob, sch, N, pattern, window, rounds, untouched_only):
         fns.update(hdiag_us=lambda: d.hdiag(x, y, obj_weight=0.7, out=ov, sync=False),
                    jsq_rows_us=lambda: d.jsq_rows(x, wx, out=oc, sync=False),
                    jsq_cols_us=lambda: d.jsq_cols(x, wc, out=ov2, sync=False))
+    if shard and not untouched_only:
+        ds = ct.DOCP(prob, N, sch, device=0, pattern=pattern, steps=(0, N // 2))
+        ds.set_stream(stream)
+        sv, sc_, sv2 = new(nvar), new(ncon), new(nvar)
+        fns.update(hdiag_shard_us=lambda: ds.hdiag_shard(x, y, 0.7, out=sv),
+                   jsq_rows_shard_us=lambda: ds.jsq_rows_shard(x, wx, out=sc_),
+                   jsq_cols_shard_us=lambda: ds.jsq_cols_shard(x, wc, out=sv2))
     fns.update(hprod_us=lambda: d.hprod(x, y, v, obj_weight=0.7, out=ov, sync=False),
                jtprod_us=lambda: d.jtprod(x, w, out=ov2, sync=False),
                jprod_us=lambda: d.jprod(x, v, out=oc, sync=False),
@@ -66,6 +76,9 @@ def workload(name, prob, sch, N, pattern, window, rounds, untouched_only):
                    jsq_rows_over_jprod=round(out["jsq_rows_us"] / out["jprod_us"], 3),
                    diagonals_over_assembly=round((out["hdiag_us"] + out["jsq_rows_us"] + out["jsq_cols_us"]) /
                                                  (out["hess_coord_us"] + out["jac_coord_us"]), 3))
+        if shard:
+            for k in ("hdiag", "jsq_rows", "jsq_cols"):
+                out[f"{k}_shard_over_half"] = round(out[f"{k}_shard_us"] / (0.5 * out[f"{k}_us"]), 3)
     return out
 
 
@@ -75,11 +88,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only", default=None, help="comma-separated workload names")
     ap.add_argument("--untouched-only", action="store_true")
+    ap.add_argument("--shard", action="store_true", help="also time the shard calls on the first of two shards")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench/diag.py needs a GPU"
     only = set(args.only.split(",")) if args.only else None
-    results = [workload(*wl, args.window, args.rounds, args.untouched_only) for wl in WORKLOADS if only is None or wl[0] in only]
+    results = [workload(*wl, args.window, args.rounds, args.untouched_only, args.shard) for wl in WORKLOADS if only is None or wl[0] in only]
     line = json.dumps({"bench": "diag", "device": torch.cuda.get_device_name(0), "workloads": results})
     print(line)
     if args.out:

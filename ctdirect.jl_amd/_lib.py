@@ -118,6 +118,9 @@ SYMBOLS = {
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),
     "ctd_kktprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctd_hdiag_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp]),
+    "ctd_jsq_rows_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "ctd_jsq_cols_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hess_coord_batch_dev_async": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64]),
     # one transcription on several GPUs of one process
     "ctd_create_sharded": (C.c_int32, [C.POINTER(ctd_desc), C.POINTER(C.c_int32), C.c_int32, C.POINTER(_vp)]),

@@ -27,8 +27,13 @@
 //              on the trapeze U_{k+1} behind it, then v; path rows -- X_k [0, n), the control block read [n, n + cu), v;
 //              boundary rows -- X_1, X_{N+1}, v.  One launch, no reduction across lanes.
 //
-// Two launches (units, finish) for hdiag and jsq_cols, one for jsq_rows.  No atomics, fixed summation order.  Whole-grid handles
-// only: the shard form is not written.
+// Two launches (units, finish) for hdiag and jsq_cols, one for jsq_rows.  No atomics, fixed summation order.
+//
+// On a shard of the grid (ctd_hdiag_shard_dev_async, ctd_jsq_rows_shard_dev_async, ctd_jsq_cols_shard_dev_async: the SH = true
+// instantiations) the same lanes run over the nodes of the shard's steps only, as the products' lanes do (ProdParams,
+// ctd_prod_kernels.hpp): the lanes at the shard's two ends resolve every region of the iterate they read through buf(), the
+// finishes add the boundary rows' (hdiag: and the Mayer term's) entries the shard owns, and the nv entries of hdiag / jsq_cols are
+// the shard's partial sums.  Weights and multipliers are always read from the pointer passed, at global indices.
 #pragma once
 #include "ctd_hprod_kernels.hpp"
 
@@ -36,7 +41,7 @@ namespace ctd {
 
 // ---- hdiag ----------------------------------------------------------------------------------------------------------------
 // direction id g0 carries the tangent AND the seed: ab = e_g0' H e_g0
-struct DiagSeedSrc {
+template <bool SH = false> struct DiagSeedSrc {
     const double* x;
     int g0;
     CTD_HD const double* buf(int64_t) const { return x; }
@@ -48,9 +53,19 @@ struct DiagSeedSrc {
     }
     CTD_HD Dual2<1> at(int64_t g, int dir) const { return at(x, g, dir); }
 };
+// On a shard: where x is found (XWhere, ctd_prod_kernels.hpp), buf() as HSeedSrc's.  A type of its own: with the member in the
+// whole-grid source too -- null there, folded away -- the whole-grid unit kernels came out of the compiler as other code.
+template <> struct DiagSeedSrc<true> : DiagSeedSrc<false> {
+    XWhere wh;
+    CTD_HD const double* buf(int64_t g) const { return (wh.nr && wh.edge) ? xnear(*wh.nr, x, g) : x; }
+};
+template <bool SH> CTD_HD DiagSeedSrc<SH> diag_src(const double* xu, int g0, const XWhere& wh) {
+    if constexpr (SH) return DiagSeedSrc<true>{{xu, g0}, wh};
+    else return DiagSeedSrc<false>{xu, g0};
+}
 
 // lane (node k, direction q of node k's variables): its block (bk entries) and v [bk, bk + nv), as hprod_unit_body with JC = 1
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __device__ __forceinline__ void hdiag_unit_body(const HProdParams& hp, const double* __restrict__ xu, int64_t k, int q, double* gv) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV;
     using T = Dual2<1>;
@@ -59,7 +74,7 @@ __device__ __forceinline__ void hdiag_unit_body(const HProdParams& hp, const dou
     const int bk = (k < L.N || SC == SC_TRAPEZE) ? L.blk : n;         // the last node of the other schemes owns X_{N+1} only
     const int g0 = q;
     if (g0 >= bk + nv) return;
-    const DiagSeedSrc src{xu, g0};
+    const DiagSeedSrc<SH> src = diag_src<SH>(xu, g0, prod_where<SH>(pp, k));
     const double* y = pp.dir;
     double acc[1] = {0.0};
     const bool hits_x = g0 < n;                     // an X_k direction
@@ -101,14 +116,15 @@ __device__ __forceinline__ void hdiag_unit_body(const HProdParams& hp, const dou
 template <class P, int SC, int S, bool SH = false>
 __global__ void __launch_bounds__(256) hdiag_units_kernel(const HProdParams hp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    prod_units_body<P::NV>(hp.p, (int)blockIdx.x, wsum, [&](int64_t k, int q, double* gv) { hdiag_unit_body<P, SC, S>(hp, xu, k, q, gv); });
+    prod_units_body<P::NV, SH>(hp.p, (int)blockIdx.x, wsum,
+                               [&](int64_t k, int q, double* gv) { hdiag_unit_body<P, SC, S, SH>(hp, xu, k, q, gv); });
 }
 
 // the finish of hprod on the diagonal's seeds: boundary rows (with multipliers) and the Mayer term, then the v partials
 template <class P, bool SH = false>
 __global__ void __launch_bounds__(64) hdiag_finish_kernel(const HProdParams hp, const double* __restrict__ xu) {
     __shared__ double bv[kMaxNV];
-    prod_finish_body<P, 1, true>(hp.p, bv, [&](int g0) { return DiagSeedSrc{xu, g0}; }, hp.sigma);
+    prod_finish_body<P, 1, true, SH>(hp.p, bv, [&](int g0) { return diag_src<SH>(xu, g0, finish_where<SH>(hp.p)); }, hp.sigma);
 }
 
 // ---- jsq_cols -------------------------------------------------------------------------------------------------------------
@@ -132,7 +148,7 @@ template <int JC> __device__ __forceinline__ auto squared_rows(const double* con
 
 // lane (node k, chunk q): the JC entries in directions [q JC, (q + 1) JC) of node k's variables -- its block (bk entries) and
 // v [bk, bk + nv) -- every scheme on the general lane of jtprod_unit_body
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __device__ __forceinline__ void jsq_cols_unit_body(const ProdParams& pp, const double* __restrict__ xu, int64_t k, int q, double* gv) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV, JC = JsqDirs<P>::JC;
     using T = Dual<JC>;
@@ -140,7 +156,7 @@ __device__ __forceinline__ void jsq_cols_unit_body(const ProdParams& pp, const d
     const int bk = (k < L.N || SC == SC_TRAPEZE) ? L.blk : n;
     const int g0 = q * JC;
     if (g0 >= bk + nv) return;
-    const SeedSrc<JC> src{xu, g0, XWhere{}};
+    const SeedSrc<JC> src{xu, g0, prod_where<SH>(pp, k)};
     const double* w = pp.dir;
     double acc[JC];
 #pragma unroll
@@ -179,11 +195,13 @@ __device__ __forceinline__ void jsq_cols_unit_body(const ProdParams& pp, const d
 template <class P, int SC, int S, bool SH = false>
 __global__ void __launch_bounds__(256) jsq_cols_units_kernel(const ProdParams pp, const double* __restrict__ xu) {
     __shared__ double wsum[4][kMaxNV];
-    prod_units_body<P::NV>(pp, (int)blockIdx.x, wsum, [&](int64_t k, int q, double* gv) { jsq_cols_unit_body<P, SC, S>(pp, xu, k, q, gv); });
+    prod_units_body<P::NV, SH>(pp, (int)blockIdx.x, wsum,
+                               [&](int64_t k, int q, double* gv) { jsq_cols_unit_body<P, SC, S, SH>(pp, xu, k, q, gv); });
 }
 
 // The finish, one wave.  prod_finish_body fixes its row sink (weighted_rows) and needs multipliers; here the sink squares and the
-// weights may be null.  Chunks, directions and the ordered sum of the v partials are prod_finish_body's.
+// weights may be null.  Chunks, directions, the ordered sum of the v partials and the shard rules (SH: chunks on the shards that
+// own X_1 or X_{N+1} only, an entry added where the shard owns it, the nv entries the shard's partial sums) are prod_finish_body's.
 template <class P, bool SH = false>
 __global__ void __launch_bounds__(64) jsq_cols_finish_kernel(const ProdParams pp, const double* __restrict__ xu) {
     __shared__ double bv[kMaxNV];
@@ -193,9 +211,10 @@ __global__ void __launch_bounds__(64) jsq_cols_finish_kernel(const ProdParams pp
     if (lane < kMaxNV) bv[lane] = 0.0;
     __syncthreads();
     if constexpr (nb > 0) {
+        const bool first = !SH || pp.owns_first, last = !SH || pp.owns_last;
         const int64_t gf = L.N * (int64_t)L.blk;
-        for (int g0 = lane * JC; g0 < 2 * n + nv; g0 += 64 * JC) {
-            const SeedSrc<JC> src{xu, g0, XWhere{}};
+        for (int g0 = lane * JC; (first || last) && g0 < 2 * n + nv; g0 += 64 * JC) {
+            const SeedSrc<JC> src{xu, g0, finish_where<SH>(pp)};
             double acc[JC];
 #pragma unroll
             for (int d = 0; d < JC; ++d) acc[d] = 0.0;
@@ -204,9 +223,9 @@ __global__ void __launch_bounds__(64) jsq_cols_finish_kernel(const ProdParams pp
 #pragma unroll
             for (int d = 0; d < JC; ++d) {
                 const int g = g0 + d;
-                if (g < n) pp.out[g] += acc[d];
-                else if (g < 2 * n) pp.out[gf + g - n] += acc[d];
-                else if (g < 2 * n + nv) bv[g - 2 * n] = acc[d];
+                if (g < n) { if (first) pp.out[g] += acc[d]; }
+                else if (g < 2 * n) { if (last) pp.out[gf + g - n] += acc[d]; }
+                else if (g < 2 * n + nv) { if (last) bv[g - 2 * n] = acc[d]; }
             }
         }
     }
@@ -222,8 +241,10 @@ __global__ void __launch_bounds__(64) jsq_cols_finish_kernel(const ProdParams pp
 // ---- jsq_rows -------------------------------------------------------------------------------------------------------------
 // One evaluation group of a row owner: NR rows over D directions in chunks of JC (ascending), row r's sum in acc[r].
 // eval(src, sink): the row evaluator on Dual<JC>; widx(g): where direction g's weight is found in wx (null: ones).
-template <int JC, int NR, class Eval, class WIdx>
-__device__ __forceinline__ void jsq_rows_group(const double* xu, const double* wx, int D, double (&acc)[NR], Eval&& eval, WIdx&& widx) {
+// SH: lane k finds the iterate where prod_where says; the weights are read from wx at global indices always
+template <int JC, int NR, bool SH, class Eval, class WIdx>
+__device__ __forceinline__ void jsq_rows_group(const ProdParams& pp, int64_t k, const double* xu, const double* wx, int D, double (&acc)[NR],
+                                               Eval&& eval, WIdx&& widx) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) acc[r] = 0.0;
     for (int g0 = 0; g0 < D; g0 += JC) {
@@ -232,7 +253,7 @@ __device__ __forceinline__ void jsq_rows_group(const double* xu, const double* w
         // register.
         int gs = g0;
         asm volatile("" : "+v"(gs));
-        const SeedSrc<JC> src{xu, gs, XWhere{}};
+        const SeedSrc<JC> src{xu, gs, prod_where<SH>(pp, k)};
         double wj[JC];
 #pragma unroll
         for (int d = 0; d < JC; ++d) wj[d] = g0 + d < D ? (wx ? wx[widx(g0 + d)] : 1.0) : 0.0;
@@ -244,7 +265,9 @@ __device__ __forceinline__ void jsq_rows_group(const double* xu, const double* w
     }
 }
 
-template <class P, int SC, int S>
+// On a shard (SH) the direction ids and the weights' indices keep this layout; the iterate's values of X_{k+1} (U_{k+1}), of the
+// control block the path rows read and of X_1 / X_{N+1} come through buf() per region in the row evaluators.
+template <class P, int SC, int S, bool SH = false>
 __device__ __forceinline__ void jsq_rows_unit_body(const ProdParams& pp, const double* __restrict__ xu, int64_t k) {
     constexpr int n = P::NX, m = P::NU, nv = P::NV, p = P::NPATH, nb = P::NBC, JC = JsqDirs<P>::JC;
     constexpr int EQ = SC == SC_IRK ? n * (S + 1) : n;         // rows of a step
@@ -258,8 +281,8 @@ __device__ __forceinline__ void jsq_rows_unit_body(const ProdParams& pp, const d
         const int vd = L.blk + n + (SC == SC_TRAPEZE ? m : 0);
         const ProdRoles ro{0, n, L.blk, SC == SC_TRAPEZE ? L.blk + n : -1, vd};
         double acc[EQ > 0 ? EQ : 1];
-        jsq_rows_group<JC, (EQ > 0 ? EQ : 1)>(
-            xu, wx, vd + nv, acc,
+        jsq_rows_group<JC, (EQ > 0 ? EQ : 1), SH>(
+            pp, k, xu, wx, vd + nv, acc,
             [&](const SeedSrc<JC>& src, auto& sink) __attribute__((always_inline)) {
                 prod_step_rows<P, SC, S, T>(pp, src, k, ro, sink);
             },
@@ -272,8 +295,8 @@ __device__ __forceinline__ void jsq_rows_unit_body(const ProdParams& pp, const d
         const int vd = n + L.cu;
         const int64_t ub = path_ctrl_node(L, k) * (int64_t)L.blk;
         double acc[p];
-        jsq_rows_group<JC, p>(
-            xu, wx, vd + nv, acc,
+        jsq_rows_group<JC, p, SH>(
+            pp, k, xu, wx, vd + nv, acc,
             [&](const SeedSrc<JC>& src, auto& sink) __attribute__((always_inline)) { prod_path_rows<P, SC, S, T>(pp, src, k, 0, n, vd, sink); },
             [&](int g) __attribute__((always_inline)) { return g < n ? b0 + g : (g < vd ? ub + g : L.v_off + (g - vd)); });
         const int64_t rp = k < L.N ? k * (int64_t)L.cb + L.eqs : L.N * (int64_t)L.cb;
@@ -284,8 +307,8 @@ __device__ __forceinline__ void jsq_rows_unit_body(const ProdParams& pp, const d
         if (k == L.N) {
             const int64_t gf = L.N * (int64_t)L.blk;
             double acc[nb];
-            jsq_rows_group<JC, nb>(
-                xu, wx, 2 * n + nv, acc,
+            jsq_rows_group<JC, nb, SH>(
+                pp, k, xu, wx, 2 * n + nv, acc,
                 [&](const SeedSrc<JC>& src, auto& sink) __attribute__((always_inline)) { prod_boundary_rows<P, T>(pp, src, true, sink); },
                 [&](int g) __attribute__((always_inline)) { return g < n ? (int64_t)g : (g < 2 * n ? gf + (g - n) : L.v_off + (g - 2 * n)); });
             const int64_t rb = L.ncon - L.bc;
@@ -295,17 +318,19 @@ __device__ __forceinline__ void jsq_rows_unit_body(const ProdParams& pp, const d
     }
 }
 
-template <class P, int SC, int S>
+template <class P, int SC, int S, bool SH = false>
 __global__ void __launch_bounds__(256) jsq_rows_kernel(const ProdParams pp, const double* __restrict__ xu) {
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id <= pp.L.N) jsq_rows_unit_body<P, SC, S>(pp, xu, id);
+    if constexpr (SH) {
+        if (pp.unit_begin + id < pp.unit_end) jsq_rows_unit_body<P, SC, S, true>(pp, xu, pp.unit_begin + id);
+    } else if (id <= pp.L.N) jsq_rows_unit_body<P, SC, S>(pp, xu, id);
 }
 
 #if !defined(__HIPCC_RTC__)
-// ---- launchers (instantiated per registry problem in ctd_dkern_*.hip) -----------------------------------------------------
+// ---- launchers (instantiated per registry problem: whole grid in ctd_dkern_*.hip, the shard forms in ctd_dskern_*.hip) -----
 struct HdiagKernels {
     using Params = HProdParams;
-    static constexpr bool kShardForm = false;
+    static constexpr bool kShardForm = true;
     static ProdParams& prod(Params& a) { return a.p; }
     static const ProdParams& prod(const Params& a) { return a.p; }
     template <class P, int SC, int S, bool SH> static constexpr auto units = &hdiag_units_kernel<P, SC, S, SH>;
@@ -313,25 +338,31 @@ struct HdiagKernels {
 };
 struct JsqColsKernels {
     using Params = ProdParams;
-    static constexpr bool kShardForm = false;
+    static constexpr bool kShardForm = true;
     static ProdParams& prod(Params& a) { return a; }
     static const ProdParams& prod(const Params& a) { return a; }
     template <class P, int SC, int S, bool SH> static constexpr auto units = &jsq_cols_units_kernel<P, SC, S, SH>;
     template <class P, bool SH> static constexpr auto finish = &jsq_cols_finish_kernel<P, SH>;
 };
-template <class P>
+// SH: the grid covers the nodes [unit_begin, unit_end)
+template <class P, bool SH = false>
 hipError_t launch_jsq_rows(const ProdParams& pp, const double* xu, hipStream_t st) {
-    const unsigned grid = (unsigned)((pp.L.N + 1 + 255) / 256);
-    for_scheme<false>(pp.L, [&](auto t) { jsq_rows_kernel<P, t.sc, t.s><<<grid, 256, 0, st>>>(pp, xu); });
+    const unsigned grid = (unsigned)(((SH ? pp.unit_end - pp.unit_begin : pp.L.N + 1) + 255) / 256);
+    for_scheme<false>(pp.L, [&](auto t) { jsq_rows_kernel<P, t.sc, t.s, SH><<<grid, 256, 0, st>>>(pp, xu); });
     return hipGetLastError();
 }
 
 #define CTD_DIAG_LAUNCHERS(X, P)                                                                                        \
     X template hipError_t launch_prod_units<P, HdiagKernels, false>(const HProdParams&, const double*, hipStream_t);    \
     X template hipError_t launch_prod_units<P, JsqColsKernels, false>(const ProdParams&, const double*, hipStream_t);   \
-    X template hipError_t launch_jsq_rows<P>(const ProdParams&, const double*, hipStream_t);
+    X template hipError_t launch_jsq_rows<P, false>(const ProdParams&, const double*, hipStream_t);
+#define CTD_DIAG_SHARD_LAUNCHERS(X, P)                                                                                  \
+    X template hipError_t launch_prod_units<P, HdiagKernels, true>(const HProdParams&, const double*, hipStream_t);     \
+    X template hipError_t launch_prod_units<P, JsqColsKernels, true>(const ProdParams&, const double*, hipStream_t);    \
+    X template hipError_t launch_jsq_rows<P, true>(const ProdParams&, const double*, hipStream_t);
 #define CTD_INSTANTIATE_DIAG(P) CTD_DIAG_LAUNCHERS(, P)
-#define CTD_EXTERN_DIAG(P) CTD_DIAG_LAUNCHERS(extern, P)
+#define CTD_INSTANTIATE_DIAG_SHARD(P) CTD_DIAG_SHARD_LAUNCHERS(, P)
+#define CTD_EXTERN_DIAG(P) CTD_DIAG_LAUNCHERS(extern, P) CTD_DIAG_SHARD_LAUNCHERS(extern, P)
 #endif  // !__HIPCC_RTC__
 
 }  // namespace ctd

@@ -60,7 +60,7 @@ template <class T = double> struct DevBuf {
 };
 
 // the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each, loaded at first use (jit_load)
-enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, JIT_KKT, JIT_KKT_SHARD, JIT_DIAG, kJitFamilies };
+enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, JIT_KKT, JIT_KKT_SHARD, JIT_DIAG, JIT_DIAG_SHARD, kJitFamilies };
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t f[5] = {};        // in the order of the family's name expressions (kJit)
@@ -131,8 +131,9 @@ struct ctd_handle {
     // matrix-free KKT products (ctd_kktprod*, the shard call included): their own partial sums again; the host call stages x, y, dx and rx as ctd_hprod does
     // and dy, sx, sc and rc here (nvar / ncon entries)
     DevBuf<> d_kktpartial, d_kdy, d_ksx, d_ksc, d_krc;
-    // matrix-free KKT diagonals (ctd_hdiag*, ctd_jsq_cols*; ctd_jsq_rows* has no reduction): a partial-sum buffer per call, so a
-    // graph captured over any other product keeps its own; the host calls stage through d_x, d_y, d_pdir and d_pout
+    // matrix-free KKT diagonals (ctd_hdiag*, ctd_jsq_cols*, the shard calls included; ctd_jsq_rows* has no reduction): a
+    // partial-sum buffer per call, so a graph captured over any other product keeps its own; the host calls stage through d_x,
+    // d_y, d_pdir and d_pout
     DevBuf<> d_hdpartial, d_jcpartial;
     std::string err;
 };
@@ -344,11 +345,13 @@ std::vector<std::string> jit_prod_shard_exprs(int sc, int s) { return prod_exprs
 std::vector<std::string> jit_hprod_shard_exprs(int sc, int s) { return hprod_exprs(sc, s, ", true"); }
 std::vector<std::string> jit_kkt_exprs(int sc, int s) { return kkt_exprs(sc, s, ""); }
 std::vector<std::string> jit_kkt_shard_exprs(int sc, int s) { return kkt_exprs(sc, s, ", true"); }
-std::vector<std::string> jit_diag_exprs(int sc, int s) {
-    const std::string a = "<ctd::UserOCP, " + std::to_string(sc) + ", " + std::to_string(sc == SC_IRK && s > 0 ? s : 1) + ">";
-    return {"ctd::hdiag_units_kernel" + a, "ctd::hdiag_finish_kernel<ctd::UserOCP>", "ctd::jsq_cols_units_kernel" + a,
-            "ctd::jsq_cols_finish_kernel<ctd::UserOCP>", "ctd::jsq_rows_kernel" + a};
+std::vector<std::string> diag_exprs(int sc, int s, const std::string& sh) {
+    const std::string a = "<ctd::UserOCP, " + std::to_string(sc) + ", " + std::to_string(sc == SC_IRK && s > 0 ? s : 1) + sh + ">";
+    return {"ctd::hdiag_units_kernel" + a, "ctd::hdiag_finish_kernel<ctd::UserOCP" + sh + ">", "ctd::jsq_cols_units_kernel" + a,
+            "ctd::jsq_cols_finish_kernel<ctd::UserOCP" + sh + ">", "ctd::jsq_rows_kernel" + a};
 }
+std::vector<std::string> jit_diag_exprs(int sc, int s) { return diag_exprs(sc, s, ""); }
+std::vector<std::string> jit_diag_shard_exprs(int sc, int s) { return diag_exprs(sc, s, ", true"); }
 
 // one row per JitFamily: the header, -ffp-contract, the name expressions
 const struct { const char* header; const char* fp_contract; std::vector<std::string> (*exprs)(int sc, int s); } kJit[kJitFamilies] = {
@@ -362,6 +365,7 @@ const struct { const char* header; const char* fp_contract; std::vector<std::str
     {"ctd_kkt_kernels.hpp", "off", jit_kkt_exprs},          // kktprod_units, kktprod_finish
     {"ctd_kkt_kernels.hpp", "off", jit_kkt_shard_exprs},    // ... and their shard forms
     {"ctd_diag_kernels.hpp", "off", jit_diag_exprs},        // hdiag_units, hdiag_finish, jsq_cols_units, jsq_cols_finish, jsq_rows
+    {"ctd_diag_kernels.hpp", "off", jit_diag_shard_exprs},  // ... and their shard forms
 };
 
 // batch: the grid's second dimension (members of a batched launch)
@@ -1564,20 +1568,25 @@ int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_
 }
 
 // ---- matrix-free KKT diagonals: diag(H), the row sums diag(J W J') and the column sums diag(J' W J) -----------------------------
-// ctd_diag_kernels.hpp.  Checks in the order of kktprod_check: handle, device, whole-grid handle, the required pointers (x and the
-// output), then the output against every input.  a: the optional input (multipliers or weights).
-static int32_t diag_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* a, const double* out) {
+// ctd_diag_kernels.hpp.  Checks in the order of kktprod_check: handle, device, whole-grid handle (not for the shard calls, which
+// take every handle), the required pointers (x and the output), then the output against every input.  a: the optional input
+// (multipliers or weights).
+static int32_t diag_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* a, const double* out,
+                          bool shard = false) {
     if (on.st) return on.st;
-    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+    if (!shard && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
         return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
-                                   "step_end, ctd_set_x_shards) is out of scope for this call");
+                                   "step_end, ctd_set_x_shards) is out of scope for this call: a shard handle calls "
+                                   "ctd_hdiag_shard_dev_async, ctd_jsq_rows_shard_dev_async or ctd_jsq_cols_shard_dev_async");
     if (!x || !out) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (x and the output are required)");
     if (out == x || (a && out == a)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
     return CTD_OK;
 }
 
-static int32_t enqueue_hdiag(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* out_dev) {
-    if (const int32_t st = jit_load(h, JIT_DIAG)) return st;
+static int32_t enqueue_hdiag(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* out_dev, bool shard = false) {
+    const char* fn = shard ? "ctd_hdiag_shard_dev_async" : "ctd_hdiag";
+    const JitFamily fam = shard ? JIT_DIAG_SHARD : JIT_DIAG;
+    if (const int32_t st = jit_load(h, fam)) return st;
     HProdParams hp;
     std::memset(&hp, 0, sizeof(hp));
     hp.p.L = h->model.L;
@@ -1585,15 +1594,16 @@ static int32_t enqueue_hdiag(ctd_handle* h, const double* x_dev, const double* y
     hp.p.dir = y_dev;
     hp.p.out = out_dev;
     hp.sigma = obj_weight;
-    prod_units(h, hp.p, false);
+    prod_units(h, hp.p, shard);
     // one direction per lane: tangent and seed are the same unit vector
-    return enqueue_prod_units<HdiagKernels>(h, "ctd_hdiag", hp, hprod_dirs_per_node(hp.p.L), 1, h->d_hdpartial, h->jit[JIT_DIAG], 0, x_dev, false);
+    return enqueue_prod_units<HdiagKernels>(h, fn, hp, hprod_dirs_per_node(hp.p.L), 1, h->d_hdpartial, h->jit[fam], 0, x_dev, shard);
 }
 
 // rows: out = diag(J diag(w) J') (ncon), one launch; otherwise out = diag(J' diag(w) J) (nvar), units + finish
-static int32_t enqueue_jsq(ctd_handle* h, bool rows, const double* x_dev, const double* w_dev, double* out_dev) {
-    const char* fn = rows ? "ctd_jsq_rows" : "ctd_jsq_cols";
-    if (const int32_t st = jit_load(h, JIT_DIAG)) return st;
+static int32_t enqueue_jsq(ctd_handle* h, bool rows, const double* x_dev, const double* w_dev, double* out_dev, bool shard = false) {
+    const char* fn = rows ? (shard ? "ctd_jsq_rows_shard_dev_async" : "ctd_jsq_rows") : (shard ? "ctd_jsq_cols_shard_dev_async" : "ctd_jsq_cols");
+    const JitFamily fam = shard ? JIT_DIAG_SHARD : JIT_DIAG;
+    if (const int32_t st = jit_load(h, fam)) return st;
     const Layout& L = h->model.L;
     ProdParams pp;
     std::memset(&pp, 0, sizeof(pp));
@@ -1601,20 +1611,23 @@ static int32_t enqueue_jsq(ctd_handle* h, bool rows, const double* x_dev, const 
     pp.tau = h->d_tau.p;
     pp.dir = w_dev;
     pp.out = out_dev;
-    prod_units(h, pp, false);
+    prod_units(h, pp, shard);
     if (!rows) {
         int jc = 1;
         if (h->rt) jc = jsq_chunk(h->rt->info.n, h->rt->dc);
         for_problem(h->model.problem, [&](auto tag) { jc = JsqDirs<typename decltype(tag)::type>::JC; });
         // the general lane for every scheme: the node's block and v (hprod's directions, not the Gauss-Legendre shortcut's)
-        return enqueue_prod_units<JsqColsKernels>(h, fn, pp, hprod_dirs_per_node(L), jc, h->d_jcpartial, h->jit[JIT_DIAG], 2, x_dev, false);
+        return enqueue_prod_units<JsqColsKernels>(h, fn, pp, hprod_dirs_per_node(L), jc, h->d_jcpartial, h->jit[fam], 2, x_dev, shard);
     }
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&pp, &x_dev};
-        e = jit_launch(h->jit[JIT_DIAG].f[4], (int)((L.N + 1 + 255) / 256), 256, 0, h->stream, args);
+        e = jit_launch(h->jit[fam].f[4], (int)((pp.unit_end - pp.unit_begin + 255) / 256), 256, 0, h->stream, args);
     }
-    for_problem(h->model.problem, [&](auto tag) { e = launch_jsq_rows<typename decltype(tag)::type>(pp, x_dev, h->stream); });
+    for_problem(h->model.problem, [&](auto tag) {
+        using P = typename decltype(tag)::type;
+        e = shard ? launch_jsq_rows<P, true>(pp, x_dev, h->stream) : launch_jsq_rows<P, false>(pp, x_dev, h->stream);
+    });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
     return CTD_OK;
 }
@@ -1633,6 +1646,24 @@ int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double*
     const OnDevice on(h, "ctd_jsq_cols_dev_async");
     const int32_t st = diag_check(on, h, "ctd_jsq_cols_dev_async", x_dev, wc_dev, out_dev);
     return st ? st : enqueue_jsq(h, false, x_dev, wc_dev, out_dev);
+}
+
+// the shard's own entries of Hd / of the column sums (+ its partial sums of the nv entries) and its own rows of the row sums, from
+// full-length buffers (see include/ctdirect_hip.h)
+int32_t ctd_hdiag_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev) {
+    const OnDevice on(h, "ctd_hdiag_shard_dev_async");
+    const int32_t st = diag_check(on, h, "ctd_hdiag_shard_dev_async", x_dev, y_dev, Hd_dev, true);
+    return st ? st : enqueue_hdiag(h, x_dev, y_dev, obj_weight, Hd_dev, true);
+}
+int32_t ctd_jsq_rows_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev) {
+    const OnDevice on(h, "ctd_jsq_rows_shard_dev_async");
+    const int32_t st = diag_check(on, h, "ctd_jsq_rows_shard_dev_async", x_dev, wx_dev, out_dev, true);
+    return st ? st : enqueue_jsq(h, true, x_dev, wx_dev, out_dev, true);
+}
+int32_t ctd_jsq_cols_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev) {
+    const OnDevice on(h, "ctd_jsq_cols_shard_dev_async");
+    const int32_t st = diag_check(on, h, "ctd_jsq_cols_shard_dev_async", x_dev, wc_dev, out_dev, true);
+    return st ? st : enqueue_jsq(h, false, x_dev, wc_dev, out_dev, true);
 }
 
 // host pointers: x, y and the weights staged through the handle's x, y and direction buffers, the result through d_pout

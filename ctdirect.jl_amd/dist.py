@@ -616,6 +616,72 @@ class ShardedDOCP:
         self._reduce_tail(out[0])
         return out
 
+    def hdiag(self, x, y, obj_weight, out, x_halo_valid=False, y_halo_valid=False):
+        """`DOCP.hdiag` of the sharded transcription (y = None: objective only): the entries of diag(H) of this rank's own variables
+        into the full-length `out`, plus the nv entries all-reduced on every rank.  y's halo rows are exchanged
+        (`exchange_product_rows`, written into y) unless `y_halo_valid`; x as in `jprod` (`x_halo_valid`)."""
+        self._product_x(x, "hdiag", x_halo_valid)
+        if y is not None and not y_halo_valid:
+            self.exchange_product_rows(y)
+        self.docp.hdiag_shard(x, y, obj_weight, out)
+        return self._reduce_tail(out)
+
+    def jsq_cols(self, x, wc, out, x_halo_valid=False):
+        """`DOCP.jsq_cols` of the sharded transcription (wc = None: ones): the entries of diag(J' diag(wc) J) of this rank's own
+        variables into the full-length `out`, plus the nv entries all-reduced on every rank.  wc: full-length, this rank's own rows
+        valid; its halo rows are exchanged here (written into wc); x as in `jprod` (`x_halo_valid`)."""
+        self._product_x(x, "jsq_cols", x_halo_valid)
+        if wc is not None:
+            self.exchange_product_rows(wc)
+        self.docp.jsq_cols_shard(x, wc, out)
+        return self._reduce_tail(out)
+
+    def jsq_rows(self, x, wx, out, x_halo_valid=False):
+        """`DOCP.jsq_rows` of the sharded transcription (wx = None: ones): this rank's rows of diag(J diag(wx) J') into the
+        full-length `out`, other rows untouched; every row sum is complete, nothing is reduced.  wx: full-length, this rank's own
+        entries and the nv tail valid; its halo is exchanged here (written into wx); x as in `jprod` (`x_halo_valid`)."""
+        self._product_x(x, "jsq_rows", x_halo_valid)
+        if wx is not None:
+            self.exchange_product_halo(wx)
+        self.docp.jsq_rows_shard(x, wx, out)
+        return out
+
+    def kkt_diag_precond(self, x, y, obj_weight=1.0, sx=None, sc=None, floor=1e-8, x_halo_valid=False, y_halo_valid=False):
+        """`DOCP.kkt_diag_precond` of the sharded transcription: returns the full-length pair (px, pc) of which this rank's own
+        entries -- and the nv tail of px, replicated -- are valid:
+            px = max(|hdiag(x, y, obj_weight) + sx|, floor),   pc = jsq_rows(x, 1 / px) + sc
+        Every input is full-length with this rank's own entries valid (x: + the nv tail; sx: the nv tail on the last rank only, the
+        convention of `kktprod`; y, sx, sc may be None).  The last rank adds the tail of sx to its partial sums of the nv entries
+        before they are all-reduced.  Three launches, one all-reduce of nv doubles and one small all-gather (the halo of 1 / px),
+        besides the halos of x and y (`x_halo_valid`, `y_halo_valid`: as in `kktprod`)."""
+        d = self.docp
+        nvar, nv = d.dim_NLP_variables, d.dims.NLP_v
+        lo, hi = self.owned_variables()
+        self._product_x(x, "kkt_diag_precond", x_halo_valid)
+        if y is not None and not y_halo_valid:
+            self.exchange_product_rows(y)
+        px = d.hdiag_shard(x, y, obj_weight)
+        own = px[lo:hi]
+        if sx is not None:
+            own += sx[lo:hi]
+            if nv and self.rank == self.world - 1:
+                px[nvar - nv:] += sx[nvar - nv:]
+        self._reduce_tail(px)
+        torch.clamp_min(torch.abs_(own), floor, out=own)
+        if nv:
+            tail = px[nvar - nv:]
+            torch.clamp_min(torch.abs_(tail), floor, out=tail)
+        wx = torch.empty_like(px)
+        torch.reciprocal(own, out=wx[lo:hi])
+        if nv:
+            torch.reciprocal(px[nvar - nv:], out=wx[nvar - nv:])
+        self.exchange_product_halo(wx)
+        pc = d.jsq_rows_shard(x, wx)
+        if sc is not None:
+            r0, r1 = self.owned_constraints()
+            pc[r0:r1] += sc[r0:r1]
+        return px, pc
+
     def obj(self, x, as_tensor=False):
         """Objective of the whole transcription: the shards' partial sums added with one all-reduce of one double that never
         leaves the device; `as_tensor=False` reads the result back at the end (the only host round trip)."""

@@ -618,7 +618,12 @@ class DOCP:
             # the element-wise operations go to the handle's stream; where Python does not know it (stream="own") the two
             # streams are ordered by waiting instead
             known = self._stream_raw is not None
-            st = torch.cuda.ExternalStream(self._stream_raw, device=x.device) if known else torch.cuda.current_stream(x.device)
+            if not known:
+                st = torch.cuda.current_stream(x.device)
+            elif self._stream_raw == 0:     # (the null stream: ExternalStream(0) is NOT it -- its cuda_stream is not 0)
+                st = torch.cuda.default_stream(x.device)
+            else:
+                st = torch.cuda.ExternalStream(self._stream_raw, device=x.device)
             with torch.cuda.stream(st):
                 px = self.hdiag(x, y, obj_weight, sync=not known)
                 if sx is not None:
@@ -719,6 +724,48 @@ class DOCP:
         if sync:
             self.sync()
         return rx, rc
+
+    def _diag_shard(self, name, x, a, aname, na, nout, out, sync, obj_weight=None):
+        """one of the matrix-free diagonals on THIS shard (`ctd_<name>_shard_dev_async`), device tensors only; a: the optional
+        input (multipliers or weights, `na` entries)"""
+        nvar = self.dim_NLP_variables
+        for nm, t in (("x", x), (aname, a), ("out", out)):
+            if t is not None and not _is_tensor(t):
+                raise TypeError(f"{nm} must be a device tensor: {name}_shard has no host path")
+        self._check_x(x)
+        for nm, t, n in ((aname, a, na), ("out", out, nout)):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{nm} has {t.numel()} entries, expected {n}")
+        if out is None:
+            import torch
+            out = torch.empty(nout, dtype=torch.float64, device=x.device)
+        extra = () if obj_weight is None else (float(obj_weight),)
+        pa = None if a is None else self._dev_ptr(a, na, aname)
+        self._ck(getattr(_lib.lib(), f"ctd_{name}_shard_dev_async")(self._h, self._dev_ptr(x, nvar, "x"), pa, *extra,
+                                                                    self._dev_ptr(out, nout, "out")))
+        if sync:
+            self.sync()
+        return out
+
+    def hdiag_shard(self, x, y, obj_weight=1.0, out=None, sync=False):
+        """`ctd_hdiag_shard_dev_async`: `hdiag` on THIS shard, device tensors only.  Into the full-length `out` (allocated,
+        uninitialised elsewhere, when None) go the entries of the shard's own variables, + the shard's partial sums in the nv tail
+        entries (the caller adds them over the shards); nothing else is touched.  x is read through the table of `set_x_shards`
+        when one is set, otherwise from x itself (halos copied in); y (None: objective only) is always read from the tensor passed:
+        the constraint-layout read set of include/ctdirect_hip.h."""
+        return self._diag_shard("hdiag", x, y, "y", self.dim_NLP_constraints, self.dim_NLP_variables, out, sync, obj_weight)
+
+    def jsq_rows_shard(self, x, wx=None, out=None, sync=False):
+        """`ctd_jsq_rows_shard_dev_async`: THIS shard's rows of `jsq_rows` -- the rows of its own steps; the last shard also the
+        final path and boundary rows -- into the full-length `out`; every row sum is complete.  wx (None: ones) is read from the
+        tensor passed: the variable-layout read set of include/ctdirect_hip.h.  See `hdiag_shard`."""
+        return self._diag_shard("jsq_rows", x, wx, "wx", self.dim_NLP_variables, self.dim_NLP_constraints, out, sync)
+
+    def jsq_cols_shard(self, x, wc=None, out=None, sync=False):
+        """`ctd_jsq_cols_shard_dev_async`: the entries of `jsq_cols` of THIS shard's own variables into the full-length `out`, + the
+        shard's partial sums in the nv tail entries.  wc (None: ones) is read from the tensor passed: the constraint-layout read
+        set of include/ctdirect_hip.h.  See `hdiag_shard`."""
+        return self._diag_shard("jsq_cols", x, wc, "wc", self.dim_NLP_constraints, self.dim_NLP_variables, out, sync)
 
     def eval_all(self, x, y=None, obj_weight=1.0, f=None, g=None, c=None, vals=None, hvals=None, sync=False):
         """One solver iteration in one call (`ctd_eval_all_dev_async`): objective -> f[0], gradient -> g, constraints -> c,

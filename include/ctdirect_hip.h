@@ -463,10 +463,11 @@ int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* 
  * calls stage x, y / the weights and the result through buffers the handle owns.
  * Run-time OCPs (ctd_register_ocp) compile these kernels -- one family for the three calls -- on the first of these calls: make one
  * call before capturing a graph.
- * OUT OF SCOPE: the shard form, batched forms, row / column max-norms.
+ * OUT OF SCOPE: batched forms, row / column max-norms.
  * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE, whatever the other arguments; shard handle
- * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL; null x or output -> CTD_EINVAL; an output
- * equal to an input -> CTD_EINVAL.  ctd_last_error names the reason. */
+ * (step_begin / step_end not the whole grid, or a ctd_set_x_shards table) -> CTD_EINVAL (a shard handle calls
+ * ctd_hdiag_shard_dev_async / ctd_jsq_rows_shard_dev_async / ctd_jsq_cols_shard_dev_async below); null x or output -> CTD_EINVAL;
+ * an output equal to an input -> CTD_EINVAL.  ctd_last_error names the reason. */
 /* host pointers: return when the result is in the caller's buffer */
 int32_t ctd_hdiag(ctd_handle* h, const double* x, const double* y, double obj_weight, double* Hd);
 int32_t ctd_jsq_rows(ctd_handle* h, const double* x, const double* wx, double* out);
@@ -518,6 +519,25 @@ int32_t ctd_hprod_shard_dev_async(ctd_handle* h, const double* x_dev, const doub
  * output equal to any input, or rx == rc -> CTD_EINVAL. */
 int32_t ctd_kktprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
                                     const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev);
+/* ctd_hdiag_dev_async, ctd_jsq_rows_dev_async and ctd_jsq_cols_dev_async on a shard: the same arguments with the same meaning
+ * (y_dev NULL: objective only; NULL weights: ones, bit-identical to a vector of ones), the same launches (two, two, one) and the
+ * partial-sum buffers of ctd_hdiag* and ctd_jsq_cols*; run-time OCPs compile one more family at the first of these three calls.
+ * WRITES -- nothing else of the output is touched:
+ *   hdiag, jsq_cols   the write set of jtprod / hprod above: the shard's own variable entries, the last shard up to v_off, and
+ *           [v_off, nvar) with the shard's PARTIAL sums, which the caller adds over the shards (one all-reduce of nv doubles).  The
+ *           boundary rows' (hdiag: and the Mayer term's) contributions go to X_1 on the first shard, to X_{N+1} and to v on the last.
+ *   jsq_rows   the write set of jprod above: the rows [sb cb, se cb), on the last shard also the tail [N cb, ncon).  Every row sum is
+ *           complete: no reduction over the shards.
+ * On a whole-grid handle each call is bit-identical to its *_dev_async counterpart, the v entries included.
+ * READS: x as above (through the table when one is set, else from x_dev with its halo copied in); y (hdiag) and wc (jsq_cols) the
+ * constraint-layout read set above, wx (jsq_rows) the variable-layout read set above, always from the pointer passed.
+ * A scaling preconditioner of ctd_kktprod_shard_dev_async per outer iteration: hdiag, an all-reduce of the nv partial sums (the last
+ * shard adds the tail of sx first), px = |Hd + sx|, an exchange of the halo of wx = 1 / px, jsq_rows, pc = out + sc on the own rows.
+ * Checks in this order: NULL handle -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE, whatever the other arguments; null x or
+ * output -> CTD_EINVAL; an output equal to an input -> CTD_EINVAL.  Every handle is accepted, shard or whole grid. */
+int32_t ctd_hdiag_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev);
+int32_t ctd_jsq_rows_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev);
+int32_t ctd_jsq_cols_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev);
 
 /* 1-based (rows[k], cols[k]), k < nnzh, CSC order */
 int32_t ctd_hess_structure(const ctd_handle* h, int64_t* rows, int64_t* cols);

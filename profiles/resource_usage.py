@@ -7,8 +7,9 @@ needed).
 Each csrc/ctd_pkern_<problem>.hip is compiled for the device only with -Rpass-analysis=kernel-resource-usage.  Per problem the
 whole-grid kernels come first, in the order the compiler reports them (trapeze, midpoint / Euler, Gauss-Legendre s = 1, 2, 3,
 then the finish kernel), followed by the shard form of the same kernels marked "shard".  The comment lines at the head of each
-log are kept.  The KKT diagonals (csrc/ctd_dkern_<problem>.hip: hdiag, jsq_cols, jsq_rows; whole-grid form only) go to a table in
-profiles/diag_resources.md, whose text above the table is kept.  The script fails if any kernel uses scratch."""
+log are kept.  The KKT diagonals (hdiag, jsq_cols, jsq_rows: the whole-grid form from csrc/ctd_dkern_<problem>.hip, the shard form
+from csrc/ctd_dskern_<problem>.hip) go to a table in profiles/diag_resources.md, each shard row under its whole-grid twin; the text
+above the table is kept.  The script fails if any kernel uses scratch."""
 import argparse
 import os
 import re
@@ -77,8 +78,9 @@ def write(log, problems, table, hprod):
     print(path, len(lines), "kernels")
 
 
-def write_diag(table):
-    """one row per problem and scheme: the three scheme-dependent kernels side by side, then the two finish kernels"""
+def write_diag(table, shard_table):
+    """per problem and scheme one row for the whole-grid form and one for the shard form: the three scheme-dependent kernels side by
+    side; then the two finish kernels, both forms"""
     path = os.path.join(ROOT, "profiles", "diag_resources.md")
     with open(path) as f:
         text = f.read()
@@ -87,14 +89,19 @@ def write_diag(table):
     lines = ["| problem | scheme | hdiag VGPR + AGPR | scratch B/lane | waves/SIMD | jsq_cols VGPR + AGPR | scratch B/lane | waves/SIMD "
              "| jsq_rows VGPR + AGPR | scratch B/lane | waves/SIMD |\n", "|---|---|---|---|---|---|---|---|---|---|---|\n"]
     for stem, name in HPROD:
-        by = {kn: [k for k in table[stem] if k["kernel"] == kn] for kn in DIAG_KERNELS}
-        for k in table[stem]:
-            assert k["scratch"] == 0, (name, k)
-        assert all(len(by[kn]) == 5 for kn in ("hdiag_units_kernel", "jsq_cols_units_kernel", "jsq_rows_kernel")), name
+        forms = []
+        for tab, shard in ((table, False), (shard_table, True)):
+            by = {kn: [k for k in tab[stem] if k["kernel"] == kn] for kn in DIAG_KERNELS}
+            for k in tab[stem]:
+                assert k["scratch"] == 0 and k["shard"] == shard, (name, k)
+            assert all(len(by[kn]) == 5 for kn in ("hdiag_units_kernel", "jsq_cols_units_kernel", "jsq_rows_kernel")), name
+            forms.append(by)
         for i, sch in enumerate(SCHEMES):
-            lines.append(f"| {name} | {sch} | {cell(by['hdiag_units_kernel'][i])} | {cell(by['jsq_cols_units_kernel'][i])} | "
-                         f"{cell(by['jsq_rows_kernel'][i])} |\n")
-        lines.append(f"| {name} | finish | {cell(by['hdiag_finish_kernel'][0])} | {cell(by['jsq_cols_finish_kernel'][0])} | | | |\n")
+            for by, tag in zip(forms, ("", ", shard")):
+                lines.append(f"| {name} | {sch}{tag} | {cell(by['hdiag_units_kernel'][i])} | {cell(by['jsq_cols_units_kernel'][i])} | "
+                             f"{cell(by['jsq_rows_kernel'][i])} |\n")
+        for by, tag in zip(forms, ("", ", shard")):
+            lines.append(f"| {name} | finish{tag} | {cell(by['hdiag_finish_kernel'][0])} | {cell(by['jsq_cols_finish_kernel'][0])} | | | |\n")
     with open(path, "w") as f:
         f.write(head)
         f.writelines(lines)
@@ -204,7 +211,8 @@ def main():
     write("hprod_resource_usage.log", HPROD, table, True)
     with ThreadPoolExecutor(args.jobs) as ex:
         dtable = dict(zip(stems, ex.map(lambda s: remarks(s, "ctd_dkern_", DIAG_KERNELS), stems)))
-    write_diag(dtable)
+        stable = dict(zip(stems, ex.map(lambda s: remarks(s, "ctd_dskern_", DIAG_KERNELS), stems)))
+    write_diag(dtable, stable)
 
 
 if __name__ == "__main__":
