@@ -59,8 +59,9 @@ template <class T = double> struct DevBuf {
     int32_t grow(ctd_handle* h, int64_t need, const char* fn);
 };
 
-// the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each, loaded at first use (jit_load)
-enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_PROD_SHARD, JIT_HPROD_SHARD, JIT_KKT, JIT_KKT_SHARD, JIT_DIAG, JIT_DIAG_SHARD, kJitFamilies };
+// the kernel families of a run-time OCP (ctd_register_ocp): one hiprtc module each -- two for the matrix-free families, whose
+// shard form is a module of its own -- loaded at first use (jit_load)
+enum JitFamily { JIT_FIRST, JIT_BATCH, JIT_PROD, JIT_HPROD, JIT_HESS, JIT_KKT, JIT_DIAG, kJitFamilies };
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t f[5] = {};        // in the order of the family's name expressions (kJit)
@@ -94,7 +95,7 @@ struct ctd_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // run-time defined OCP (ctd_register_ocp): kernels compiled with hiprtc and launched through the module API
     const RtOcp* rt = nullptr;
-    JitModule jit[kJitFamilies];
+    JitModule jit[kJitFamilies][2];     // [family][shard form]
     // Hessian of the Lagrangian: tables are uploaded by the first Hessian call (hess_ready)
     bool hess_ready = false;
     HParams hp;
@@ -229,8 +230,9 @@ static void destroy_handle(ctd_handle* h) {
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
         if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-        for (JitModule& m : h->jit)
-            if (m.mod) (void)hipModuleUnload(m.mod);
+        for (auto& fam : h->jit)
+            for (JitModule& m : fam)
+                if (m.mod) (void)hipModuleUnload(m.mod);
     }
     delete h;
 }
@@ -310,22 +312,22 @@ int32_t jit_compile(const RtOcp& ro, const char* header, const std::vector<std::
 }
 
 // The name expressions of each family.  s: stages of a Gauss-Legendre scheme; for the midpoint scheme the controls per step
-// (control_steps)
-std::vector<std::string> jit_first_exprs(int sc, int s) {
+// (control_steps); sh: ", true" for the shard form of the matrix-free kernels (a module of its own, compiled by the first shard
+// call), "" otherwise and for the families that have none
+std::vector<std::string> jit_first_exprs(int sc, int s, const std::string&) {
     const std::string P = "ctd::UserOCP", a = std::to_string(sc), b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
     return {"ctd::cons_jac_kernel<" + P + ", " + a + ", " + b + ", false>", "ctd::obj_partial_kernel<" + P + ", " + a + ">",
             "ctd::obj_finish_kernel<" + P + ">", "ctd::grad_units_kernel<" + P + ", " + a + ", " + b + ">",
             "ctd::grad_finish_kernel<" + P + ">"};
 }
-std::vector<std::string> jit_hess_exprs(int sc, int s) {
+std::vector<std::string> jit_hess_exprs(int sc, int s, const std::string&) {
     const std::string P = "ctd::UserOCP", a = std::to_string(sc), b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
     return {"ctd::hess_kernel<" + P + ", " + a + ", " + b + ", false>", "ctd::hess_finish_kernel<" + P + ">"};
 }
-std::vector<std::string> jit_batch_exprs(int sc, int s) {
+std::vector<std::string> jit_batch_exprs(int sc, int s, const std::string&) {
     const std::string b = std::to_string((sc == SC_IRK || sc == SC_MIDPOINT) && s > 0 ? s : 1);
     return {"ctd::cons_jac_batch_kernel<ctd::UserOCP, " + std::to_string(sc) + ", " + b + ">"};
 }
-// sh: ", true" for the shard form of the product kernels (a family of its own, compiled by the first shard call), "" otherwise
 std::vector<std::string> prod_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
     return {"ctd::jprod_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::jtprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">",
@@ -339,33 +341,22 @@ std::vector<std::string> kkt_exprs(int sc, int s, const std::string& sh) {
     const std::string a = std::to_string(sc), b = std::to_string(sc == SC_IRK && s > 0 ? s : 1);
     return {"ctd::kktprod_units_kernel<ctd::UserOCP, " + a + ", " + b + sh + ">", "ctd::kktprod_finish_kernel<ctd::UserOCP" + sh + ">"};
 }
-std::vector<std::string> jit_prod_exprs(int sc, int s) { return prod_exprs(sc, s, ""); }
-std::vector<std::string> jit_hprod_exprs(int sc, int s) { return hprod_exprs(sc, s, ""); }
-std::vector<std::string> jit_prod_shard_exprs(int sc, int s) { return prod_exprs(sc, s, ", true"); }
-std::vector<std::string> jit_hprod_shard_exprs(int sc, int s) { return hprod_exprs(sc, s, ", true"); }
-std::vector<std::string> jit_kkt_exprs(int sc, int s) { return kkt_exprs(sc, s, ""); }
-std::vector<std::string> jit_kkt_shard_exprs(int sc, int s) { return kkt_exprs(sc, s, ", true"); }
 std::vector<std::string> diag_exprs(int sc, int s, const std::string& sh) {
     const std::string a = "<ctd::UserOCP, " + std::to_string(sc) + ", " + std::to_string(sc == SC_IRK && s > 0 ? s : 1) + sh + ">";
     return {"ctd::hdiag_units_kernel" + a, "ctd::hdiag_finish_kernel<ctd::UserOCP" + sh + ">", "ctd::jsq_cols_units_kernel" + a,
             "ctd::jsq_cols_finish_kernel<ctd::UserOCP" + sh + ">", "ctd::jsq_rows_kernel" + a};
 }
-std::vector<std::string> jit_diag_exprs(int sc, int s) { return diag_exprs(sc, s, ""); }
-std::vector<std::string> jit_diag_shard_exprs(int sc, int s) { return diag_exprs(sc, s, ", true"); }
 
 // one row per JitFamily: the header, -ffp-contract, the name expressions
-const struct { const char* header; const char* fp_contract; std::vector<std::string> (*exprs)(int sc, int s); } kJit[kJitFamilies] = {
-    {"ctd_kernels.hpp", "off", jit_first_exprs},            // cons_jac, obj_partial, obj_finish, grad_units, grad_finish
-    {"ctd_kernels.hpp", "off", jit_batch_exprs},            // cons_jac_batch
-    {"ctd_prod_kernels.hpp", "off", jit_prod_exprs},        // jprod, jtprod_units, jtprod_finish
-    {"ctd_hprod_kernels.hpp", "off", jit_hprod_exprs},      // hprod_units, hprod_finish
-    {"ctd_hess_kernels.hpp", "fast", jit_hess_exprs},       // hess, hess_finish
-    {"ctd_prod_kernels.hpp", "off", jit_prod_shard_exprs},  // the shard forms of jprod, jtprod_units, jtprod_finish
-    {"ctd_hprod_kernels.hpp", "off", jit_hprod_shard_exprs},    // ... and of hprod_units, hprod_finish
-    {"ctd_kkt_kernels.hpp", "off", jit_kkt_exprs},          // kktprod_units, kktprod_finish
-    {"ctd_kkt_kernels.hpp", "off", jit_kkt_shard_exprs},    // ... and their shard forms
-    {"ctd_diag_kernels.hpp", "off", jit_diag_exprs},        // hdiag_units, hdiag_finish, jsq_cols_units, jsq_cols_finish, jsq_rows
-    {"ctd_diag_kernels.hpp", "off", jit_diag_shard_exprs},  // ... and their shard forms
+const struct { const char* header; const char* fp_contract; std::vector<std::string> (*exprs)(int sc, int s, const std::string& sh); }
+kJit[kJitFamilies] = {
+    {"ctd_kernels.hpp", "off", jit_first_exprs},        // cons_jac, obj_partial, obj_finish, grad_units, grad_finish
+    {"ctd_kernels.hpp", "off", jit_batch_exprs},        // cons_jac_batch
+    {"ctd_prod_kernels.hpp", "off", prod_exprs},        // jprod, jtprod_units, jtprod_finish
+    {"ctd_hprod_kernels.hpp", "off", hprod_exprs},      // hprod_units, hprod_finish
+    {"ctd_hess_kernels.hpp", "fast", jit_hess_exprs},   // hess, hess_finish
+    {"ctd_kkt_kernels.hpp", "off", kkt_exprs},          // kktprod_units, kktprod_finish
+    {"ctd_diag_kernels.hpp", "off", diag_exprs},        // hdiag_units, hdiag_finish, jsq_cols_units, jsq_cols_finish, jsq_rows
 };
 
 // batch: the grid's second dimension (members of a batched launch)
@@ -377,17 +368,17 @@ hipError_t jit_launch(hipFunction_t f, int grid, int block, size_t lds, hipStrea
 }
 }  // namespace
 
-// The kernels of family `fam` of a run-time OCP: compiled (or taken from the cache) and loaded once, nothing for a registry
-// problem.  The first family is loaded by ctd_create, whose errors go to ctd_last_error(NULL).
-static int32_t jit_load(ctd_handle* h, JitFamily fam) {
-    JitModule& m = h->jit[fam];
+// The kernels of family `fam` of a run-time OCP, its shard form when `shard`: compiled (or taken from the cache) and loaded once,
+// nothing for a registry problem.  The first family is loaded by ctd_create, whose errors go to ctd_last_error(NULL).
+static int32_t jit_load(ctd_handle* h, JitFamily fam, bool shard = false) {
+    JitModule& m = h->jit[fam][shard];
     if (!h->rt || m.mod) return CTD_OK;
     ctd_handle* eh = fam == JIT_FIRST ? nullptr : h;
     const Layout& L = h->model.L;
     std::string code, err;
     std::vector<std::string> names;
-    const int32_t st = jit_compile(*h->rt, kJit[fam].header, kJit[fam].exprs(L.sc, L.sc == SC_MIDPOINT ? L.cs : L.s), kJit[fam].fp_contract,
-                                   code, names, err);
+    const int32_t st = jit_compile(*h->rt, kJit[fam].header, kJit[fam].exprs(L.sc, L.sc == SC_MIDPOINT ? L.cs : L.s, shard ? ", true" : ""),
+                                   kJit[fam].fp_contract, code, names, err);
     if (st) return fail(eh, st, err);
     hipError_t e = hipModuleLoadData(&m.mod, code.data());
     for (size_t i = 0; e == hipSuccess && i < names.size(); ++i) e = hipModuleGetFunction(&m.f[i], m.mod, names[i].c_str());
@@ -414,36 +405,90 @@ static int32_t host_call(ctd_handle* h, std::initializer_list<Staged<const doubl
     return CTD_OK;
 }
 
-// The unit pass and the finish of a transposed product (jtprod, hprod): `dirs` directions per node in chunks of jc -- the
-// ProdDirs / HProdDirs of a registry problem, the same formula for a run-time OCP -- give the geometry and the size of the caller's
-// partial buffer, written into a's ProdParams; then the two kernels: f[f0], f[f0 + 1] of the run-time OCP's module, or
-// launch_prod_units.  a: the kernels' argument struct, its unit range set by the caller (prod_units): the grid and the partial
-// sums cover those nodes -- all N + 1 of a whole-grid call; shard: the shard form of the kernels
+// ---- the matrix-free operators: one row each -----------------------------------------------------------------------------
+// The three entry points of an operator: host pointers (ctd_X), device pointers (ctd_X_dev_async), device pointers on a shard of the
+// grid (ctd_X_shard_dev_async)
+enum MfForm { MF_HOST, MF_DEV, MF_SHARD };
+// name: the entry points by MfForm; fam, f0: the kernels of a run-time OCP -- f[f0] of the family's module, and f[f0 + 1] unless
+// one_launch: then there is no finish kernel; dir_ncon / out_ncon: the direction (v, w, dx, the weights) / the first output has
+// ncon entries, not nvar (what the host form stages); required, outs: the pointers that must not be null and the outputs, as
+// the messages name them
+struct MfOp {
+    const char* name[3];
+    JitFamily fam;
+    int f0;
+    bool one_launch, dir_ncon, out_ncon;
+    const char *required, *outs;
+};
+#define CTD_MF_OP(X, ...) {{"ctd_" #X, "ctd_" #X "_dev_async", "ctd_" #X "_shard_dev_async"}, __VA_ARGS__}
+static constexpr MfOp kJprod = CTD_MF_OP(jprod, JIT_PROD, 0, true, false, true, "x, v and Jv", "Jv"),
+                      kJtprod = CTD_MF_OP(jtprod, JIT_PROD, 1, false, true, false, "x, w and Jtw", "Jtw"),
+                      kHprod = CTD_MF_OP(hprod, JIT_HPROD, 0, false, false, false, "x, v and Hv", "Hv"),
+                      kKktprod = CTD_MF_OP(kktprod, JIT_KKT, 0, false, false, false, "x, dx, dy, rx and rc", "rx and rc"),
+                      kHdiag = CTD_MF_OP(hdiag, JIT_DIAG, 0, false, false, false, "x and Hd", "Hd"),
+                      kJsqCols = CTD_MF_OP(jsq_cols, JIT_DIAG, 2, false, true, false, "x and out", "out"),
+                      kJsqRows = CTD_MF_OP(jsq_rows, JIT_DIAG, 4, true, false, true, "x and out", "out");
+#undef CTD_MF_OP
+// One call of an operator: every message carries fn(), the entry point that was called
+struct MfCall {
+    const MfOp& op;
+    MfForm form;
+    const char* fn() const { return op.name[form]; }
+    bool shard() const { return form == MF_SHARD; }
+    int32_t launched(ctd_handle* h, hipError_t e) const {
+        return e == hipSuccess ? CTD_OK : fail(h, CTD_EHIP, std::string(fn()) + ": kernel launch: " + hipGetErrorString(e));
+    }
+};
+
+// The directions a lane of a unit pass takes together: D<P>::JC of a registry problem, the same rule for a run-time OCP
+template <template <class> class D>
+static int prod_chunk(const ctd_handle* h, int (*rule)(int n, int dc)) {
+    int jc = 1;
+    if (h->rt) jc = rule(h->rt->info.n, h->rt->dc);
+    for_problem(h->model.problem, [&](auto tag) { jc = D<typename decltype(tag)::type>::JC; });
+    return jc;
+}
+
+// An operator of one launch (jprod, jsq_rows): f[f0] of the run-time OCP's module over the call's nodes, or launch(tag, SH) -- the
+// launcher of registry problem `tag`, SH a std::bool_constant: the shard form.  pp: see enqueue_prod_units
+template <class Launch>
+static int32_t enqueue_prod_launch(ctd_handle* h, const MfCall& c, const ProdParams& pp, const double* x_dev, Launch&& launch) {
+    hipError_t e = hipErrorInvalidValue;
+    if (h->rt) {
+        void* args[] = {(void*)&pp, &x_dev};
+        e = jit_launch(h->jit[c.op.fam][c.shard()].f[c.op.f0], (int)((pp.unit_end - pp.unit_begin + 255) / 256), 256, 0, h->stream, args);
+    }
+    for_problem(h->model.problem, [&](auto tag) { e = c.shard() ? launch(tag, std::true_type{}) : launch(tag, std::false_type{}); });
+    return c.launched(h, e);
+}
+
+// The unit pass and the finish of a transposed product (jtprod, hprod, kktprod, hdiag, jsq_cols): `dirs` directions per node in
+// chunks of jc (prod_chunk) give the geometry and the size of the caller's partial buffer, written into a's ProdParams; then the two
+// kernels: f[f0], f[f0 + 1] of the run-time OCP's module, or launch_prod_units.  a: the kernels' argument struct, its unit range
+// set by the caller (prod_params): the grid and the partial sums cover those nodes -- all N + 1 of a whole-grid call
 template <class K>
-static int32_t enqueue_prod_units(ctd_handle* h, const char* fn, typename K::Params& a, int dirs, int jc, DevBuf<>& partial,
-                                  const JitModule& jm, int f0, const double* x_dev, bool shard) {
+static int32_t enqueue_prod_units(ctd_handle* h, const MfCall& c, typename K::Params& a, int dirs, int jc, DevBuf<>& partial,
+                                  const double* x_dev) {
     ProdParams& pp = K::prod(a);
     pp.nch = (int32_t)((dirs + jc - 1) / jc);
     const int64_t blocks = ((pp.unit_end - pp.unit_begin) * (int64_t)pp.nch + 255) / 256;
-    if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(fn) + ": grid too large");
+    if (blocks > 0x7fffffff) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": grid too large");
     pp.nblocks = (int32_t)blocks;
-    const int32_t st = partial.grow(h, blocks * kMaxNV, fn);
+    const int32_t st = partial.grow(h, blocks * kMaxNV, c.fn());
     if (st) return st;
     pp.partial = partial.p;
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
+        const JitModule& jm = h->jit[c.op.fam][c.shard()];
         void* args[] = {&a, &x_dev};
-        e = jit_launch(jm.f[f0], (int)blocks, 256, 0, h->stream, args);
-        if (e == hipSuccess) e = jit_launch(jm.f[f0 + 1], 1, 64, 0, h->stream, args);
+        e = jit_launch(jm.f[c.op.f0], (int)blocks, 256, 0, h->stream, args);
+        if (e == hipSuccess) e = jit_launch(jm.f[c.op.f0 + 1], 1, 64, 0, h->stream, args);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        if constexpr (K::kShardForm)
-            e = shard ? launch_prod_units<P, K, true>(a, x_dev, h->stream) : launch_prod_units<P, K, false>(a, x_dev, h->stream);
-        else e = launch_prod_units<P, K, false>(a, x_dev, h->stream);
+        e = c.shard() ? launch_prod_units<P, K, true>(a, x_dev, h->stream) : launch_prod_units<P, K, false>(a, x_dev, h->stream);
     });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return c.launched(h, e);
 }
 
 extern "C" {
@@ -674,7 +719,7 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
                 if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hp->device) != hipSuccess) cus = 256;
                 if (per_cu == 0) {
                     if (hp->rt) {
-                        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hp->jit[JIT_FIRST].f[0], hp->block, hp->lds_bytes) != hipSuccess) per_cu = 0;
+                        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hp->jit[JIT_FIRST][0].f[0], hp->block, hp->lds_bytes) != hipSuccess) per_cu = 0;
                     } else {
                         for_problem(mo.problem, [&](auto tag) {
                             using P = typename decltype(tag)::type;
@@ -724,8 +769,8 @@ int32_t ctd_jit_check(int32_t problem_id, int32_t scheme) {
     if (scheme == 1) s = env_int("CTD_JIT_CHECK_CS", 0);       // midpoint: controls per step of the kernels to build (default 1)
     std::string code, err;
     std::vector<std::string> names;
-    int32_t st = jit_compile(*ro, "ctd_kernels.hpp", jit_first_exprs(sc, s), "off", code, names, err);
-    if (st == CTD_OK) st = jit_compile(*ro, "ctd_hess_kernels.hpp", jit_hess_exprs(sc, s), "fast", code, names, err);
+    int32_t st = jit_compile(*ro, "ctd_kernels.hpp", jit_first_exprs(sc, s, ""), "off", code, names, err);
+    if (st == CTD_OK) st = jit_compile(*ro, "ctd_hess_kernels.hpp", jit_hess_exprs(sc, s, ""), "fast", code, names, err);
     if (st) return fail(nullptr, st, err);
     return CTD_OK;
 }
@@ -1062,7 +1107,7 @@ int32_t ctd_launch_info(const ctd_handle* h, int64_t* o) {
         DeviceGuard dg(h->device);
         int per_cu = 0;
         if (dg.err == hipSuccess) {
-            if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit[JIT_FIRST].f[0], h->block, h->lds_bytes) != hipSuccess) per_cu = 0; }
+            if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit[JIT_FIRST][0].f[0], h->block, h->lds_bytes) != hipSuccess) per_cu = 0; }
             else for_problem(h->model.problem, [&](auto tag) {
                 using P = typename decltype(tag)::type;
                 per_cu = occupancy_cons_jac<P>(h->kp, h->block, h->lds_bytes);
@@ -1098,7 +1143,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
         if (h->rt) {
             if (const int32_t jst = jit_load(h, JIT_BATCH)) return jst;
             void* args[] = {&kp, &x_dev, &bl};
-            e = jit_launch(h->jit[JIT_BATCH].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
+            e = jit_launch(h->jit[JIT_BATCH][0].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
         }
         for_problem(h->model.problem, [&](auto tag) {
             using P = typename decltype(tag)::type;
@@ -1109,7 +1154,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     }
     if (h->rt) {
         void* args[] = {&kp, &x_dev};
-        e = jit_launch(h->jit[JIT_FIRST].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, te0, te1);
+        e = jit_launch(h->jit[JIT_FIRST][0].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, te0, te1);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1203,8 +1248,8 @@ static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev, co
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&op, &x_dev};
-        e = lagrange ? jit_launch(h->jit[JIT_FIRST].f[1], blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
-        if (e == hipSuccess) e = jit_launch(h->jit[JIT_FIRST].f[2], 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
+        e = lagrange ? jit_launch(h->jit[JIT_FIRST][0].f[1], blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
+        if (e == hipSuccess) e = jit_launch(h->jit[JIT_FIRST][0].f[2], 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1320,8 +1365,8 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&gp, &x_dev};
-        e = lagrange ? jit_launch(h->jit[JIT_FIRST].f[3], blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
-        if (e == hipSuccess) e = jit_launch(h->jit[JIT_FIRST].f[4], 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
+        e = lagrange ? jit_launch(h->jit[JIT_FIRST][0].f[3], blocks, 256, 0, h->stream, args, nullptr, nullptr, nb) : hipSuccess;
+        if (e == hipSuccess) e = jit_launch(h->jit[JIT_FIRST][0].f[4], 1, 64, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
@@ -1339,354 +1384,240 @@ int32_t ctd_grad(ctd_handle* h, const double* x, double* g) {
     return host_call(h, {{x, h->d_x, nvar}}, [&] { return enqueue_grad(h, h->d_x.p, h->d_g.p); }, {{g, h->d_g, nvar}});
 }
 
-// ---- matrix-free Jacobian products: jprod!(nlp, x, v, Jv), jtprod!(nlp, x, w, Jtw) -------------------------------------
-// ctd_prod_kernels.hpp.  Checks in this order: handle, device (CTD_ENODEVICE) -- the prologue, OnDevice(h, fn) --, whole-grid
-// handle (not for the shard calls, which take every handle), then pointers (CTD_EINVAL).  The enqueue runs under the caller's
+// ---- the matrix-free operators (rows: kJprod ... kJsqRows above) ---------------------------------------------------------
+// jprod!(nlp, x, v, Jv), jtprod!(nlp, x, w, Jtw): ctd_prod_kernels.hpp; hprod!(nlp, x, y, v, Hv; obj_weight): ctd_hprod_kernels.hpp;
+// the KKT product rx = (sigma H_f + sum y_r H_{c_r}) dx + J' dy + sx o dx, rc = J dx - sc o dy: ctd_kkt_kernels.hpp; the KKT
+// diagonals diag(H), diag(J W J') (row sums) and diag(J' W J) (column sums): ctd_diag_kernels.hpp.
+//
+// The checks of every entry point, in this order: handle (CTD_EINVAL), device (CTD_ENODEVICE) -- the prologue, OnDevice(h, fn) --,
+// whole-grid handle (not for the shard calls, which take every handle), the required pointers -- `req` and `out`; `opt` may be
+// null --, then every output against every input and against the other outputs (CTD_EINVAL).  The enqueue runs under the caller's
 // prologue.
-static int32_t prod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* d, const double* out,
-                          bool shard = false) {
+static int32_t mf_check(const OnDevice& on, ctd_handle* h, const MfCall& c, std::initializer_list<const double*> req,
+                        std::initializer_list<const double*> opt, std::initializer_list<const double*> out) {
     if (on.st) return on.st;
-    if (!shard && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; on a shard handle (step_begin / "
-                                   "step_end, ctd_set_x_shards) call ctd_jprod_shard_dev_async, ctd_jtprod_shard_dev_async or "
-                                   "ctd_hprod_shard_dev_async");
-    if (!x || !d || !out) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument");
-    if (out == x || out == d) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
+    if (!c.shard() && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
+        return fail(h, CTD_EINVAL, std::string(c.fn()) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
+                                   "step_end, ctd_set_x_shards) is out of scope for this call: a shard handle calls " + c.op.name[MF_SHARD]);
+    for (const auto& ptrs : {req, out})
+        for (const double* p : ptrs)
+            if (!p) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": null argument (" + c.op.required + " are required)");
+    for (const double* const* o = out.begin(); o != out.end(); ++o) {
+        for (const auto& ptrs : {req, opt})
+            for (const double* p : ptrs)
+                if (p == *o) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": the output (" + c.op.outs + ") must not be an input buffer");
+        for (const double* const* o2 = out.begin(); o2 != o; ++o2)
+            if (*o2 == *o) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": " + c.op.outs + " must be different buffers");
+    }
     return CTD_OK;
 }
 
-// The nodes a product launch evaluates.  Whole grid: all N + 1.  shard: the nodes of the handle's steps [step_begin, step_end),
-// node N too on the last shard; the iterate's entries of other shards through the handle's table when one is set
-static void prod_units(const ctd_handle* h, ProdParams& pp, bool shard) {
+// The kernels' common arguments: the inputs, and the nodes the launch evaluates.  Whole grid: all N + 1.  Shard call: the nodes of
+// the handle's steps [step_begin, step_end), node N too on the last shard; the iterate's entries of other shards through the
+// handle's table when one is set
+static ProdParams prod_params(const ctd_handle* h, const MfCall& c, const double* dir_dev, double* out_dev) {
+    ProdParams pp;
+    std::memset(&pp, 0, sizeof(pp));
     const int64_t N = h->model.L.N;
-    const bool first = !shard || h->step_begin == 0, last = !shard || h->step_end == N;
+    const bool shard = c.shard(), first = !shard || h->step_begin == 0, last = !shard || h->step_end == N;
+    pp.L = h->model.L;
+    pp.tau = h->d_tau.p;
+    pp.dir = dir_dev;
+    pp.out = out_dev;
     pp.unit_begin = shard ? h->step_begin : 0;
     pp.unit_end = last ? N + 1 : h->step_end;
     pp.owns_first = first ? 1 : 0;
     pp.owns_last = last ? 1 : 0;
     if (shard) { pp.halo = h->kp.halo; pp.near = h->kp.near; }
+    return pp;
 }
 
-static int32_t enqueue_prod(ctd_handle* h, bool transpose, const double* x_dev, const double* d_dev, double* out_dev, bool shard = false) {
-    const char* fn = transpose ? (shard ? "ctd_jtprod_shard_dev_async" : "ctd_jtprod") : (shard ? "ctd_jprod_shard_dev_async" : "ctd_jprod");
-    const JitFamily fam = shard ? JIT_PROD_SHARD : JIT_PROD;
-    if (const int32_t st = jit_load(h, fam)) return st;
-    const Layout& L = h->model.L;
-    ProdParams pp;
-    std::memset(&pp, 0, sizeof(pp));
-    pp.L = L;
-    pp.tau = h->d_tau.p;
-    pp.dir = d_dev;
-    pp.out = out_dev;
-    prod_units(h, pp, shard);
-    hipError_t e = hipErrorInvalidValue;
-    if (!transpose) {
-        if (h->rt) {
-            void* args[] = {&pp, &x_dev};
-            e = jit_launch(h->jit[fam].f[0], (int)((pp.unit_end - pp.unit_begin + 255) / 256), 256, 0, h->stream, args);
-        }
-        for_problem(h->model.problem, [&](auto tag) {
-            using P = typename decltype(tag)::type;
-            e = shard ? launch_jprod<P, true>(pp, x_dev, h->stream) : launch_jprod<P, false>(pp, x_dev, h->stream);
+static int32_t enqueue_prod(ctd_handle* h, const MfCall& c, const double* x_dev, const double* d_dev, double* out_dev) {
+    if (const int32_t st = jit_load(h, c.op.fam, c.shard())) return st;
+    ProdParams pp = prod_params(h, c, d_dev, out_dev);
+    if (c.op.one_launch)
+        return enqueue_prod_launch(h, c, pp, x_dev, [&](auto tag, auto sh) {
+            return launch_jprod<typename decltype(tag)::type, decltype(sh)::value>(pp, x_dev, h->stream);
         });
-    } else {
-        int jc = 1;
-        if (h->rt) jc = jtprod_chunk(h->rt->info.n, h->rt->dc);
-        for_problem(h->model.problem, [&](auto tag) { jc = ProdDirs<typename decltype(tag)::type>::JC; });
-        return enqueue_prod_units<JtprodKernels>(h, fn, pp, prod_dirs_per_node(L), jc, h->d_ppartial, h->jit[fam], 1, x_dev, shard);
-    }
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return enqueue_prod_units<JtprodKernels>(h, c, pp, prod_dirs_per_node(pp.L), prod_chunk<ProdDirs>(h, jtprod_chunk), h->d_ppartial, x_dev);
 }
 
-int32_t ctd_jprod_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
-    const OnDevice on(h, "ctd_jprod_dev_async");
-    const int32_t st = prod_check(on, h, "ctd_jprod_dev_async", x_dev, v_dev, Jv_dev);
-    return st ? st : enqueue_prod(h, false, x_dev, v_dev, Jv_dev);
-}
-int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
-    const OnDevice on(h, "ctd_jtprod_dev_async");
-    const int32_t st = prod_check(on, h, "ctd_jtprod_dev_async", x_dev, w_dev, Jtw_dev);
-    return st ? st : enqueue_prod(h, true, x_dev, w_dev, Jtw_dev);
-}
-// the shard's own rows of Jv / entries of Jtw (+ its partial sums of d/dv) from full-length buffers (see include/ctdirect_hip.h)
-int32_t ctd_jprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
-    const OnDevice on(h, "ctd_jprod_shard_dev_async");
-    const int32_t st = prod_check(on, h, "ctd_jprod_shard_dev_async", x_dev, v_dev, Jv_dev, true);
-    return st ? st : enqueue_prod(h, false, x_dev, v_dev, Jv_dev, true);
-}
-int32_t ctd_jtprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
-    const OnDevice on(h, "ctd_jtprod_shard_dev_async");
-    const int32_t st = prod_check(on, h, "ctd_jtprod_shard_dev_async", x_dev, w_dev, Jtw_dev, true);
-    return st ? st : enqueue_prod(h, true, x_dev, w_dev, Jtw_dev, true);
-}
-
-// host pointers: staged through the handle's x buffer and two vectors of nvar / ncon entries
-static int32_t host_prod(ctd_handle* h, bool transpose, const double* x, const double* d, double* out) {
-    const char* fn = transpose ? "ctd_jtprod" : "ctd_jprod";
-    const OnDevice on(h, fn);
-    const int32_t st = prod_check(on, h, fn, x, d, out);
-    if (st) return st;
-    const Layout& L = h->model.L;
-    return host_call(h, {{x, h->d_x, L.nvar}, {d, h->d_pdir, transpose ? L.ncon : L.nvar}},
-                     [&] { return enqueue_prod(h, transpose, h->d_x.p, h->d_pdir.p, h->d_pout.p); },
-                     {{out, h->d_pout, transpose ? L.nvar : L.ncon}});
-}
-int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv) { return host_prod(h, false, x, v, Jv); }
-int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw) { return host_prod(h, true, x, w, Jtw); }
-
-// ---- matrix-free Hessian products: hprod!(nlp, x, y, v, Hv; obj_weight) ------------------------------------------------
-// ctd_hprod_kernels.hpp.  Checks in the order of prod_check; y may be null (objective only) but Hv must not alias it.
-static int32_t hprod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* y, const double* v,
-                           const double* out, bool shard = false) {
-    const int32_t st = prod_check(on, h, fn, x, v, out, shard);
-    if (st) return st;
-    if (y && out == y) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
-    return CTD_OK;
-}
-
-static int32_t enqueue_hprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
-                             double* out_dev, bool shard = false) {
-    const char* fn = shard ? "ctd_hprod_shard_dev_async" : "ctd_hprod";
-    const JitFamily fam = shard ? JIT_HPROD_SHARD : JIT_HPROD;
-    if (const int32_t st = jit_load(h, fam)) return st;
-    const Layout& L = h->model.L;
+static int32_t enqueue_hprod(ctd_handle* h, const MfCall& c, const double* x_dev, const double* y_dev, double obj_weight,
+                             const double* v_dev, double* out_dev) {
+    if (const int32_t st = jit_load(h, c.op.fam, c.shard())) return st;
     HProdParams hp;
     std::memset(&hp, 0, sizeof(hp));
-    hp.p.L = L;
-    hp.p.tau = h->d_tau.p;
-    hp.p.dir = y_dev;
-    hp.p.out = out_dev;
+    hp.p = prod_params(h, c, y_dev, out_dev);
     hp.vt = v_dev;
     hp.sigma = obj_weight;
-    prod_units(h, hp.p, shard);
-    int jc = 1;
-    if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
-    for_problem(h->model.problem, [&](auto tag) { jc = HProdDirs<typename decltype(tag)::type>::JC; });
-    return enqueue_prod_units<HprodKernels>(h, fn, hp, hprod_dirs_per_node(L), jc, h->d_hppartial, h->jit[fam], 0, x_dev, shard);
+    return enqueue_prod_units<HprodKernels>(h, c, hp, hprod_dirs_per_node(hp.p.L), prod_chunk<HProdDirs>(h, hprod_chunk), h->d_hppartial, x_dev);
 }
 
-int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
-                            double* Hv_dev) {
-    const OnDevice on(h, "ctd_hprod_dev_async");
-    const int32_t st = hprod_check(on, h, "ctd_hprod_dev_async", x_dev, y_dev, v_dev, Hv_dev);
-    return st ? st : enqueue_hprod(h, x_dev, y_dev, obj_weight, v_dev, Hv_dev);
-}
-// the shard's own entries of Hv + its partial sums of d/dv (see include/ctdirect_hip.h)
-int32_t ctd_hprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
-                                  double* Hv_dev) {
-    const OnDevice on(h, "ctd_hprod_shard_dev_async");
-    const int32_t st = hprod_check(on, h, "ctd_hprod_shard_dev_async", x_dev, y_dev, v_dev, Hv_dev, true);
-    return st ? st : enqueue_hprod(h, x_dev, y_dev, obj_weight, v_dev, Hv_dev, true);
-}
-
-// host pointers: x, y and v staged through the handle's x, y and direction buffers
-int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* v, double* Hv) {
-    const OnDevice on(h, "ctd_hprod");
-    const int32_t st = hprod_check(on, h, "ctd_hprod", x, y, v, Hv);
-    if (st) return st;
-    const Layout& L = h->model.L;
-    return host_call(h, {{x, h->d_x, L.nvar}, {v, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}},
-                     [&] { return enqueue_hprod(h, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_pout.p); },
-                     {{Hv, h->d_pout, L.nvar}});
-}
-
-// ---- matrix-free KKT products: rx = (sigma H_f + sum y_r H_{c_r}) dx + J' dy + sx o dx, rc = J dx - sc o dy ------------------
-// ctd_kkt_kernels.hpp.  Checks in the order of prod_check: handle, device, whole-grid handle (not for the shard call, which takes
-// every handle), the required pointers, then the outputs against every input and against each other.
-static int32_t kktprod_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* y, const double* dx,
-                             const double* dy, const double* sx, const double* sc, const double* rx, const double* rc,
-                             bool shard = false) {
-    if (on.st) return on.st;
-    if (!shard && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
-                                   "step_end, ctd_set_x_shards) is out of scope for this call: a shard handle calls "
-                                   "ctd_kktprod_shard_dev_async");
-    if (!x || !dx || !dy || !rx || !rc) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (x, dx, dy, rx and rc are required)");
-    for (const double* in : {x, y, dx, dy, sx, sc})
-        if (in && (in == rx || in == rc)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
-    if (rx == rc) return fail(h, CTD_EINVAL, std::string(fn) + ": rx and rc must be different buffers");
-    return CTD_OK;
-}
-
-static int32_t enqueue_kktprod(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
-                               const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev,
-                               bool shard = false) {
-    const char* fn = shard ? "ctd_kktprod_shard_dev_async" : "ctd_kktprod";
-    const JitFamily fam = shard ? JIT_KKT_SHARD : JIT_KKT;
-    if (const int32_t st = jit_load(h, fam)) return st;
-    const Layout& L = h->model.L;
+static int32_t enqueue_kktprod(ctd_handle* h, const MfCall& c, const double* x_dev, const double* y_dev, double obj_weight,
+                               const double* dx_dev, const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev,
+                               double* rc_dev) {
+    if (const int32_t st = jit_load(h, c.op.fam, c.shard())) return st;
     KktParams kp;
     std::memset(&kp, 0, sizeof(kp));
-    kp.h.p.L = L;
-    kp.h.p.tau = h->d_tau.p;
-    kp.h.p.dir = y_dev;
-    kp.h.p.out = rx_dev;
+    kp.h.p = prod_params(h, c, y_dev, rx_dev);
     kp.h.vt = dx_dev;
     kp.h.sigma = obj_weight;
     kp.dy = dy_dev;
     kp.sx = sx_dev;
     kp.sc = sc_dev;
     kp.rc = rc_dev;
-    prod_units(h, kp.h.p, shard);
-    int jc = 1;         // the fused lanes keep the hprod chunk rule (profiles/kktprod_resources.md)
-    if (h->rt) jc = hprod_chunk(h->rt->info.n, h->rt->dc);
-    for_problem(h->model.problem, [&](auto tag) { jc = HProdDirs<typename decltype(tag)::type>::JC; });
-    return enqueue_prod_units<KktKernels>(h, fn, kp, hprod_dirs_per_node(L), jc, h->d_kktpartial, h->jit[fam], 0, x_dev, shard);
+    // the fused lanes keep the hprod chunk rule (profiles/kktprod_resources.md)
+    return enqueue_prod_units<KktKernels>(h, c, kp, hprod_dirs_per_node(kp.h.p.L), prod_chunk<HProdDirs>(h, hprod_chunk), h->d_kktpartial, x_dev);
 }
 
-int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
-                              const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
-    const OnDevice on(h, "ctd_kktprod_dev_async");
-    const int32_t st = kktprod_check(on, h, "ctd_kktprod_dev_async", x_dev, y_dev, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
-    return st ? st : enqueue_kktprod(h, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
+static int32_t enqueue_hdiag(ctd_handle* h, const MfCall& c, const double* x_dev, const double* y_dev, double obj_weight, double* out_dev) {
+    if (const int32_t st = jit_load(h, c.op.fam, c.shard())) return st;
+    HProdParams hp;
+    std::memset(&hp, 0, sizeof(hp));
+    hp.p = prod_params(h, c, y_dev, out_dev);
+    hp.sigma = obj_weight;
+    // one direction per lane: tangent and seed are the same unit vector
+    return enqueue_prod_units<HdiagKernels>(h, c, hp, hprod_dirs_per_node(hp.p.L), 1, h->d_hdpartial, x_dev);
 }
 
-// the shard's own entries of rx (+ its partial sums of d/dv) and its own rows of rc (see include/ctdirect_hip.h)
-int32_t ctd_kktprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
-                                    const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
-    const OnDevice on(h, "ctd_kktprod_shard_dev_async");
-    const int32_t st = kktprod_check(on, h, "ctd_kktprod_shard_dev_async", x_dev, y_dev, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev,
-                                     true);
-    return st ? st : enqueue_kktprod(h, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev, true);
+// jsq_rows: out = diag(J diag(w) J') (ncon), one launch; jsq_cols: out = diag(J' diag(w) J) (nvar), units + finish
+static int32_t enqueue_jsq(ctd_handle* h, const MfCall& c, const double* x_dev, const double* w_dev, double* out_dev) {
+    if (const int32_t st = jit_load(h, c.op.fam, c.shard())) return st;
+    ProdParams pp = prod_params(h, c, w_dev, out_dev);
+    if (c.op.one_launch)
+        return enqueue_prod_launch(h, c, pp, x_dev, [&](auto tag, auto sh) {
+            return launch_jsq_rows<typename decltype(tag)::type, decltype(sh)::value>(pp, x_dev, h->stream);
+        });
+    // the general lane for every scheme: the node's block and v (hprod's directions, not the Gauss-Legendre shortcut's)
+    return enqueue_prod_units<JsqColsKernels>(h, c, pp, hprod_dirs_per_node(pp.L), prod_chunk<JsqDirs>(h, jsq_chunk), h->d_jcpartial, x_dev);
 }
 
-// host pointers: x, y, dx and rx staged as for ctd_hprod; dy, sx, sc and rc through buffers of their own
-int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* dx, const double* dy,
-                    const double* sx, const double* sc, double* rx, double* rc) {
-    const OnDevice on(h, "ctd_kktprod");
-    const int32_t st = kktprod_check(on, h, "ctd_kktprod", x, y, dx, dy, sx, sc, rx, rc);
-    if (st) return st;
+// The entry points of each operator: prologue, checks, then the enqueue on the caller's device pointers -- or, for the host form, on
+// the handle's staging buffers: x in d_x, y in d_y, the direction (v, w, dx, the weights) in d_pdir, the result in d_pout; dy, sx,
+// sc and rc of ctd_kktprod in buffers of their own.  Vectors of nvar / ncon entries: nothing proportional to nnzj
+static int32_t mf_prod(ctd_handle* h, const MfCall& c, const double* x, const double* d, double* out) {
+    const OnDevice on(h, c.fn());
+    if (const int32_t st = mf_check(on, h, c, {x, d}, {}, {out})) return st;
+    if (c.form != MF_HOST) return enqueue_prod(h, c, x, d, out);
+    const Layout& L = h->model.L;
+    return host_call(h, {{x, h->d_x, L.nvar}, {d, h->d_pdir, c.op.dir_ncon ? L.ncon : L.nvar}},
+                     [&] { return enqueue_prod(h, c, h->d_x.p, h->d_pdir.p, h->d_pout.p); },
+                     {{out, h->d_pout, c.op.out_ncon ? L.ncon : L.nvar}});
+}
+
+// y may be null: the objective only
+static int32_t mf_hprod(ctd_handle* h, const MfCall& c, const double* x, const double* y, double obj_weight, const double* v, double* Hv) {
+    const OnDevice on(h, c.fn());
+    if (const int32_t st = mf_check(on, h, c, {x, v}, {y}, {Hv})) return st;
+    if (c.form != MF_HOST) return enqueue_hprod(h, c, x, y, obj_weight, v, Hv);
+    const Layout& L = h->model.L;
+    return host_call(h, {{x, h->d_x, L.nvar}, {v, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}},
+                     [&] { return enqueue_hprod(h, c, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_pout.p); },
+                     {{Hv, h->d_pout, L.nvar}});
+}
+
+// y, sx and sc may be null: no multipliers, no diagonal term
+static int32_t mf_kktprod(ctd_handle* h, const MfCall& c, const double* x, const double* y, double obj_weight, const double* dx,
+                          const double* dy, const double* sx, const double* sc, double* rx, double* rc) {
+    const OnDevice on(h, c.fn());
+    if (const int32_t st = mf_check(on, h, c, {x, dx, dy}, {y, sx, sc}, {rx, rc})) return st;
+    if (c.form != MF_HOST) return enqueue_kktprod(h, c, x, y, obj_weight, dx, dy, sx, sc, rx, rc);
     const Layout& L = h->model.L;
     return host_call(h, {{x, h->d_x, L.nvar}, {dx, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}, {dy, h->d_kdy, L.ncon},
                          {sx, h->d_ksx, L.nvar}, {sc, h->d_ksc, L.ncon}},
                      [&] {
-                         return enqueue_kktprod(h, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_kdy.p,
+                         return enqueue_kktprod(h, c, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_kdy.p,
                                                 sx ? h->d_ksx.p : nullptr, sc ? h->d_ksc.p : nullptr, h->d_pout.p, h->d_krc.p);
                      },
                      {{rx, h->d_pout, L.nvar}, {rc, h->d_krc, L.ncon}});
 }
 
-// ---- matrix-free KKT diagonals: diag(H), the row sums diag(J W J') and the column sums diag(J' W J) -----------------------------
-// ctd_diag_kernels.hpp.  Checks in the order of kktprod_check: handle, device, whole-grid handle (not for the shard calls, which
-// take every handle), the required pointers (x and the output), then the output against every input.  a: the optional input
-// (multipliers or weights).
-static int32_t diag_check(const OnDevice& on, ctd_handle* h, const char* fn, const double* x, const double* a, const double* out,
-                          bool shard = false) {
-    if (on.st) return on.st;
-    if (!shard && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
-                                   "step_end, ctd_set_x_shards) is out of scope for this call: a shard handle calls "
-                                   "ctd_hdiag_shard_dev_async, ctd_jsq_rows_shard_dev_async or ctd_jsq_cols_shard_dev_async");
-    if (!x || !out) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (x and the output are required)");
-    if (out == x || (a && out == a)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output must not be an input buffer");
-    return CTD_OK;
-}
-
-static int32_t enqueue_hdiag(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* out_dev, bool shard = false) {
-    const char* fn = shard ? "ctd_hdiag_shard_dev_async" : "ctd_hdiag";
-    const JitFamily fam = shard ? JIT_DIAG_SHARD : JIT_DIAG;
-    if (const int32_t st = jit_load(h, fam)) return st;
-    HProdParams hp;
-    std::memset(&hp, 0, sizeof(hp));
-    hp.p.L = h->model.L;
-    hp.p.tau = h->d_tau.p;
-    hp.p.dir = y_dev;
-    hp.p.out = out_dev;
-    hp.sigma = obj_weight;
-    prod_units(h, hp.p, shard);
-    // one direction per lane: tangent and seed are the same unit vector
-    return enqueue_prod_units<HdiagKernels>(h, fn, hp, hprod_dirs_per_node(hp.p.L), 1, h->d_hdpartial, h->jit[fam], 0, x_dev, shard);
-}
-
-// rows: out = diag(J diag(w) J') (ncon), one launch; otherwise out = diag(J' diag(w) J) (nvar), units + finish
-static int32_t enqueue_jsq(ctd_handle* h, bool rows, const double* x_dev, const double* w_dev, double* out_dev, bool shard = false) {
-    const char* fn = rows ? (shard ? "ctd_jsq_rows_shard_dev_async" : "ctd_jsq_rows") : (shard ? "ctd_jsq_cols_shard_dev_async" : "ctd_jsq_cols");
-    const JitFamily fam = shard ? JIT_DIAG_SHARD : JIT_DIAG;
-    if (const int32_t st = jit_load(h, fam)) return st;
-    const Layout& L = h->model.L;
-    ProdParams pp;
-    std::memset(&pp, 0, sizeof(pp));
-    pp.L = L;
-    pp.tau = h->d_tau.p;
-    pp.dir = w_dev;
-    pp.out = out_dev;
-    prod_units(h, pp, shard);
-    if (!rows) {
-        int jc = 1;
-        if (h->rt) jc = jsq_chunk(h->rt->info.n, h->rt->dc);
-        for_problem(h->model.problem, [&](auto tag) { jc = JsqDirs<typename decltype(tag)::type>::JC; });
-        // the general lane for every scheme: the node's block and v (hprod's directions, not the Gauss-Legendre shortcut's)
-        return enqueue_prod_units<JsqColsKernels>(h, fn, pp, hprod_dirs_per_node(L), jc, h->d_jcpartial, h->jit[fam], 2, x_dev, shard);
-    }
-    hipError_t e = hipErrorInvalidValue;
-    if (h->rt) {
-        void* args[] = {&pp, &x_dev};
-        e = jit_launch(h->jit[fam].f[4], (int)((pp.unit_end - pp.unit_begin + 255) / 256), 256, 0, h->stream, args);
-    }
-    for_problem(h->model.problem, [&](auto tag) {
-        using P = typename decltype(tag)::type;
-        e = shard ? launch_jsq_rows<P, true>(pp, x_dev, h->stream) : launch_jsq_rows<P, false>(pp, x_dev, h->stream);
-    });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
-}
-
-int32_t ctd_hdiag_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev) {
-    const OnDevice on(h, "ctd_hdiag_dev_async");
-    const int32_t st = diag_check(on, h, "ctd_hdiag_dev_async", x_dev, y_dev, Hd_dev);
-    return st ? st : enqueue_hdiag(h, x_dev, y_dev, obj_weight, Hd_dev);
-}
-int32_t ctd_jsq_rows_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev) {
-    const OnDevice on(h, "ctd_jsq_rows_dev_async");
-    const int32_t st = diag_check(on, h, "ctd_jsq_rows_dev_async", x_dev, wx_dev, out_dev);
-    return st ? st : enqueue_jsq(h, true, x_dev, wx_dev, out_dev);
-}
-int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev) {
-    const OnDevice on(h, "ctd_jsq_cols_dev_async");
-    const int32_t st = diag_check(on, h, "ctd_jsq_cols_dev_async", x_dev, wc_dev, out_dev);
-    return st ? st : enqueue_jsq(h, false, x_dev, wc_dev, out_dev);
-}
-
-// the shard's own entries of Hd / of the column sums (+ its partial sums of the nv entries) and its own rows of the row sums, from
-// full-length buffers (see include/ctdirect_hip.h)
-int32_t ctd_hdiag_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev) {
-    const OnDevice on(h, "ctd_hdiag_shard_dev_async");
-    const int32_t st = diag_check(on, h, "ctd_hdiag_shard_dev_async", x_dev, y_dev, Hd_dev, true);
-    return st ? st : enqueue_hdiag(h, x_dev, y_dev, obj_weight, Hd_dev, true);
-}
-int32_t ctd_jsq_rows_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev) {
-    const OnDevice on(h, "ctd_jsq_rows_shard_dev_async");
-    const int32_t st = diag_check(on, h, "ctd_jsq_rows_shard_dev_async", x_dev, wx_dev, out_dev, true);
-    return st ? st : enqueue_jsq(h, true, x_dev, wx_dev, out_dev, true);
-}
-int32_t ctd_jsq_cols_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev) {
-    const OnDevice on(h, "ctd_jsq_cols_shard_dev_async");
-    const int32_t st = diag_check(on, h, "ctd_jsq_cols_shard_dev_async", x_dev, wc_dev, out_dev, true);
-    return st ? st : enqueue_jsq(h, false, x_dev, wc_dev, out_dev, true);
-}
-
-// host pointers: x, y and the weights staged through the handle's x, y and direction buffers, the result through d_pout
-int32_t ctd_hdiag(ctd_handle* h, const double* x, const double* y, double obj_weight, double* Hd) {
-    const OnDevice on(h, "ctd_hdiag");
-    const int32_t st = diag_check(on, h, "ctd_hdiag", x, y, Hd);
-    if (st) return st;
+// y may be null: the objective only
+static int32_t mf_hdiag(ctd_handle* h, const MfCall& c, const double* x, const double* y, double obj_weight, double* Hd) {
+    const OnDevice on(h, c.fn());
+    if (const int32_t st = mf_check(on, h, c, {x}, {y}, {Hd})) return st;
+    if (c.form != MF_HOST) return enqueue_hdiag(h, c, x, y, obj_weight, Hd);
     const Layout& L = h->model.L;
     return host_call(h, {{x, h->d_x, L.nvar}, {y, h->d_y, L.ncon}},
-                     [&] { return enqueue_hdiag(h, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pout.p); }, {{Hd, h->d_pout, L.nvar}});
+                     [&] { return enqueue_hdiag(h, c, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pout.p); }, {{Hd, h->d_pout, L.nvar}});
 }
-static int32_t host_jsq(ctd_handle* h, bool rows, const double* x, const double* w, double* out) {
-    const char* fn = rows ? "ctd_jsq_rows" : "ctd_jsq_cols";
-    const OnDevice on(h, fn);
-    const int32_t st = diag_check(on, h, fn, x, w, out);
-    if (st) return st;
+
+// w may be null: ones
+static int32_t mf_jsq(ctd_handle* h, const MfCall& c, const double* x, const double* w, double* out) {
+    const OnDevice on(h, c.fn());
+    if (const int32_t st = mf_check(on, h, c, {x}, {w}, {out})) return st;
+    if (c.form != MF_HOST) return enqueue_jsq(h, c, x, w, out);
     const Layout& L = h->model.L;
-    return host_call(h, {{x, h->d_x, L.nvar}, {w, h->d_pdir, rows ? L.nvar : L.ncon}},
-                     [&] { return enqueue_jsq(h, rows, h->d_x.p, w ? h->d_pdir.p : nullptr, h->d_pout.p); },
-                     {{out, h->d_pout, rows ? L.ncon : L.nvar}});
+    return host_call(h, {{x, h->d_x, L.nvar}, {w, h->d_pdir, c.op.dir_ncon ? L.ncon : L.nvar}},
+                     [&] { return enqueue_jsq(h, c, h->d_x.p, w ? h->d_pdir.p : nullptr, h->d_pout.p); },
+                     {{out, h->d_pout, c.op.out_ncon ? L.ncon : L.nvar}});
 }
-int32_t ctd_jsq_rows(ctd_handle* h, const double* x, const double* wx, double* out) { return host_jsq(h, true, x, wx, out); }
-int32_t ctd_jsq_cols(ctd_handle* h, const double* x, const double* wc, double* out) { return host_jsq(h, false, x, wc, out); }
+
+// The shard calls write the shard's own rows (jprod, jsq_rows, rc) or the entries of its own variables + its partial sums of the nv
+// tail entries, from full-length buffers (see include/ctdirect_hip.h)
+int32_t ctd_jprod(ctd_handle* h, const double* x, const double* v, double* Jv) { return mf_prod(h, {kJprod, MF_HOST}, x, v, Jv); }
+int32_t ctd_jprod_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
+    return mf_prod(h, {kJprod, MF_DEV}, x_dev, v_dev, Jv_dev);
+}
+int32_t ctd_jprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* v_dev, double* Jv_dev) {
+    return mf_prod(h, {kJprod, MF_SHARD}, x_dev, v_dev, Jv_dev);
+}
+int32_t ctd_jtprod(ctd_handle* h, const double* x, const double* w, double* Jtw) { return mf_prod(h, {kJtprod, MF_HOST}, x, w, Jtw); }
+int32_t ctd_jtprod_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
+    return mf_prod(h, {kJtprod, MF_DEV}, x_dev, w_dev, Jtw_dev);
+}
+int32_t ctd_jtprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* w_dev, double* Jtw_dev) {
+    return mf_prod(h, {kJtprod, MF_SHARD}, x_dev, w_dev, Jtw_dev);
+}
+
+int32_t ctd_hprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* v, double* Hv) {
+    return mf_hprod(h, {kHprod, MF_HOST}, x, y, obj_weight, v, Hv);
+}
+int32_t ctd_hprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                            double* Hv_dev) {
+    return mf_hprod(h, {kHprod, MF_DEV}, x_dev, y_dev, obj_weight, v_dev, Hv_dev);
+}
+int32_t ctd_hprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* v_dev,
+                                  double* Hv_dev) {
+    return mf_hprod(h, {kHprod, MF_SHARD}, x_dev, y_dev, obj_weight, v_dev, Hv_dev);
+}
+
+int32_t ctd_kktprod(ctd_handle* h, const double* x, const double* y, double obj_weight, const double* dx, const double* dy,
+                    const double* sx, const double* sc, double* rx, double* rc) {
+    return mf_kktprod(h, {kKktprod, MF_HOST}, x, y, obj_weight, dx, dy, sx, sc, rx, rc);
+}
+int32_t ctd_kktprod_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                              const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
+    return mf_kktprod(h, {kKktprod, MF_DEV}, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
+}
+int32_t ctd_kktprod_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, const double* dx_dev,
+                                    const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev, double* rc_dev) {
+    return mf_kktprod(h, {kKktprod, MF_SHARD}, x_dev, y_dev, obj_weight, dx_dev, dy_dev, sx_dev, sc_dev, rx_dev, rc_dev);
+}
+
+int32_t ctd_hdiag(ctd_handle* h, const double* x, const double* y, double obj_weight, double* Hd) {
+    return mf_hdiag(h, {kHdiag, MF_HOST}, x, y, obj_weight, Hd);
+}
+int32_t ctd_hdiag_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev) {
+    return mf_hdiag(h, {kHdiag, MF_DEV}, x_dev, y_dev, obj_weight, Hd_dev);
+}
+int32_t ctd_hdiag_shard_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* Hd_dev) {
+    return mf_hdiag(h, {kHdiag, MF_SHARD}, x_dev, y_dev, obj_weight, Hd_dev);
+}
+int32_t ctd_jsq_rows(ctd_handle* h, const double* x, const double* wx, double* out) { return mf_jsq(h, {kJsqRows, MF_HOST}, x, wx, out); }
+int32_t ctd_jsq_rows_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev) {
+    return mf_jsq(h, {kJsqRows, MF_DEV}, x_dev, wx_dev, out_dev);
+}
+int32_t ctd_jsq_rows_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev) {
+    return mf_jsq(h, {kJsqRows, MF_SHARD}, x_dev, wx_dev, out_dev);
+}
+int32_t ctd_jsq_cols(ctd_handle* h, const double* x, const double* wc, double* out) { return mf_jsq(h, {kJsqCols, MF_HOST}, x, wc, out); }
+int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev) {
+    return mf_jsq(h, {kJsqCols, MF_DEV}, x_dev, wc_dev, out_dev);
+}
+int32_t ctd_jsq_cols_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev) {
+    return mf_jsq(h, {kJsqCols, MF_SHARD}, x_dev, wc_dev, out_dev);
+}
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {
     const OnDevice on(h);
@@ -1922,8 +1853,8 @@ static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
         void* args[] = {&hp, &x_dev, &y_dev};
-        e = jit_launch(h->jit[JIT_HESS].f[0], hp.ntiles + hp.n_edge_blocks, kHessBlock, h->hess_lds_bytes, h->stream, args, te0, te1, nb);
-        if (e == hipSuccess && hp.nvv > 0) e = jit_launch(h->jit[JIT_HESS].f[1], 1, kHessBlock, 0, h->stream, args, nullptr, nullptr, nb);
+        e = jit_launch(h->jit[JIT_HESS][0].f[0], hp.ntiles + hp.n_edge_blocks, kHessBlock, h->hess_lds_bytes, h->stream, args, te0, te1, nb);
+        if (e == hipSuccess && hp.nvv > 0) e = jit_launch(h->jit[JIT_HESS][0].f[1], 1, kHessBlock, 0, h->stream, args, nullptr, nullptr, nb);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;

@@ -86,6 +86,32 @@ def _is_tensor(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
 
+# The matrix-free operators, one row each (DOCP._mf): the vector inputs in the order of the C arguments, x first, as (name, layout,
+# required) -- layout "v": dim_NLP_variables entries, "c": dim_NLP_constraints --; the number of them that the scalar arguments
+# follow; the outputs as (name, layout).  The entry points are ctd_<op> (host pointers), ctd_<op>_dev_async and
+# ctd_<op>_shard_dev_async
+_MF_OPS = {
+    "jprod": ((("x", "v", True), ("v", "v", True)), 2, (("out", "c"),)),
+    "jtprod": ((("x", "v", True), ("w", "c", True)), 2, (("out", "v"),)),
+    "hprod": ((("x", "v", True), ("y", "c", False), ("v", "v", True)), 2, (("out", "v"),)),
+    "kktprod": ((("x", "v", True), ("y", "c", False), ("dx", "v", True), ("dy", "c", True), ("sx", "v", False), ("sc", "c", False)), 2,
+                (("out[0]", "v"), ("out[1]", "c"))),
+    "hdiag": ((("x", "v", True), ("y", "c", False)), 2, (("out", "v"),)),
+    "jsq_rows": ((("x", "v", True), ("wx", "v", False)), 2, (("out", "c"),)),
+    "jsq_cols": ((("x", "v", True), ("wc", "c", False)), 2, (("out", "v"),)),
+}
+
+
+def _mf_rows(L, nvar, ncon):
+    """_MF_OPS for one handle, per operator: the names and the lengths of its vectors, inputs then outputs; the number of inputs;
+    the positions of the required inputs; the position of the scalars; the three entry points of the library L"""
+    n = {"v": nvar, "c": ncon}
+    return {op: (tuple(nm for nm, *_ in ins + outs), tuple(n[row[1]] for row in ins + outs), len(ins),
+                 tuple(i for i, row in enumerate(ins) if row[2]), k,
+                 (getattr(L, f"ctd_{op}"), getattr(L, f"ctd_{op}_dev_async"), getattr(L, f"ctd_{op}_shard_dev_async")))
+            for op, (ins, k, outs) in _MF_OPS.items()}
+
+
 def register_ocp(name, *, dynamics, n=None, m=0, nv=0, lagrange=None, mayer=None, path=(), boundary=(), constants=None,
                  t0=0.0, tf=1.0, it0=-1, itf=-1, maximize=False, state_box=None, control_box=None, variable_box=None,
                  path_bounds=None, boundary_bounds=None):
@@ -248,6 +274,8 @@ class DOCP:
         nvar, ncon, nnzj, nnzh = (C.c_int64() for _ in range(4))
         self._ck(L.ctd_sizes(self._h, C.byref(nvar), C.byref(ncon), C.byref(nnzj), C.byref(nnzh)))
         self.dim_NLP_variables, self.dim_NLP_constraints = nvar.value, ncon.value
+        self._mf_rows = _mf_rows(L, nvar.value, ncon.value)
+        self._f64 = None
         self.nnzj, self.nnzh = nnzj.value, nnzh.value
         o = np.zeros(16, dtype=np.int64)
         self._ck(L.ctd_dims(self._h, _ip(o)))
@@ -313,13 +341,23 @@ class DOCP:
 
     # ---- NLPModels-style callbacks --------------------------------------------------------------------------
     def _check_x(self, x):
-        n = x.numel() if _is_tensor(x) else x.size
+        """x has dim_NLP_variables entries; returns whether it is a tensor"""
+        dev = _is_tensor(x)
+        n = x.numel() if dev else x.size
         if n != self.dim_NLP_variables:
             raise ValueError(f"x has {n} entries, expected dim_NLP_variables = {self.dim_NLP_variables}")
+        return dev
 
     def _dev_ptr(self, t, n, name):
-        import torch
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n):
+        """The device pointer of the tensor t, checked: n float64 entries, contiguous, on the handle's GPU.  None (an optional
+        argument left out) gives None, the C side's NULL"""
+        if t is None:
+            return None
+        f64 = self._f64
+        if f64 is None:                 # (torch is imported by the first call that is given a tensor)
+            import torch
+            f64 = self._f64 = torch.float64
+        if not (t.is_cuda and t.dtype == f64 and t.is_contiguous() and t.numel() == n):
             raise ValueError(f"{name} must be a contiguous float64 tensor of {n} entries on the handle's GPU")
         if t.device.index != self.device:
             raise ValueError(f"{name} lives on cuda:{t.device.index}, handle is bound to device {self.device}")
@@ -450,69 +488,66 @@ class DOCP:
         self._ck(L.ctd_grad(self._h, _dp(x), _dp(g)))
         return g
 
-    def _prod(self, x, d, out, sync, transpose):
-        nin, nout = ((self.dim_NLP_constraints, self.dim_NLP_variables) if transpose
-                     else (self.dim_NLP_variables, self.dim_NLP_constraints))
-        name = "w" if transpose else "v"
-        L = _lib.lib()
-        self._check_x(x)
-        if _is_tensor(x):
-            import torch
-            if out is None:
-                out = torch.empty(nout, dtype=torch.float64, device=x.device)
-            fn = L.ctd_jtprod_dev_async if transpose else L.ctd_jprod_dev_async
-            self._ck(fn(self._h, self._dev_ptr(x, self.dim_NLP_variables, "x"), self._dev_ptr(d, nin, name),
-                        self._dev_ptr(out, nout, "out")))
-            if sync:
-                self.sync()
-            return out
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        d = np.ascontiguousarray(d, dtype=np.float64)
-        if d.size != nin:
-            raise ValueError(f"{name} has {d.size} entries, expected {nin}")
-        out = np.empty(nout) if out is None else _host_out(out, nout, "out")
-        self._ck((L.ctd_jtprod if transpose else L.ctd_jprod)(self._h, _dp(x), _dp(d), _dp(out)))
-        return out
+    def _mf(self, op, shard, vecs, scalars, outs, sync):
+        """One call of the matrix-free operator `op`, a row of _MF_OPS.  vecs: its vector inputs in the row's order, x first, None
+        for an optional one left out; outs: its outputs, allocated when None.  shard: `ctd_<op>_shard_dev_async`, device tensors
+        only, every length checked by name; otherwise `ctd_<op>_dev_async` for device tensors and `ctd_<op>` for NumPy arrays.
+        Device calls are followed by a sync when `sync`.  Returns the output, or the tuple of them."""
+        names, lens, nin, required, k, fns = self._mf_rows[op]
+        for i in required:
+            if vecs[i] is None:
+                raise ValueError(f"{names[i]} is required")
+        x = vecs[0]
+        dev = hasattr(x, "is_cuda")
+        if (x.numel() if dev else x.size) != lens[0]:
+            self._check_x(x)
+        if shard:
+            for a, nm, n in zip(vecs + outs, names, lens):
+                if a is not None:
+                    if not hasattr(a, "is_cuda"):
+                        raise TypeError(f"{nm} must be a device tensor: {op}_shard has no host path")
+                    if a.numel() != n:
+                        raise ValueError(f"{nm} has {a.numel()} entries, expected {n}")
+        if dev:
+            if outs[0] is None or outs[-1] is None:         # (one output or two)
+                import torch
+                outs = tuple(torch.empty(n, dtype=torch.float64, device=x.device) if a is None else a for a, n in zip(outs, lens[nin:]))
+            args = list(map(self._dev_ptr, vecs + outs, lens, names))
+            fn = fns[2 if shard else 1]
+        else:
+            args = []
+            for a, nm, n in zip(vecs, names, lens):
+                if a is not None:
+                    a = np.ascontiguousarray(a, dtype=np.float64)
+                    if a.size != n:
+                        raise ValueError(f"{nm} has {a.size} entries, expected {n}")
+                args.append(_dp(a))
+            outs = tuple(np.empty(n) if a is None else _host_out(a, n, nm) for a, nm, n in zip(outs, names[nin:], lens[nin:]))
+            args.extend(map(_dp, outs))
+            fn, sync = fns[0], False
+        if scalars:
+            args[k:k] = scalars
+        self._ck(fn(self._h, *args))
+        if sync:
+            self.sync()
+        return outs[0] if len(outs) == 1 else outs
 
     def jprod(self, x, v, out=None, sync=True):
         """jprod!(nlp, x, v, Jv): J(x) v without assembling J (ncon entries).  J is the exact derivative of the constraints
         (the structural Jacobian, whatever the pattern mode).  NumPy inputs use the host entry point; device tensors are
         enqueued on the handle's stream (`ctd_jprod_dev_async`), followed by a sync when `sync`."""
-        return self._prod(x, v, out, sync, False)
+        return self._mf("jprod", False, (x, v), (), (out,), sync)
 
     def jtprod(self, x, w, out=None, sync=True):
         """jtprod!(nlp, x, w, Jtw): J(x)' w without assembling J (nvar entries); see `jprod`."""
-        return self._prod(x, w, out, sync, True)
+        return self._mf("jtprod", False, (x, w), (), (out,), sync)
 
     def hprod(self, x, y, v, obj_weight=1.0, out=None, sync=True):
         """hprod!(nlp, x, y, v, Hv; obj_weight): (obj_weight d2 f + sum_i y_i d2 c_i)(x) v without assembling the Hessian (nvar
         entries).  y = None: the objective-only hprod!(nlp, x, v, Hv; obj_weight).  The Hessian is the exact second derivative
         of the objective and the constraints (the structural one, whatever the pattern mode).  NumPy inputs use the host entry
         point; device tensors are enqueued on the handle's stream (`ctd_hprod_dev_async`), followed by a sync when `sync`."""
-        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        L = _lib.lib()
-        self._check_x(x)
-        if _is_tensor(x):
-            import torch
-            if out is None:
-                out = torch.empty(nvar, dtype=torch.float64, device=x.device)
-            py = None if y is None else self._dev_ptr(y, ncon, "y")
-            self._ck(L.ctd_hprod_dev_async(self._h, self._dev_ptr(x, nvar, "x"), py, float(obj_weight), self._dev_ptr(v, nvar, "v"),
-                                           self._dev_ptr(out, nvar, "out")))
-            if sync:
-                self.sync()
-            return out
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        if v.size != nvar:
-            raise ValueError(f"v has {v.size} entries, expected {nvar}")
-        if y is not None:
-            y = np.ascontiguousarray(y, dtype=np.float64)
-            if y.size != ncon:
-                raise ValueError(f"y has {y.size} entries, expected {ncon}")
-        out = np.empty(nvar) if out is None else _host_out(out, nvar, "out")
-        self._ck(L.ctd_hprod(self._h, _dp(x), _dp(y), float(obj_weight), _dp(v), _dp(out)))
-        return out
+        return self._mf("hprod", False, (x, y, v), (float(obj_weight),), (out,), sync)
 
     def kktprod(self, x, y, dx, dy, obj_weight=1.0, sx=None, sc=None, out=None, sync=True):
         """The regularised KKT operator of an interior-point / SQP step applied to (dx, dy), matrix-free:
@@ -523,81 +558,23 @@ class DOCP:
         are the structural ones (see `hprod`, `jprod`).  NumPy inputs use the host entry point; device tensors are enqueued on
         the handle's stream (`ctd_kktprod_dev_async`), followed by a sync when `sync`.  Whole-grid handles only: a shard handle
         calls `kktprod_shard`."""
-        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        L = _lib.lib()
-        self._check_x(x)
-        sizes = (("y", y, ncon), ("dx", dx, nvar), ("dy", dy, ncon), ("sx", sx, nvar), ("sc", sc, ncon))
-        for name, a, n in sizes:
-            if a is None and name in ("dx", "dy"):
-                raise ValueError(f"{name} is required")
-        rx, rc = (None, None) if out is None else out
-        if _is_tensor(x):
-            import torch
-            if rx is None:
-                rx = torch.empty(nvar, dtype=torch.float64, device=x.device)
-            if rc is None:
-                rc = torch.empty(ncon, dtype=torch.float64, device=x.device)
-            p = {name: None if a is None else self._dev_ptr(a, n, name) for name, a, n in sizes}
-            self._ck(L.ctd_kktprod_dev_async(self._h, self._dev_ptr(x, nvar, "x"), p["y"], float(obj_weight), p["dx"], p["dy"],
-                                             p["sx"], p["sc"], self._dev_ptr(rx, nvar, "out[0]"), self._dev_ptr(rc, ncon, "out[1]")))
-            if sync:
-                self.sync()
-            return rx, rc
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        h = {}
-        for name, a, n in sizes:
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != n:
-                    raise ValueError(f"{name} has {a.size} entries, expected {n}")
-            h[name] = a
-        rx = np.empty(nvar) if rx is None else _host_out(rx, nvar, "out[0]")
-        rc = np.empty(ncon) if rc is None else _host_out(rc, ncon, "out[1]")
-        self._ck(L.ctd_kktprod(self._h, _dp(x), _dp(h["y"]), float(obj_weight), _dp(h["dx"]), _dp(h["dy"]), _dp(h["sx"]),
-                               _dp(h["sc"]), _dp(rx), _dp(rc)))
-        return rx, rc
-
-    def _diag(self, name, x, a, aname, na, nout, out, sync, obj_weight=None):
-        """one of the matrix-free diagonals: `ctd_<name>` (NumPy) or `ctd_<name>_dev_async` (device tensors); a: the optional
-        input (multipliers or weights, `na` entries)"""
-        nvar = self.dim_NLP_variables
-        L = _lib.lib()
-        self._check_x(x)
-        extra = () if obj_weight is None else (float(obj_weight),)
-        if _is_tensor(x):
-            import torch
-            if out is None:
-                out = torch.empty(nout, dtype=torch.float64, device=x.device)
-            pa = None if a is None else self._dev_ptr(a, na, aname)
-            self._ck(getattr(L, f"ctd_{name}_dev_async")(self._h, self._dev_ptr(x, nvar, "x"), pa, *extra,
-                                                         self._dev_ptr(out, nout, "out")))
-            if sync:
-                self.sync()
-            return out
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        if a is not None:
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.size != na:
-                raise ValueError(f"{aname} has {a.size} entries, expected {na}")
-        out = np.empty(nout) if out is None else _host_out(out, nout, "out")
-        self._ck(getattr(L, f"ctd_{name}")(self._h, _dp(x), _dp(a), *extra, _dp(out)))
-        return out
+        return self._mf("kktprod", False, (x, y, dx, dy, sx, sc), (float(obj_weight),), (None, None) if out is None else tuple(out), sync)
 
     def hdiag(self, x, y, obj_weight=1.0, out=None, sync=True):
         """The diagonal of the Hessian of the Lagrangian, (obj_weight d2 f + sum_i y_i d2 c_i)(x)_jj, without assembling it (nvar
         entries; `ctd_hdiag*`).  y = None: the objective only.  The structural Hessian, as for `hprod`.  NumPy inputs use the host
         entry point; device tensors are enqueued on the handle's stream, followed by a sync when `sync`."""
-        return self._diag("hdiag", x, y, "y", self.dim_NLP_constraints, self.dim_NLP_variables, out, sync, obj_weight)
+        return self._mf("hdiag", False, (x, y), (float(obj_weight),), (out,), sync)
 
     def jsq_rows(self, x, wx=None, out=None, sync=True):
         """diag(J diag(wx) J'): out_r = sum_j wx_j J_rj^2 without assembling J (ncon entries; `ctd_jsq_rows*`).  wx = None: ones,
         the squared row norms of J.  The structural Jacobian, as for `jprod`; inputs as for `hdiag`."""
-        return self._diag("jsq_rows", x, wx, "wx", self.dim_NLP_variables, self.dim_NLP_constraints, out, sync)
+        return self._mf("jsq_rows", False, (x, wx), (), (out,), sync)
 
     def jsq_cols(self, x, wc=None, out=None, sync=True):
         """diag(J' diag(wc) J): out_j = sum_r wc_r J_rj^2 without assembling J (nvar entries; `ctd_jsq_cols*`).  wc = None: ones,
         the squared column norms of J.  The structural Jacobian, as for `jprod`; inputs as for `hdiag`."""
-        return self._diag("jsq_cols", x, wc, "wc", self.dim_NLP_constraints, self.dim_NLP_variables, out, sync)
+        return self._mf("jsq_cols", False, (x, wc), (), (out,), sync)
 
     def kkt_diag_precond(self, x, y, obj_weight=1.0, sx=None, sc=None, floor=1e-8):
         """The diagonal (scaling) preconditioner of the operator `kktprod`, K = [[H + Sx, J'], [J, -Sc]]: returns the pair
@@ -656,45 +633,23 @@ class DOCP:
             self.sync()
         return g
 
-    def _prod_shard(self, x, d, out, sync, transpose):
-        nin, nout = ((self.dim_NLP_constraints, self.dim_NLP_variables) if transpose
-                     else (self.dim_NLP_variables, self.dim_NLP_constraints))
-        L = _lib.lib()
-        self._check_x(x)
-        fn = L.ctd_jtprod_shard_dev_async if transpose else L.ctd_jprod_shard_dev_async
-        self._ck(fn(self._h, self._dev_ptr(x, self.dim_NLP_variables, "x"), self._dev_ptr(d, nin, "w" if transpose else "v"),
-                    self._dev_ptr(out, nout, "out")))
-        if sync:
-            self.sync()
-        return out
-
     def jprod_shard(self, x, v, out, sync=False):
         """`ctd_jprod_shard_dev_async`: THIS shard's rows of J(x) v -- the rows of its own steps; the last shard also the final path
         and boundary rows -- into the full-length device tensor `out`; nothing else of `out` is touched.  x is read through the
         table of `set_x_shards` when one is set, otherwise from x itself (halos copied in); v is always read from the tensor
         passed.  include/ctdirect_hip.h lists the entries read."""
-        return self._prod_shard(x, v, out, sync, False)
+        return self._mf("jprod", True, (x, v), (), (out,), sync)
 
     def jtprod_shard(self, x, w, out, sync=False):
         """`ctd_jtprod_shard_dev_async`: the entries of J(x)' w of THIS shard's own variables into the full-length device tensor
         `out`, + the shard's partial sums of d/dv in the nv tail entries (the caller adds them over the shards); see `jprod_shard`."""
-        return self._prod_shard(x, w, out, sync, True)
+        return self._mf("jtprod", True, (x, w), (), (out,), sync)
 
     def hprod_shard(self, x, y, v, obj_weight=1.0, out=None, sync=False):
         """`ctd_hprod_shard_dev_async`: the entries of (obj_weight d2 f + sum_i y_i d2 c_i)(x) v of THIS shard's own variables into
         the full-length device tensor `out` (allocated, uninitialised elsewhere, when None), + the shard's partial sums of d/dv in
         the nv tail entries.  y = None: objective only.  See `jprod_shard`."""
-        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        self._check_x(x)
-        if out is None:
-            import torch
-            out = torch.empty(nvar, dtype=torch.float64, device=x.device)
-        py = None if y is None else self._dev_ptr(y, ncon, "y")
-        self._ck(_lib.lib().ctd_hprod_shard_dev_async(self._h, self._dev_ptr(x, nvar, "x"), py, float(obj_weight),
-                                                      self._dev_ptr(v, nvar, "v"), self._dev_ptr(out, nvar, "out")))
-        if sync:
-            self.sync()
-        return out
+        return self._mf("hprod", True, (x, y, v), (float(obj_weight),), (out,), sync)
 
     def kktprod_shard(self, x, y, dx, dy, obj_weight=1.0, sx=None, sc=None, out=None, sync=False):
         """`ctd_kktprod_shard_dev_async`: `kktprod` on THIS shard, device tensors only.  Into the full-length pair `out` = (rx, rc)
@@ -703,49 +658,7 @@ class DOCP:
         shard's own rows of rc (the last shard: also the final path and boundary rows); nothing else is touched.  x is read through
         the table of `set_x_shards` when one is set, otherwise from x itself (halos copied in); y, dx, dy, sx and sc are always read
         from the tensors passed.  include/ctdirect_hip.h lists the entries read.  Returns (rx, rc)."""
-        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        self._check_x(x)
-        rx, rc = (None, None) if out is None else out
-        sizes = (("y", y, ncon), ("dx", dx, nvar), ("dy", dy, ncon), ("sx", sx, nvar), ("sc", sc, ncon), ("out[0]", rx, nvar),
-                 ("out[1]", rc, ncon))
-        for name, a, n in sizes:
-            if a is None and name in ("dx", "dy"):
-                raise ValueError(f"{name} is required")
-            if a is not None and a.numel() != n:
-                raise ValueError(f"{name} has {a.numel()} entries, expected {n}")
-        if rx is None or rc is None:
-            import torch
-            rx = torch.empty(nvar, dtype=torch.float64, device=x.device) if rx is None else rx
-            rc = torch.empty(ncon, dtype=torch.float64, device=x.device) if rc is None else rc
-        p = {name: None if a is None else self._dev_ptr(a, n, name) for name, a, n in sizes[:5]}
-        self._ck(_lib.lib().ctd_kktprod_shard_dev_async(self._h, self._dev_ptr(x, nvar, "x"), p["y"], float(obj_weight), p["dx"],
-                                                        p["dy"], p["sx"], p["sc"], self._dev_ptr(rx, nvar, "out[0]"),
-                                                        self._dev_ptr(rc, ncon, "out[1]")))
-        if sync:
-            self.sync()
-        return rx, rc
-
-    def _diag_shard(self, name, x, a, aname, na, nout, out, sync, obj_weight=None):
-        """one of the matrix-free diagonals on THIS shard (`ctd_<name>_shard_dev_async`), device tensors only; a: the optional
-        input (multipliers or weights, `na` entries)"""
-        nvar = self.dim_NLP_variables
-        for nm, t in (("x", x), (aname, a), ("out", out)):
-            if t is not None and not _is_tensor(t):
-                raise TypeError(f"{nm} must be a device tensor: {name}_shard has no host path")
-        self._check_x(x)
-        for nm, t, n in ((aname, a, na), ("out", out, nout)):
-            if t is not None and t.numel() != n:
-                raise ValueError(f"{nm} has {t.numel()} entries, expected {n}")
-        if out is None:
-            import torch
-            out = torch.empty(nout, dtype=torch.float64, device=x.device)
-        extra = () if obj_weight is None else (float(obj_weight),)
-        pa = None if a is None else self._dev_ptr(a, na, aname)
-        self._ck(getattr(_lib.lib(), f"ctd_{name}_shard_dev_async")(self._h, self._dev_ptr(x, nvar, "x"), pa, *extra,
-                                                                    self._dev_ptr(out, nout, "out")))
-        if sync:
-            self.sync()
-        return out
+        return self._mf("kktprod", True, (x, y, dx, dy, sx, sc), (float(obj_weight),), (None, None) if out is None else tuple(out), sync)
 
     def hdiag_shard(self, x, y, obj_weight=1.0, out=None, sync=False):
         """`ctd_hdiag_shard_dev_async`: `hdiag` on THIS shard, device tensors only.  Into the full-length `out` (allocated,
@@ -753,19 +666,19 @@ class DOCP:
         entries (the caller adds them over the shards); nothing else is touched.  x is read through the table of `set_x_shards`
         when one is set, otherwise from x itself (halos copied in); y (None: objective only) is always read from the tensor passed:
         the constraint-layout read set of include/ctdirect_hip.h."""
-        return self._diag_shard("hdiag", x, y, "y", self.dim_NLP_constraints, self.dim_NLP_variables, out, sync, obj_weight)
+        return self._mf("hdiag", True, (x, y), (float(obj_weight),), (out,), sync)
 
     def jsq_rows_shard(self, x, wx=None, out=None, sync=False):
         """`ctd_jsq_rows_shard_dev_async`: THIS shard's rows of `jsq_rows` -- the rows of its own steps; the last shard also the
         final path and boundary rows -- into the full-length `out`; every row sum is complete.  wx (None: ones) is read from the
         tensor passed: the variable-layout read set of include/ctdirect_hip.h.  See `hdiag_shard`."""
-        return self._diag_shard("jsq_rows", x, wx, "wx", self.dim_NLP_variables, self.dim_NLP_constraints, out, sync)
+        return self._mf("jsq_rows", True, (x, wx), (), (out,), sync)
 
     def jsq_cols_shard(self, x, wc=None, out=None, sync=False):
         """`ctd_jsq_cols_shard_dev_async`: the entries of `jsq_cols` of THIS shard's own variables into the full-length `out`, + the
         shard's partial sums in the nv tail entries.  wc (None: ones) is read from the tensor passed: the constraint-layout read
         set of include/ctdirect_hip.h.  See `hdiag_shard`."""
-        return self._diag_shard("jsq_cols", x, wc, "wc", self.dim_NLP_constraints, self.dim_NLP_variables, out, sync)
+        return self._mf("jsq_cols", True, (x, wc), (), (out,), sync)
 
     def eval_all(self, x, y=None, obj_weight=1.0, f=None, g=None, c=None, vals=None, hvals=None, sync=False):
         """One solver iteration in one call (`ctd_eval_all_dev_async`): objective -> f[0], gradient -> g, constraints -> c,

@@ -46,6 +46,7 @@ def test_host_only_handle_refuses_diag_first():
             for a in (valid, nulls, aliased):
                 assert fn(d._h, *a) == ct._lib.CTD_ENODEVICE, (base + suffix, a)
                 assert b"host-only" in L.ctd_last_error(d._h), base + suffix
+                assert L.ctd_last_error(d._h).startswith((base + suffix).encode() + b": "), base + suffix
             assert fn(None, *valid) == ct._lib.CTD_EINVAL, base + suffix
             assert fn(None, *nulls) == ct._lib.CTD_EINVAL, base + suffix
     assert not ov.any() and not oc.any() and not x.any() and (wx == 1.0).all()

@@ -402,16 +402,20 @@ def test_refusals(torch_cuda):
         for args in ((None, a, o), (x, a, None)):
             assert fn(d._h, *args) == E, name
             assert b"null" in L.ctd_last_error(d._h), name
+            assert L.ctd_last_error(d._h).startswith(b"ctd_" + name.encode() + b"_dev_async: "), name
             assert untouched(), name
         for args, keep in (((x, a, x), x), ((x, a, a), a)):
             before = keep.clone()
             assert fn(d._h, *args) == E, name
             assert b"input" in L.ctd_last_error(d._h), name
+            assert L.ctd_last_error(d._h).startswith(b"ctd_" + name.encode() + b"_dev_async: "), name
             d.sync()
             assert torch.equal(keep, before) and untouched(), name
         # shard handles: a range of steps, and a whole-grid handle with an x-shard table
         assert fn(s._h, x, a, o) == E, name
         assert b"shard" in L.ctd_last_error(s._h) and b"out of scope" in L.ctd_last_error(s._h), name
+        assert L.ctd_last_error(s._h).startswith(b"ctd_" + name.encode() + b"_dev_async: "), name
+        assert b"ctd_" + name.encode() + b"_shard_dev_async" in L.ctd_last_error(s._h), name
         assert fn(sh._h, x, a, o) == E, name
         assert b"shard" in L.ctd_last_error(sh._h), name
         assert untouched(), name

@@ -329,9 +329,11 @@ def test_refusals(torch_cuda):
     assert fn(d._h, P(x), P(y), 1.0, None, P(o)) == ct._lib.CTD_EINVAL
     assert fn(d._h, P(x), P(y), 1.0, P(v), None) == ct._lib.CTD_EINVAL
     assert b"null" in L.ctd_last_error(d._h)
+    assert L.ctd_last_error(d._h).startswith(b"ctd_hprod_dev_async: ")
     for alias in (x, v):
         assert fn(d._h, P(x), P(y), 1.0, P(v), P(alias)) == ct._lib.CTD_EINVAL
         assert b"input" in L.ctd_last_error(d._h)
+        assert L.ctd_last_error(d._h).startswith(b"ctd_hprod_dev_async: ")
     assert fn(d._h, P(x), P(y), 1.0, P(v), P(y)) == ct._lib.CTD_EINVAL
     assert b"input" in L.ctd_last_error(d._h)
     assert fn(d._h, P(x), None, 1.0, P(v), P(o)) == 0
@@ -339,6 +341,7 @@ def test_refusals(torch_cuda):
     s = ct.DOCP("goddard", 20, "midpoint", device=0, steps=(0, 10))
     assert fn(s._h, P(x), P(y), 1.0, P(v), P(o)) == ct._lib.CTD_EINVAL
     assert b"shard" in L.ctd_last_error(s._h)
+    assert L.ctd_last_error(s._h).startswith(b"ctd_hprod_dev_async: ") and b"ctd_hprod_shard_dev_async" in L.ctd_last_error(s._h)
 
 
 # ---- end to end: trust-constr with Hessians given only as products ------------------------------------------------------------

@@ -385,6 +385,7 @@ def test_refusals(torch_cuda):
     for name in ("x", "dx", "dy", "rx", "rc"):
         assert call(d._h, **{name: None}) == E, name
         assert b"null" in L.ctd_last_error(d._h), name
+        assert L.ctd_last_error(d._h).startswith(b"ctd_kktprod_dev_async: "), name
         assert untouched(), name
     # every output against every input (same-length pairs and, through raw pointers, the others too), and rx == rc
     for out in ("rx", "rc"):
@@ -392,15 +393,18 @@ def test_refusals(torch_cuda):
             before = good[inp].clone()
             assert call(d._h, **{out: good[inp]}) == E, (out, inp)
             assert b"input" in L.ctd_last_error(d._h), (out, inp)
+            assert L.ctd_last_error(d._h).startswith(b"ctd_kktprod_dev_async: "), (out, inp)
             d.sync()
             assert torch.equal(good[inp], before) and untouched(), (out, inp)
     assert call(d._h, rc=rx) == E
     assert b"rx and rc" in L.ctd_last_error(d._h)
+    assert L.ctd_last_error(d._h).startswith(b"ctd_kktprod_dev_async: ")
     assert untouched()
     # shard handles: a range of steps, and a whole-grid handle with an x-shard table
     s = ct.DOCP("goddard", 20, "midpoint", device=0, steps=(0, 10))
     assert call(s._h) == E
     assert b"shard" in L.ctd_last_error(s._h) and b"out of scope" in L.ctd_last_error(s._h)
+    assert L.ctd_last_error(s._h).startswith(b"ctd_kktprod_dev_async: ") and b"ctd_kktprod_shard_dev_async" in L.ctd_last_error(s._h)
     assert untouched()
     sh = ct.DOCP("goddard", 20, "midpoint", device=0)
     sh.set_x_shards([0, 20], [x.data_ptr()], 0)

@@ -247,10 +247,20 @@ def test_refusals(torch_cuda):
     o = torch.zeros(d.dim_NLP_constraints, dtype=torch.float64, device="cuda")
     P = lambda t: C.c_void_p(t.data_ptr())        # noqa: E731
     assert L.ctd_jprod_dev_async(d._h, P(x), None, P(o)) == ct._lib.CTD_EINVAL
+    assert L.ctd_last_error(d._h).startswith(b"ctd_jprod_dev_async: ")
     assert L.ctd_jtprod_dev_async(d._h, None, P(o), P(v)) == ct._lib.CTD_EINVAL
+    assert L.ctd_last_error(d._h).startswith(b"ctd_jtprod_dev_async: ")
     assert L.ctd_jprod_dev_async(d._h, P(x), P(v), P(x)) == ct._lib.CTD_EINVAL
     assert b"input" in L.ctd_last_error(d._h)
+    assert L.ctd_last_error(d._h).startswith(b"ctd_jprod_dev_async: ")
+    # the methods on device tensors: a vector of wrong length is refused by its name
+    for call, name in ((lambda: d.jprod(x, v[:-1]), "v"), (lambda: d.jtprod(x, o[:-1]), "w"), (lambda: d.jprod(x, v, out=o[:-1]), "out"),
+                       (lambda: d.jprod(x[:-1], v), "x")):
+        with pytest.raises(ValueError, match=f"^{name} "):
+            call()
     s = ct.DOCP("goddard", 20, "midpoint", device=0, steps=(0, 10))
     assert L.ctd_jprod_dev_async(s._h, P(x), P(v), P(o)) == ct._lib.CTD_EINVAL
     assert b"shard" in L.ctd_last_error(s._h)
+    assert L.ctd_last_error(s._h).startswith(b"ctd_jprod_dev_async: ") and b"ctd_jprod_shard_dev_async" in L.ctd_last_error(s._h)
     assert L.ctd_jtprod_dev_async(s._h, P(x), P(o), P(v)) == ct._lib.CTD_EINVAL
+    assert L.ctd_last_error(s._h).startswith(b"ctd_jtprod_dev_async: ") and b"ctd_jtprod_shard_dev_async" in L.ctd_last_error(s._h)

@@ -42,6 +42,7 @@ def test_host_only_handle_refuses_kktprod_first():
         for a in (valid, nulls, aliased):
             assert fn(d._h, *a) == ct._lib.CTD_ENODEVICE, (name, a)
             assert b"host-only" in L.ctd_last_error(d._h), name
+            assert L.ctd_last_error(d._h).startswith(name.encode() + b": "), name
         assert fn(None, *valid) == ct._lib.CTD_EINVAL, name
         assert fn(None, *nulls) == ct._lib.CTD_EINVAL, name
     assert not rx.any() and not rc.any()

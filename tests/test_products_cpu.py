@@ -46,6 +46,7 @@ def test_host_only_handle_refuses_products_first():
         for a in (args, (None, None, None)):
             assert fn(d._h, *a) == ct._lib.CTD_ENODEVICE, (name, a)
             assert b"host-only" in L.ctd_last_error(d._h), name
+            assert L.ctd_last_error(d._h).startswith(name.encode() + b": "), name
         assert fn(None, *args) == ct._lib.CTD_EINVAL, name
         assert fn(None, None, None, None) == ct._lib.CTD_EINVAL, name
 
