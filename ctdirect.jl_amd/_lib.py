@@ -39,6 +39,20 @@ class ctd_ocp_def(C.Structure):
                                                      "variable_ub", "path_lb", "path_ub", "boundary_lb", "boundary_ub")]
 
 
+# status of the device-resident MINRES solve (ctd_minres_info.status), by CTD_MINRES_* value
+MINRES_STATUS = ("running", "converged", "max_iter", "breakdown")
+
+
+class ctd_kkt_system(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("obj_weight", C.c_double), ("sx", C.c_void_p), ("sc", C.c_void_p), ("px", C.c_void_p), ("pc", C.c_void_p)]
+
+
+class ctd_minres_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("iterations", C.c_int64), ("phibar", C.c_double),
+                ("Anorm", C.c_double), ("ynorm", C.c_double), ("beta1", C.c_double)]
+
+
 # every symbol include/ctdirect_hip.h declares: name -> (restype, argtypes)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -114,6 +128,14 @@ SYMBOLS = {
     "ctd_jsq_rows_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jsq_cols": (C.c_int32, [_vp, _dp, _dp, _dp]),
     "ctd_jsq_cols_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    # device-resident preconditioned MINRES solve of the KKT system
+    "ctd_kkt_minres_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, C.c_double]),
+    "ctd_kkt_minres_iters_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, C.c_int64]),
+    "ctd_kkt_minres_info": (C.c_int32, [_vp, C.POINTER(ctd_minres_info)]),
+    "ctd_kkt_minres_dev": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, C.c_double, C.c_int64, C.c_int64,
+                                       C.POINTER(ctd_minres_info)]),
+    "ctd_kkt_minres": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _dp, _dp, C.c_double, C.c_int64, C.c_int64,
+                                   C.POINTER(ctd_minres_info)]),
     "ctd_jprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

@@ -27,6 +27,7 @@
 #include "ctd_hprod_kernels.hpp"
 #include "ctd_kkt_kernels.hpp"
 #include "ctd_diag_kernels.hpp"
+#include "ctd_krylov_kernels.hpp"
 #include "ctd_jit.hpp"
 
 using namespace ctd;
@@ -136,6 +137,12 @@ struct ctd_handle {
     // partial-sum buffer per call, so a graph captured over any other product keeps its own; the host calls stage through d_x,
     // d_y, d_pdir and d_pout
     DevBuf<> d_hdpartial, d_jcpartial;
+    // device-resident MINRES solve (ctd_kkt_minres*): the workspace of ctd_krylov_kernels.hpp (krylov_workspace(nvar + ncon) doubles),
+    // the partial sums of its own kktprod launches (a graph captured over ctd_kktprod keeps its buffer), the host form's staging
+    // of (px, pc), rhs and z; the iterate and the preconditioner flag of the solve started last (mr_z null: none yet)
+    DevBuf<> d_mrws, d_mrkpartial, d_mrp, d_mrrhs, d_mrz;
+    double* mr_z = nullptr;
+    bool mr_precond = false;
     std::string err;
 };
 
@@ -1455,7 +1462,7 @@ static int32_t enqueue_hprod(ctd_handle* h, const MfCall& c, const double* x_dev
 
 static int32_t enqueue_kktprod(ctd_handle* h, const MfCall& c, const double* x_dev, const double* y_dev, double obj_weight,
                                const double* dx_dev, const double* dy_dev, const double* sx_dev, const double* sc_dev, double* rx_dev,
-                               double* rc_dev) {
+                               double* rc_dev, DevBuf<>& partial) {
     if (const int32_t st = jit_load(h, c.op.fam, c.shard())) return st;
     KktParams kp;
     std::memset(&kp, 0, sizeof(kp));
@@ -1467,7 +1474,7 @@ static int32_t enqueue_kktprod(ctd_handle* h, const MfCall& c, const double* x_d
     kp.sc = sc_dev;
     kp.rc = rc_dev;
     // the fused lanes keep the hprod chunk rule (profiles/kktprod_resources.md)
-    return enqueue_prod_units<KktKernels>(h, c, kp, hprod_dirs_per_node(kp.h.p.L), prod_chunk<HProdDirs>(h, hprod_chunk), h->d_kktpartial, x_dev);
+    return enqueue_prod_units<KktKernels>(h, c, kp, hprod_dirs_per_node(kp.h.p.L), prod_chunk<HProdDirs>(h, hprod_chunk), partial, x_dev);
 }
 
 static int32_t enqueue_hdiag(ctd_handle* h, const MfCall& c, const double* x_dev, const double* y_dev, double obj_weight, double* out_dev) {
@@ -1521,13 +1528,13 @@ static int32_t mf_kktprod(ctd_handle* h, const MfCall& c, const double* x, const
                           const double* dy, const double* sx, const double* sc, double* rx, double* rc) {
     const OnDevice on(h, c.fn());
     if (const int32_t st = mf_check(on, h, c, {x, dx, dy}, {y, sx, sc}, {rx, rc})) return st;
-    if (c.form != MF_HOST) return enqueue_kktprod(h, c, x, y, obj_weight, dx, dy, sx, sc, rx, rc);
+    if (c.form != MF_HOST) return enqueue_kktprod(h, c, x, y, obj_weight, dx, dy, sx, sc, rx, rc, h->d_kktpartial);
     const Layout& L = h->model.L;
     return host_call(h, {{x, h->d_x, L.nvar}, {dx, h->d_pdir, L.nvar}, {y, h->d_y, L.ncon}, {dy, h->d_kdy, L.ncon},
                          {sx, h->d_ksx, L.nvar}, {sc, h->d_ksc, L.ncon}},
                      [&] {
                          return enqueue_kktprod(h, c, h->d_x.p, y ? h->d_y.p : nullptr, obj_weight, h->d_pdir.p, h->d_kdy.p,
-                                                sx ? h->d_ksx.p : nullptr, sc ? h->d_ksc.p : nullptr, h->d_pout.p, h->d_krc.p);
+                                                sx ? h->d_ksx.p : nullptr, sc ? h->d_ksc.p : nullptr, h->d_pout.p, h->d_krc.p, h->d_kktpartial);
                      },
                      {{rx, h->d_pout, L.nvar}, {rc, h->d_krc, L.ncon}});
 }
@@ -1617,6 +1624,185 @@ int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double*
 }
 int32_t ctd_jsq_cols_shard_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev) {
     return mf_jsq(h, {kJsqCols, MF_SHARD}, x_dev, wc_dev, out_dev);
+}
+
+// ---- device-resident preconditioned MINRES solve of K z = rhs (kernels, state and freeze: ctd_krylov_kernels.hpp) -----------------
+// One row per entry point (none has a shard form; the KKT family: what enqueue_kktprod launches for a run-time OCP)
+#define CTD_MR_OP(X, REQ) {{X, X, X}, JIT_KKT, 0, false, false, false, REQ, "z"}
+static constexpr MfOp kMrStart = CTD_MR_OP("ctd_kkt_minres_start_dev_async", "sys->x, rhs and z"),
+                      kMrIters = CTD_MR_OP("ctd_kkt_minres_iters_dev_async", "sys->x and z"),
+                      kMrDev = CTD_MR_OP("ctd_kkt_minres_dev", "sys->x, rhs and z"),
+                      kMrHost = CTD_MR_OP("ctd_kkt_minres", "sys->x, rhs and z");
+#undef CTD_MR_OP
+
+// The checks of the solve's entry points, in the header's order.  Before the device: the handle and the layout of the caller's structs
+// (*st = the status to return when the result is false)
+static bool mr_structs_ok(ctd_handle* h, const char* fn, const ctd_kkt_system* sys, bool with_info, const ctd_minres_info* info, int32_t* st) {
+    *st = CTD_EINVAL;
+    if (!h) return false;
+    if (!sys || sys->struct_size != sizeof(ctd_kkt_system))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": sys is null or its struct_size is not sizeof(ctd_kkt_system) = " +
+                                       std::to_string(sizeof(ctd_kkt_system))), false;
+    if (with_info && (!info || info->struct_size != sizeof(ctd_minres_info)))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
+                                       std::to_string(sizeof(ctd_minres_info))), false;
+    return true;
+}
+// ... after it (OnDevice): whole-grid handle, the pointers (mf_check), the preconditioner pair
+static int32_t mr_check(const OnDevice& on, ctd_handle* h, const MfCall& c, const ctd_kkt_system* sys, const double* rhs, const double* z,
+                        bool with_rhs) {
+    if (on.st) return on.st;
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+        return fail(h, CTD_EINVAL, std::string(c.fn()) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
+                                   "step_end, ctd_set_x_shards) is out of scope: the solve has no shard form yet (it needs the "
+                                   "all-reduce of ctd_kktprod_shard_dev_async's partial sums and of the inner products)");
+    const int32_t st = with_rhs ? mf_check(on, h, c, {sys->x, rhs}, {sys->y, sys->sx, sys->sc, sys->px, sys->pc}, {z})
+                                : mf_check(on, h, c, {sys->x}, {sys->y, sys->sx, sys->sc, sys->px, sys->pc}, {z});
+    if (st) return st;
+    if (!sys->px != !sys->pc)
+        return fail(h, CTD_EINVAL, std::string(c.fn()) + ": px and pc are given both (M = diag(1 / px, 1 / pc)) or neither (no preconditioner)");
+    return CTD_OK;
+}
+static int32_t mr_check_count(ctd_handle* h, const MfCall& c, const char* name, int64_t v) {
+    return v >= 1 ? CTD_OK : fail(h, CTD_EINVAL, std::string(c.fn()) + ": " + name + " = " + std::to_string(v) + ", must be at least 1");
+}
+static int32_t mr_check_rtol(ctd_handle* h, const MfCall& c, double rtol) {
+    return rtol >= 0.0 ? CTD_OK : fail(h, CTD_EINVAL, std::string(c.fn()) + ": rtol must not be negative (or NaN)");
+}
+
+static KrylovParams mr_params(const ctd_handle* h) {
+    return krylov_params(h->d_mrws.p, h->model.L.nvar + h->model.L.ncon, h->mr_z, h->mr_precond);
+}
+
+// max_iter: the cap the device state carries
+static int32_t mr_enqueue_start(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, const double* rhs_dev, double* z_dev, double rtol,
+                                int64_t max_iter) {
+    const Layout& L = h->model.L;
+    const int64_t n = L.nvar + L.ncon;
+    if (const int32_t st = h->d_mrws.grow(h, krylov_workspace(n), c.fn())) return st;
+    h->mr_z = z_dev;
+    h->mr_precond = sys.px != nullptr;
+    return c.launched(h, krylov_start(mr_params(h), rhs_dev, sys.px, sys.pc, L.nvar, rtol, max_iter, h->stream));
+}
+
+// k iterations: K v (v and kv are Krylov vectors: dx / dy and rx / rc are their halves), then (A), (B), (C)
+static int32_t mr_enqueue_iters(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, int64_t k) {
+    const KrylovParams kp = mr_params(h);
+    const int64_t nvar = h->model.L.nvar;
+    for (int64_t it = 0; it < k; ++it) {
+        if (const int32_t st = enqueue_kktprod(h, c, sys.x, sys.y, sys.obj_weight, kp.v, kp.v + nvar, sys.sx, sys.sc, kp.kv, kp.kv + nvar,
+                                               h->d_mrkpartial))
+            return st;
+        hipError_t e = krylov_alfa(kp, h->stream);
+        if (e == hipSuccess) e = krylov_step(kp, h->stream);
+        if (e != hipSuccess) return c.launched(h, e);
+    }
+    return CTD_OK;
+}
+
+static int32_t mr_read_info(ctd_handle* h, ctd_minres_info* info) {
+    KrylovState s;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(&s, mr_params(h).pend, sizeof(s), hipMemcpyDeviceToHost));
+    info->status = s.status;
+    info->iterations = s.itn;
+    info->phibar = s.phibar;
+    info->Anorm = s.Anorm;
+    info->ynorm = s.ynorm;
+    info->beta1 = s.beta1;
+    return CTD_OK;
+}
+
+// start, then at most ceil(max_iter / check_every) chunks: the device freezes the solve at max_iter iterations
+static int32_t mr_drive(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, const double* rhs_dev, double* z_dev, double rtol,
+                        int64_t max_iter, int64_t check_every, ctd_minres_info* info) {
+    if (const int32_t st = mr_enqueue_start(h, c, sys, rhs_dev, z_dev, rtol, max_iter)) return st;
+    for (int64_t done = 0; done < max_iter; done += check_every) {
+        if (const int32_t st = mr_enqueue_iters(h, c, sys, check_every)) return st;
+        if (const int32_t st = mr_read_info(h, info)) return st;
+        if (info->status != CTD_MINRES_RUNNING) return CTD_OK;
+    }
+    return mr_read_info(h, info);
+}
+
+int32_t ctd_kkt_minres_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev, double rtol) {
+    const MfCall c{kMrStart, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
+    if ((st = mr_check_rtol(h, c, rtol))) return st;
+    return mr_enqueue_start(h, c, *sys, rhs_dev, z_dev, rtol, INT64_MAX);
+}
+
+int32_t ctd_kkt_minres_iters_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* z_dev, int64_t k) {
+    const MfCall c{kMrIters, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if ((st = mr_check(on, h, c, sys, nullptr, z_dev, false))) return st;
+    if ((st = mr_check_count(h, c, "k", k))) return st;
+    if (!h->mr_z) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": no solve has been started on this handle (ctd_kkt_minres_start_dev_async)");
+    if (z_dev != h->mr_z) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": z is not the iterate of the solve started last");
+    return mr_enqueue_iters(h, c, *sys, k);
+}
+
+int32_t ctd_kkt_minres_info(ctd_handle* h, ctd_minres_info* info) {
+    const char* fn = "ctd_kkt_minres_info";
+    if (!h) return CTD_EINVAL;
+    if (!info || info->struct_size != sizeof(ctd_minres_info))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
+                                       std::to_string(sizeof(ctd_minres_info)));
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    if (!h->mr_z) return fail(h, CTD_EINVAL, std::string(fn) + ": no solve has been started on this handle (ctd_kkt_minres_start_dev_async)");
+    return mr_read_info(h, info);
+}
+
+int32_t ctd_kkt_minres_dev(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev, double rtol, int64_t max_iter,
+                           int64_t check_every, ctd_minres_info* info) {
+    const MfCall c{kMrDev, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, true, info, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
+    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c, "check_every", check_every)))
+        return st;
+    return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info);
+}
+
+int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs, double* z, double rtol, int64_t max_iter,
+                       int64_t check_every, ctd_minres_info* info) {
+    const MfCall c{kMrHost, MF_HOST};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, true, info, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if ((st = mr_check(on, h, c, sys, rhs, z, true))) return st;
+    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c, "check_every", check_every)))
+        return st;
+    // x, y, sx, sc where ctd_kktprod stages them; (px, pc), rhs and z in buffers of the solve's own
+    const Layout& L = h->model.L;
+    const int64_t n = L.nvar + L.ncon;
+    HIP_TRY(h, h->d_mrp.ensure(n));
+    ctd_kkt_system dev = *sys;  // (the device pointers are set once host_call has allocated the staging buffers)
+    return host_call(h, {{sys->x, h->d_x, L.nvar}, {sys->y, h->d_y, L.ncon}, {sys->sx, h->d_ksx, L.nvar}, {sys->sc, h->d_ksc, L.ncon},
+                         {rhs, h->d_mrrhs, n}},
+                     [&]() -> int32_t {
+                         if (sys->px) {
+                             HIP_TRY(h, hipMemcpyAsync(h->d_mrp.p, sys->px, sizeof(double) * L.nvar, hipMemcpyHostToDevice, h->stream));
+                             HIP_TRY(h, hipMemcpyAsync(h->d_mrp.p + L.nvar, sys->pc, sizeof(double) * L.ncon, hipMemcpyHostToDevice, h->stream));
+                         }
+                         dev.x = h->d_x.p;
+                         dev.y = sys->y ? h->d_y.p : nullptr;
+                         dev.sx = sys->sx ? h->d_ksx.p : nullptr;
+                         dev.sc = sys->sc ? h->d_ksc.p : nullptr;
+                         dev.px = sys->px ? h->d_mrp.p : nullptr;
+                         dev.pc = sys->pc ? h->d_mrp.p + L.nvar : nullptr;
+                         return mr_drive(h, c, dev, h->d_mrrhs.p, h->d_mrz.p, rtol, max_iter, check_every, info);
+                     },
+                     {{z, h->d_mrz, n}});
 }
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {

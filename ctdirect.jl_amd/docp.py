@@ -18,6 +18,7 @@ All arithmetic happens in the HIP library; this module only moves pointers.  Num
 host-pointer entry points, torch CUDA(=HIP) tensors through the device-pointer ones.
 """
 import ctypes as C
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -100,6 +101,12 @@ _MF_OPS = {
     "jsq_rows": ((("x", "v", True), ("wx", "v", False)), 2, (("out", "c"),)),
     "jsq_cols": ((("x", "v", True), ("wc", "c", False)), 2, (("out", "v"),)),
 }
+
+
+# What DOCP.kkt_minres / kkt_minres_info return with the iterate: status is "running", "converged", "max_iter" or "breakdown";
+# iterations: the completed ones; phibar: the estimate of the M-norm of the residual, beta1 its initial value; Anorm, ynorm: the
+# estimates of |K| and |z| (ctd_minres_info)
+MinresInfo = namedtuple("MinresInfo", "status iterations phibar Anorm ynorm beta1")
 
 
 def _mf_rows(L, nvar, ncon):
@@ -622,6 +629,115 @@ class DOCP:
         if sc is not None:
             pc = pc + np.asarray(sc, dtype=np.float64)
         return px, pc
+
+    # ---- device-resident preconditioned MINRES solve of K z = rhs (ctd_kkt_minres*) ---------------------------------------------
+    def _kkt_system(self, fn, vecs, obj_weight, host_ok):
+        """The ctd_kkt_system of a solve and the pointers of its other vectors.  vecs: (name, array, layout, required) rows, x
+        first -- layout "v": nvar, "c": ncon, "k": nvar + ncon entries --; those named x, y, sx, sc, px, pc fill the struct.  Every
+        length is checked by name, as DOCP._mf does.  Returns (dev, sys, pointers of the rows by name, arrays to keep alive)."""
+        size = {"v": self.dim_NLP_variables, "c": self.dim_NLP_constraints, "k": self.dim_NLP_variables + self.dim_NLP_constraints}
+        for nm, a, _, required in vecs:
+            if required and a is None:
+                raise ValueError(f"{nm} is required")
+        dev = hasattr(vecs[0][1], "is_cuda")
+        self._check_x(vecs[0][1])
+        by = {nm: a for nm, a, _, _ in vecs}
+        if (by.get("px") is None) != (by.get("pc") is None):
+            raise ValueError("px and pc are given both (M = diag(1 / px, 1 / pc)) or neither")
+        ptrs, keep = {}, []
+        for nm, a, lay, _ in vecs:          # every kind and length first, by name
+            if a is None:
+                continue
+            n = size[lay]
+            if dev and not hasattr(a, "is_cuda"):
+                raise TypeError(f"{nm} must be a device tensor like x")
+            if not dev and not host_ok:
+                raise TypeError(f"{nm} must be a device tensor: {fn} has no host path")
+            if not dev and nm == "out":
+                _host_out(a, n, nm)
+            elif (a.numel() if dev else np.size(a)) != n:
+                raise ValueError(f"{nm} has {a.numel() if dev else np.size(a)} entries, expected {n}")
+        for nm, a, lay, _ in vecs:
+            if a is None:
+                ptrs[nm] = None
+            elif dev:
+                ptrs[nm] = self._dev_ptr(a, size[lay], nm)
+            else:
+                a = a if nm == "out" else np.ascontiguousarray(a, dtype=np.float64)
+                keep.append(a)
+                ptrs[nm] = C.c_void_p(a.ctypes.data)
+        sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=float(obj_weight))
+        for nm in ("x", "y", "sx", "sc", "px", "pc"):
+            q = ptrs.get(nm)
+            setattr(sys, nm, q.value if q is not None else None)
+        return dev, sys, ptrs, keep
+
+    @staticmethod
+    def _minres_info(info):
+        return MinresInfo(_lib.MINRES_STATUS[info.status], int(info.iterations), info.phibar, info.Anorm, info.ynorm, info.beta1)
+
+    def kkt_minres(self, x, y, rhs, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10, max_iter=None, check_every=16,
+                   out=None):
+        """Preconditioned MINRES on K z = rhs, K = [[H + Sx, J'], [J, -Sc]] the operator of `kktprod` at (x, y, obj_weight, sx, sc),
+        entirely on the device (`ctd_kkt_minres*`): per iteration the two launches of `kktprod` and three vector kernels, the
+        scalar recurrences and the stopping tests included; the host reads the status once per `check_every` iterations.  rhs
+        and z have nvar + ncon entries, z0 = 0.  The recurrences and the stopping tests (rtol) are those of
+        scipy.sparse.linalg.minres, so iteration counts are comparable with it.
+        precond: None; a pair (px, pc), M = diag(1 / px, 1 / pc), which must be positive; or "diag": the pair of
+        `kkt_diag_precond(x, y, obj_weight, sx, sc)`.  max_iter: default 5 (nvar + ncon), scipy's.
+        Returns (z, info), info a MinresInfo: status "converged", "max_iter" or "breakdown" (M not positive definite, a NaN, or
+        the Krylov space exhausted), the iterations done, phibar, Anorm, ynorm, beta1.  Iterations enqueued after the status was
+        set change nothing: z does not depend on check_every.  Results are reproducible bit for bit.  NumPy inputs use the host
+        entry point; device tensors the device one (`out`: z).  Whole-grid handles only."""
+        L = _lib.lib()
+        n = self.dim_NLP_variables + self.dim_NLP_constraints
+        if x is None or rhs is None:
+            raise ValueError(("x" if x is None else "rhs") + " is required")
+        if isinstance(precond, str):
+            if precond != "diag":
+                raise ValueError(f'precond is None, a pair (px, pc) or "diag", not {precond!r}')
+            self._check_x(x)
+            px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc)
+        else:
+            px, pc = (None, None) if precond is None else precond
+        dev = hasattr(x, "is_cuda")
+        if out is None:
+            if dev:
+                import torch
+                out = torch.empty(n, dtype=torch.float64, device=x.device)
+            else:
+                out = np.empty(n)
+        rows = (("x", x, "v", True), ("y", y, "c", False), ("rhs", rhs, "k", True), ("sx", sx, "v", False), ("sc", sc, "c", False),
+                ("px", px, "v", False), ("pc", pc, "c", False), ("out", out, "k", True))
+        dev, sys, p, keep = self._kkt_system("kkt_minres", rows, obj_weight, True)
+        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        fn = L.ctd_kkt_minres_dev if dev else L.ctd_kkt_minres
+        rhs_p, out_p = (p["rhs"], p["out"]) if dev else (C.cast(p["rhs"], C.POINTER(C.c_double)), C.cast(p["out"], C.POINTER(C.c_double)))
+        self._ck(fn(self._h, C.byref(sys), rhs_p, out_p, float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every),
+                    C.byref(info)))
+        return out, self._minres_info(info)
+
+    def kkt_minres_start(self, x, y, rhs, z, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10):
+        """`ctd_kkt_minres_start_dev_async`: enqueues the initialisation of a solve on the device tensors (z = 0, the state) on the
+        handle's stream; precond: None or a pair (px, pc), read now only.  No iteration cap.  See `kkt_minres`."""
+        px, pc = (None, None) if precond is None else precond
+        rows = (("x", x, "v", True), ("y", y, "c", False), ("rhs", rhs, "k", True), ("z", z, "k", True), ("sx", sx, "v", False),
+                ("sc", sc, "c", False), ("px", px, "v", False), ("pc", pc, "c", False))
+        _, sys, p, _ = self._kkt_system("kkt_minres_start", rows, obj_weight, False)
+        self._ck(_lib.lib().ctd_kkt_minres_start_dev_async(self._h, C.byref(sys), p["rhs"], p["z"], float(rtol)))
+
+    def kkt_minres_iters(self, x, y, z, k, obj_weight=1.0, sx=None, sc=None):
+        """`ctd_kkt_minres_iters_dev_async`: enqueues k iterations of the solve started last, on the same z and the same operator;
+        they change nothing once the status is set.  Enqueue-only on the handle's stream."""
+        rows = (("x", x, "v", True), ("y", y, "c", False), ("z", z, "k", True), ("sx", sx, "v", False), ("sc", sc, "c", False))
+        _, sys, p, _ = self._kkt_system("kkt_minres_iters", rows, obj_weight, False)
+        self._ck(_lib.lib().ctd_kkt_minres_iters_dev_async(self._h, C.byref(sys), p["z"], int(k)))
+
+    def kkt_minres_info(self):
+        """`ctd_kkt_minres_info`: waits for the handle's stream and returns the MinresInfo of the solve started last."""
+        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        self._ck(_lib.lib().ctd_kkt_minres_info(self._h, C.byref(info)))
+        return self._minres_info(info)
 
     def grad_shard(self, x, g, sync=False):
         """`ctd_grad_shard_dev_async`: the gradient entries of THIS shard's own variables into the full-length device tensor g

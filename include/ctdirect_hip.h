@@ -477,6 +477,71 @@ int32_t ctd_hdiag_dev_async(ctd_handle* h, const double* x_dev, const double* y_
 int32_t ctd_jsq_rows_dev_async(ctd_handle* h, const double* x_dev, const double* wx_dev, double* out_dev);
 int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double* wc_dev, double* out_dev);
 
+/* ---- device-resident preconditioned MINRES solve of the KKT system ------------------------------------------------------
+ * K z = rhs with K = [[H + Sx, J'], [J, -Sc]] the operator of ctd_kktprod at (x, y, obj_weight, sx, sc), z and rhs of
+ * nvar + ncon entries (variables first), H and J assembled nowhere.  The recurrences are preconditioned MINRES (Paige & Saunders)
+ * exactly as scipy.sparse.linalg.minres evaluates them -- the same variables, the same initialisation, z0 = 0, the stopping tests
+ * test1 = phibar / (Anorm ynorm) <= rtol or test2 = root / Anorm <= rtol -- so iteration counts are comparable with scipy's.
+ * The preconditioner is M = diag(1 / px, 1 / pc), applied element-wise (px: nvar entries, pc: ncon entries, e.g. the pair of
+ * DOCP.kkt_diag_precond / ctd_hdiag + ctd_jsq_rows); px == NULL and pc == NULL: none.  M must be positive definite.
+ * One iteration is the two launches of ctd_kktprod_dev_async plus three vector kernels, with no host synchronisation: the scalar
+ * recurrences and the stopping tests run on the device, in a state block the handle owns.  Once the status is set -- converged,
+ * breakdown (r2' M r2 negative or not finite: M is not positive definite, or a NaN appeared; or the Krylov space is exhausted
+ * without convergence), iteration cap -- the kernels of every later iteration return before they store anything: iterations
+ * enqueued past that point cost time and change no bit of z or of the state.  Every entry point enqueues a number of launches
+ * fixed by its arguments; kernel boundaries are the only synchronisation between workgroups.
+ * Results are reproducible bit for bit (fixed summation order of the inner products, documented in csrc/ctd_krylov_kernels.hpp; no
+ * floating-point atomics), equal for the host and the device form and for every pattern_mode / value_order of one transcription.
+ * No pointer needs more than 8-byte alignment.
+ * WORKSPACE: CTD_KKT_MINRES_WORKSPACE(nvar + ncon) doubles of device memory the handle owns (the Krylov vectors, the partial sums,
+ * the state), allocated by the first start and freed with the handle, plus a partial-sum buffer for its kktprod launches that is
+ * not the one of ctd_kktprod* (a graph captured over ctd_kktprod keeps working); nothing nnzj- or nnzh-sized.  The host form also
+ * stages its vectors (3 (nvar + ncon) doubles more).  One solve per handle at a time: a start discards the solve before it.
+ * Capturable after one warm start on the handle (run-time OCPs compile their KKT kernels then).
+ * OUT OF SCOPE: shard handles (the all-reduce inside the recurrences), several right-hand sides, a nonzero initial guess.
+ * Checks in this order: NULL handle -> CTD_EINVAL; sys (info) NULL or its struct_size not sizeof(ctd_kkt_system)
+ * (sizeof(ctd_minres_info)) -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle -> CTD_EINVAL (there is no shard form
+ * yet); null x, rhs or z -> CTD_EINVAL; z equal to any input -> CTD_EINVAL; only one of px / pc -> CTD_EINVAL; k, max_iter or
+ * check_every < 1, or rtol < 0 or NaN -> CTD_EINVAL; iters before any start, or with another z than the start -> CTD_EINVAL.
+ * ctd_last_error names the reason, beginning with the entry point that was called. */
+#define CTD_KKT_MINRES_WORKSPACE(n) (8 * (int64_t)(n) + 3072)
+enum { CTD_MINRES_RUNNING = 0, CTD_MINRES_CONVERGED = 1, CTD_MINRES_MAX_ITER = 2, CTD_MINRES_BREAKDOWN = 3 };
+/* the operator and the preconditioner: the arguments of ctd_kktprod (y, sx, sc may be NULL with its meaning) and px, pc (both or
+ * neither).  struct_size = sizeof(ctd_kkt_system), set by the caller */
+typedef struct ctd_kkt_system {
+    uint32_t struct_size;
+    uint32_t reserved;          /* 0 */
+    const double* x;
+    const double* y;
+    double obj_weight;
+    const double* sx;
+    const double* sc;
+    const double* px;
+    const double* pc;
+} ctd_kkt_system;
+/* struct_size = sizeof(ctd_minres_info), set by the caller; iterations: completed ones (the iterate z is theirs); phibar: the
+ * estimate of the M-norm of the residual, beta1 its initial value sqrt(rhs' M rhs); Anorm, ynorm: scipy's estimates of |K|, |z| */
+typedef struct ctd_minres_info {
+    uint32_t struct_size;
+    int32_t status;             /* CTD_MINRES_* */
+    int64_t iterations;
+    double phibar, Anorm, ynorm, beta1;
+} ctd_minres_info;
+/* Enqueue-only on the handle's stream, device pointers.  start: the initialisation (two launches): z = 0, the state; reads rhs and
+ * px, pc once (later calls do not read them again).  No iteration cap.  iters: k iterations (5 k launches) of the solve started
+ * last, on the same z; x, y, sx, sc are read by every iteration. */
+int32_t ctd_kkt_minres_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev, double rtol);
+int32_t ctd_kkt_minres_iters_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* z_dev, int64_t k);
+/* waits for the handle's stream and reads the state */
+int32_t ctd_kkt_minres_info(ctd_handle* h, ctd_minres_info* info);
+/* The drivers: start, then chunks of check_every iterations with one ctd_kkt_minres_info between chunks, until the status is set --
+ * at most ceil(max_iter / check_every) chunks: the device sets CTD_MINRES_MAX_ITER after max_iter iterations.  z does not depend
+ * on check_every.  Device pointers / host pointers (staged like the other host forms); both return when z is final. */
+int32_t ctd_kkt_minres_dev(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev, double rtol,
+                           int64_t max_iter, int64_t check_every, ctd_minres_info* info);
+int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs, double* z, double rtol, int64_t max_iter,
+                       int64_t check_every, ctd_minres_info* info);
+
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
  * ctd_sharded_handle included), modelled on ctd_grad_shard_dev_async: enqueue-only on the handle's stream, capturable after one

@@ -9,7 +9,8 @@ whole-grid kernels come first, in the order the compiler reports them (trapeze, 
 then the finish kernel), followed by the shard form of the same kernels marked "shard".  The comment lines at the head of each
 log are kept.  The KKT diagonals (hdiag, jsq_cols, jsq_rows: the whole-grid form from csrc/ctd_dkern_<problem>.hip, the shard form
 from csrc/ctd_dskern_<problem>.hip) go to a table in profiles/diag_resources.md, each shard row under its whole-grid twin; the text
-above the table is kept.  The script fails if any kernel uses scratch."""
+above the table is kept.  The script fails if any kernel uses scratch.  --krylov: the vector kernels of the device-resident MINRES
+solve (csrc/ctd_krylov.hip) to profiles/kkt_minres_resources.md, nothing else."""
 import argparse
 import os
 import re
@@ -197,13 +198,36 @@ def cons_jac_table():
                   f"| {k['sec_stores']} | {k['sgpr']} | {k['vgpr']} | {k['sgpr_spill']} / {k['vgpr_spill']} | {k['scratch']} | {k['waves']} |")
 
 
+# ---- vector kernels of the device-resident MINRES solve (csrc/ctd_krylov.hip; profiles/kkt_minres_resources.md) -----------------
+KRYLOV_KERNELS = ("krylov_init_kernel", "krylov_first_kernel", "krylov_alfa_kernel", "krylov_lanczos_kernel", "krylov_update_kernel")
+
+
+def krylov_table():
+    ks = remarks("ctd_krylov", "", KRYLOV_KERNELS)
+    assert [k["kernel"] for k in ks] == list(KRYLOV_KERNELS), ks
+    path = os.path.join(ROOT, "profiles", "kkt_minres_resources.md")
+    lines = ["# Resources of the MINRES vector kernels (csrc/ctd_krylov.hip)\n\n",
+             "From the compiler's remarks for gfx950 (`python profiles/resource_usage.py --krylov`, no GPU needed).  The kernels do not\n"
+             "depend on the OCP: one instantiation each.  The script fails if any of them uses scratch.\n\n",
+             "| kernel | VGPR + AGPR | scratch B/lane | waves/SIMD |\n", "|---|---|---|---|\n"]
+    for k in ks:
+        assert k["scratch"] == 0, k
+        lines.append(f"| {k['kernel']} | {k['vgpr']} + {k['agpr']} | {k['scratch']} | {k['waves']} |\n")
+    with open(path, "w") as f:
+        f.writelines(lines)
+    print(path, len(ks), "kernels")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--krylov", action="store_true", help="write profiles/kkt_minres_resources.md (the MINRES vector kernels) and stop")
     ap.add_argument("--cons-jac", action="store_true", help="print the table of profiles/static_emit.md (lean and static-emit kernels of cfg2 / cfg3 / cfg4) and stop")
     args = ap.parse_args()
     if args.cons_jac:
         return cons_jac_table()
+    if args.krylov:
+        return krylov_table()
     stems = [s for s, _ in PRODUCTS]
     with ThreadPoolExecutor(args.jobs) as ex:
         table = dict(zip(stems, ex.map(remarks, stems)))
