@@ -17,18 +17,14 @@ using __hip_internal::uint16_t;
 using __hip_internal::uint8_t;
 typedef unsigned long uintptr_t;
 #define CTD_HD __host__ __device__ __forceinline__
-#define CTD_STORE2(p, a, b) (*reinterpret_cast<double2*>(p) = make_double2((a), (b)))
 #elif defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define CTD_HD __host__ __device__ __forceinline__
-// one 16-byte store of two consecutive doubles (p is 16-byte aligned)
-#define CTD_STORE2(p, a, b) (*reinterpret_cast<double2*>(p) = make_double2((a), (b)))
 #else
 // The kernel bodies are plain C++ templates so that the test-suite can compile them with g++ and step them
 // serially with bounds checking (tests/emu/, test infrastructure only).  The shipped library always builds
 // them with hipcc for gfx950 and the C ABI only ever launches the HIP kernels.
 #define CTD_HD inline
-#define CTD_STORE2(p, a, b) do { (p)[0] = (a); (p)[1] = (b); } while (0)
 #endif
 
 namespace ctd {

@@ -261,6 +261,16 @@ int32_t ctd_jac_coord(ctd_handle* h, const double* x, double* vals);
 int32_t ctd_cons_jac(ctd_handle* h, const double* x, double* c, double* vals);
 
 /* ---- the hot path: device pointers (inputs and outputs stay in HBM) --------------------------------------- */
+/* POINTERS, for every entry point of this header whose name ends in _dev, _dev_async, _shard_dev_async or _batch_dev_async
+ * (this section, the Hessian, the batched callbacks, the fused iteration, the matrix-free operators, the MINRES solve and their
+ * shard forms):
+ *   - no pointer needs more than 8-byte alignment -- inputs and outputs may be slices of one workspace at any offset that is a
+ *     multiple of 8 bytes, the rows of a batched argument at any leading dimension the entry point accepts;
+ *   - nothing outside the documented output ranges is written: not one double before or after an output, none of the padding
+ *     between the rows of a batched output, and on a shard handle none of the entries the shard does not own;
+ *   - inputs are never written.
+ * The results do not depend on the addresses.  tests/test_gpu_write_sets.py holds every one of these entry points to that between
+ * guard regions (tests/guarded.py), tests/test_gpu_kkt_minres.py the MINRES solve. */
 /* c_dev has ncon entries and vals_dev nnzj entries (global indexing also for sharded handles: a shard writes only
  * its rows / its CSC ranges, see ctd_shard_info).  Either of c_dev / vals_dev may be NULL to skip that output. */
 int32_t ctd_cons_jac_dev(ctd_handle* h, const double* x_dev, double* c_dev, double* vals_dev);

@@ -11,6 +11,9 @@ BARS
                    covers the different summation order of the inner products (a tree per workgroup against NumPy's sums),
                    compounding over five iterations.  D_REF is d_ref as measured on the MI355X (the test prints it): 2.28e-12
                    (goddard, trapeze, N = 7, preconditioned, k = 5); the largest device difference measured there is 3.92e-12.
+                   Both were measured again with the N = 75 000 case included and did not move: that case's own largest
+                   figures are 1.78e-12 through the GPU operator and 1.78e-12 on the device (preconditioned, k = 2), both
+                   halves (plain and preconditioned) run -- assembling K_asm and the scipy runs take about 2 s at that size.
   the solve        N = 20 Goddard trapeze, seed 21, rtol 1e-10, cap 10 n: converged; iterations within +-2 of scipy's on K_asm
                    with the same M (the margin the project grants for last-bit differences of the operator); at most half those
                    of the unpreconditioned device solve; true residual |K_asm z - r| / |r| at most rho^2 times that of scipy's
@@ -20,10 +23,16 @@ BARS
                    solve: 310), residual 2.2915e-6 against scipy's 2.2916e-6, rho = 1.58 (rho^2 = 2.50).
 Everything else is exact: bit equality (freeze, reproducibility, capture), statuses, iteration counts, refusals.
 
-Workgroups: the vector kernels give a workgroup 1024 elements (ctd_krylov_kernels.hpp), so of the cases below N = 300 (n = 2109)
-spans 3 workgroups and N = 2000 (n = 14009) spans 14: the partial-sum path and its order are exercised; every other case is one
-workgroup, N = 1 (n = 16) less than one wave."""
+Workgroups: the vector kernels give a workgroup 1024 elements, up to 512 workgroups, then longer chunks (krylov_geom of
+ctd_krylov_kernels.hpp; `krylov_geom` below restates the rule and reads its constants from that header).  Of the cases below
+N = 300 (n = 2109) spans 3 workgroups and N = 2000 (n = 14009) spans 14: the partial-sum path and its order are exercised.
+N = 75 000 (n = 525 009) is the capped geometry: 512 workgroups with a chunk of 1280 elements, so a thread makes five passes, one
+past the four unrolled ones, every thread adds 512 partial sums, and the workgroups 411 to 511 own nothing (asserted next to
+CASES, without a GPU).  Every other case is one workgroup, N = 1 (n = 16) less than one wave."""
 import ctypes as C
+import functools
+import os
+import re
 
 import numpy as np
 import pytest
@@ -36,12 +45,45 @@ from oracle.oracle import OracleDOCP
 
 pytestmark = pytest.mark.gpu
 
-D_REF = 2.281364561561445e-12            # d_ref on the MI355X (goddard, trapeze, N = 7, preconditioned, k = 5)
+D_REF = 2.281364561561445e-12            # d_ref on the MI355X over all CASES, N = 75 000 included (goddard, trapeze, N = 7, preconditioned, k = 5)
 BAR = 10.0 * D_REF
 KS = (1, 2, 5)
 # (problem, scheme, N, run-time twin)
 CASES = [("goddard", "trapeze", N, False) for N in (1, 2, 7, 20, 300, 2000)] + \
-        [("double_integrator_path", "midpoint", 7, False), ("goddard", "gauss_legendre_2", 7, False), ("goddard", "midpoint", 7, True)]
+        [("double_integrator_path", "midpoint", 7, False), ("goddard", "gauss_legendre_2", 7, False), ("goddard", "midpoint", 7, True)] + \
+        [("goddard", "trapeze", 75000, False)]
+CAPPED = CASES[-1]                       # the case of the capped workgroup count; n = 7 N + 9 (4 N + 5 variables, 3 N + 4 constraints)
+CAPPED_N = 7 * CAPPED[2] + 9
+
+
+def krylov_constants():
+    """kKrylovBlock, kKrylovSpan, kKrylovMaxWg as csrc/ctd_krylov_kernels.hpp has them"""
+    hpp = os.path.join(os.path.dirname(os.path.abspath(ct.__file__)), "csrc", "ctd_krylov_kernels.hpp")
+    with open(hpp) as f:
+        text = f.read()
+    return tuple(int(re.search(rf"constexpr int {name} = (\d+);", text).group(1)) for name in ("kKrylovBlock", "kKrylovSpan", "kKrylovMaxWg"))
+
+
+def krylov_geom(n):
+    """(nwg, chunk) by the rule stated in ctd_krylov_kernels.hpp: min(kKrylovMaxWg, ceil(n / kKrylovSpan)) workgroups, at least one;
+    chunk = ceil(n / nwg) rounded up to a multiple of kKrylovBlock"""
+    block, span, max_wg = krylov_constants()
+    nwg = max(1, min(max_wg, -(-n // span)))
+    chunk = -(-(-(-n // nwg)) // block) * block
+    return nwg, chunk
+
+
+def capped_geometry():
+    """what the N = 75 000 case is there for: the workgroup count at its cap, more passes per thread than the four unrolled ones
+    (chunk > 1024), trailing workgroups that own nothing ((nwg - 1) chunk >= n).  Returns (nwg, chunk, first empty workgroup)"""
+    nwg, chunk = krylov_geom(CAPPED_N)
+    assert nwg == 512, (nwg, chunk)
+    assert chunk > 1024, (nwg, chunk)
+    assert (nwg - 1) * chunk >= CAPPED_N, (nwg, chunk, CAPPED_N)
+    return nwg, chunk, -(-CAPPED_N // chunk)
+
+
+assert capped_geometry() == (512, 1280, 411)                # (checked wherever this module is collected; tests/test_kkt_minres_cpu.py too)
 
 
 @pytest.fixture(scope="module")
@@ -59,10 +101,11 @@ def dev(torch, *arrays):
     return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
 
 
+@functools.lru_cache(maxsize=None)
 def minres_case(prob="goddard", sch="trapeze", N=20):
     """structural pattern: the seeded inputs (seed 21), K_asm assembled from the oracle, its blocks H and J.  N = 20 only: sx is
     shifted by max(0, -lambda_min(H)) (a dense eigendecomposition) so that K is quasi-definite, as in test_gpu_diag.py; the
-    fixed-k cases do not need definiteness"""
+    fixed-k cases do not need definiteness.  Computed once per transcription and shared: nobody writes to the result"""
     import scipy.sparse as sp
     o = OracleDOCP(prob, sch, N)
     o.set_pattern_mode(1)
@@ -244,11 +287,23 @@ def test_reproducible_host_device_offset(torch_cuda, solve20):
     zh0, ih0 = s.d.kkt_minres(c["x"], None, c["rhs"], rtol=0.0, max_iter=12)             # every optional argument left out
     zd0, id0 = s.d.kkt_minres(s.x, None, s.rhs, rtol=0.0, max_iter=12)
     assert ih0 == id0 and np.array_equal(zh0, zd0.cpu().numpy())
+    odd_offset_equals_aligned(torch, s, za, ia, 12)
+    # the same at the capped workgroup count (CAPPED: five passes per thread, 512 partial sums, empty trailing workgroups)
+    big = Solve(torch, minres_case(*CAPPED[:3]))
+    assert krylov_geom(big.n)[0] == 512 and big.n == CAPPED_N
+    zA, iA = big.run(rtol=0.0, max_iter=6)
+    assert iA.status == "max_iter" and iA.iterations == 6, iA
+    odd_offset_equals_aligned(torch, big, zA, iA, 6)
+    big.d.close()
+
+
+def odd_offset_equals_aligned(torch, s, za, ia, max_iter):
+    """rhs and z as views at an odd multiple of 8 bytes, z between guards: the bits and the info of the aligned run (za, ia)"""
     buf_r = torch.zeros(s.n + 1, dtype=torch.float64, device="cuda")
     buf_z = torch.full((s.n + 3,), 7.0, dtype=torch.float64, device="cuda")
     buf_r[1:].copy_(s.rhs)
     assert buf_r[1:].data_ptr() % 16 == 8 and buf_z[1:s.n + 1].data_ptr() % 16 == 8
-    zo, io = s.run(rhs=buf_r[1:], rtol=0.0, max_iter=12, out=buf_z[1:s.n + 1])
+    zo, io = s.run(rhs=buf_r[1:], rtol=0.0, max_iter=max_iter, out=buf_z[1:s.n + 1])
     assert io == ia and np.array_equal(zo.cpu().numpy(), za.cpu().numpy())
     assert float(buf_z[0]) == 7.0 and bool((buf_z[s.n + 1:] == 7.0).all())
 

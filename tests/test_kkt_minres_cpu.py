@@ -148,3 +148,27 @@ def test_struct_size_is_checked_before_the_device(handle):
     assert (z == 7.0).all()
     # the sizes the header states
     assert C.sizeof(lib.ctd_kkt_system) == 64 and C.sizeof(lib.ctd_minres_info) == 48
+
+
+def test_the_capped_krylov_geometry_case_reaches_the_cap():
+    """the N = 75 000 case of tests/test_gpu_kkt_minres.py is there for the geometry no other case has: 512 workgroups (the cap), a
+    chunk above 1024 elements (more passes per thread than the four unrolled ones) and trailing workgroups that own nothing.  The
+    rule is restated in Python with the constants read from csrc/ctd_krylov_kernels.hpp, so the case cannot stop exercising this
+    unnoticed when the constants move; the handle's sizes are the ones the arithmetic assumes."""
+    import test_gpu_kkt_minres as g
+    prob, sch, N, rt = g.CAPPED
+    assert g.CAPPED in g.CASES and not rt
+    d = ct.DOCP(prob, N, sch, device=-1, pattern="structural")
+    n = d.dim_NLP_variables + d.dim_NLP_constraints
+    d.close()
+    assert n == g.CAPPED_N == 525009
+    block, span, max_wg = g.krylov_constants()
+    nwg, chunk = g.krylov_geom(n)
+    assert nwg == max_wg == 512
+    assert chunk > 1024 and chunk % block == 0 and chunk > 4 * block           # five passes of 256 threads
+    assert (nwg - 1) * chunk >= n                                              # the last workgroup owns nothing ...
+    assert g.capped_geometry() == (512, 1280, 411)                             # ... nor do the workgroups 411 to 511
+    assert nwg * chunk >= n                                                    # (and the chunks cover the vector)
+    # every other case stays below the cap, the largest one spanning several workgroups
+    others = [7 * c[2] + 9 for c in g.CASES if c[:2] == ("goddard", "trapeze") and c is not g.CAPPED]
+    assert max(g.krylov_geom(k)[0] for k in others) == 14 and all(g.krylov_geom(k)[1] <= span for k in others)
