@@ -74,11 +74,7 @@ struct ctd_handle {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int64_t step_begin = 0, step_end = 0;
-    int tile = 0, block = 256;
-    int lean_ok = 1;            // registry OCPs: the lean variant of the constraint / Jacobian kernel may be launched (env CTD_LEAN=0: never)
-    KParams kp;                 // device pointers filled in, outputs set per call
-    size_t lds_bytes = 0;
-    int grid = 0;
+    LaunchPlan plan;            // constraint / Jacobian kernel (plan_cons_jac): plan.kp with the device pointers filled in, outputs set per call
     // static device data
     DevBuf<double> d_tau;
     DevBuf<uint32_t> d_tmpl, d_vtmpl;
@@ -123,7 +119,6 @@ struct ctd_handle {
     // batched callbacks (ctd_*_batch_dev_async): doubles of Hessian partial sums per member -- the partial-sum buffers grow with
     // the batch
     int64_t hpart_member = 0;
-    double out_mb = 0.0;            // megabytes of constraint / Jacobian outputs of one evaluation (the write-through rule, ctd_create)
     // matrix-free Jacobian products (ctd_jprod*, ctd_jtprod*): per-workgroup partial sums of d/dv, host-call staging of the
     // direction and the product (nvar / ncon entries: nothing proportional to nnzj)
     DevBuf<> d_ppartial, d_pdir, d_pout;
@@ -146,10 +141,9 @@ struct ctd_handle {
     std::string err;
 };
 
-// write-through stores (emit_store) for launches whose outputs are small: what a kernel leaves dirty in the XCDs' L2s is written
-// back at its end, serial with the next launch.  Outputs up to these many megabytes (MI355X sweeps, profiles/r03_experiments.md)
-constexpr double kWtMB = 64.0;          // constraint / Jacobian
-constexpr double kHessWtMB = 16.0;      // Hessian (gains up to ~10 MB, even at 16, losses from ~80)
+// write-through stores of the Hessian kernel, as write_through (ctd_host.cpp) for the constraint / Jacobian kernel: outputs up to
+// these many megabytes (gains up to ~10 MB, even at 16, losses from ~80)
+constexpr double kHessWtMB = 16.0;
 
 static thread_local std::string g_create_err;      // error of this thread's last failed handle-less call (ctd_last_error(NULL))
 
@@ -395,6 +389,21 @@ static int32_t jit_load(ctd_handle* h, JitFamily fam, bool shard = false) {
     return fail(eh, CTD_EHIP, std::string(kJit[fam].header) + " module: " + hipGetErrorString(e));
 }
 
+// Workgroups of the handle's constraint / Jacobian kernel that one CU keeps resident, as the runtime computes it from the kernel's
+// registers and `lds_bytes` of LDS at `block` lanes; 0: the query failed.  The Resident of the launch plan (plan_cons_jac) and
+// ctd_launch_info's.  A registry problem is always asked about its GENERAL kernel (occupancy_cons_jac), also where the lean or
+// the static-emit form is launched: the tile choices were measured with that answer.
+static int resident_cons_jac(const ctd_handle* h, const KParams& kp, int block, size_t lds_bytes) {
+    DeviceGuard dg(h->device);
+    int per_cu = 0;
+    if (dg.err == hipSuccess) {
+        if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit[JIT_FIRST][0].f[0], block, lds_bytes) != hipSuccess) per_cu = 0; }
+        else for_problem(h->model.problem, [&](auto tag) { per_cu = occupancy_cons_jac<typename decltype(tag)::type>(kp, block, lds_bytes); });
+    }
+    (void)hipGetLastError();
+    return per_cu;
+}
+
 // A host array of a host-pointer call and the handle's buffer that stages it: n doubles (a null host pointer is not staged)
 template <class T> struct Staged { T* host; DevBuf<>& buf; int64_t n; };
 
@@ -563,110 +572,22 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
     if (h->step_begin == 0 && h->step_end == 0) h->step_end = mo.L.N;
     if (h->step_begin < 0 || h->step_end > mo.L.N || h->step_begin >= h->step_end)
         return fail(nullptr, CTD_EINVAL, "ctd_create: shard [step_begin, step_end) is not inside [0, N)");
-    h->tile = env_int("CTD_TILE", 0);
-    h->lean_ok = env_int("CTD_LEAN", 1) ? 1 : 0;
-    // bit 1: the static-emit form of the lean kernel (launch_variant) -- registry OCPs, manual pattern in CSC order, the whole grid
-    if (h->lean_ok && env_int("CTD_STATIC_EMIT", 1) && !runtime_ocp(mo.problem) && mo.pattern_mode == 0 && mo.order == 0 &&
-        h->step_begin == 0 && h->step_end == mo.L.N)
-        h->lean_ok |= 2;
-    if (h->tile <= 0) h->tile = default_tile(mo, h->step_end - h->step_begin);
-    int maxb = 256;
-    for_problem(mo.problem, [&](auto tag) { maxb = decltype(tag)::type::MAXB; });
     h->rt = runtime_ocp(mo.problem);
-    if (h->rt) maxb = h->rt->maxb;
-    h->block = env_int("CTD_BLOCK", 0);
-    if (h->block <= 0) {
-        // 256 lanes, or 320 on small grids (everything resident at once) when a fifth wave lets the emit phase hold one more
-        // replica of the CSC period: 10 000-step Goddard / GL2, period 102: 3 x 102 = 306 of 320 lanes, 7.5 us vs 7.8 us
-        h->block = 256;
-        const int64_t ntl = (h->step_end - h->step_begin + h->tile - 1) / h->tile;
-        // (not for the wide OCPs: their kernels keep fewer workgroups resident with five waves each -- 8-state quadrotor, 2 controls per
-        // step, optimized pattern, 40-step tiles: 501 workgroups no longer start together, 14.4 us against 8.8)
-        if (ntl <= 512 && mo.nch_dyn <= 1 && mo.Lseg > 0 && 320 / mo.Lseg > 256 / mo.Lseg && mo.Lseg * (320 / mo.Lseg) * 10 >= 320 * 9) h->block = 320;
-        // (a fifth wave for the symbolic path rows of the wide OCPs was measured slower -- quadrotor12 midpoint N = 20 000 30.1 us
-        // against 24.4 -- and is gone: profiles/r03_experiments.md)
-    }
-    if (h->block < 64 || (h->block % 64)) h->block = 256;
-    if (h->block > maxb) h->block = maxb;
-    mo.fill_kparams(h->kp, h->step_begin, h->step_end, h->tile);
-    h->lds_bytes = (size_t)lds_doubles(h->kp) * sizeof(double);
-    const int debug_stop = env_int("CTD_DEBUG_STOP", 0);
-    const size_t lds_cap = h->rt ? 64 * 1024 : 80 * 1024;   // module-API kernels stay inside the default 64 KiB of dynamic LDS
-    while (h->lds_bytes > lds_cap && h->tile > 1) {        // a requested tile that does not fit (2 workgroups / CU) is shrunk, not rejected
-        h->tile = (h->tile + 1) / 2;
-        mo.fill_kparams(h->kp, h->step_begin, h->step_end, h->tile);
-        h->lds_bytes = (size_t)lds_doubles(h->kp) * sizeof(double);
-    }
-    // Gauss-Legendre schemes of the narrow OCPs on long grids: the kernel keeps R workgroups per CU resident (R from the runtime:
-    // registers and LDS of the instantiation), a round of 256 R tiles, and its time follows rounds x steps per tile -- Goddard GL3,
-    // N = 80 000 at the 32 steps of default_tile: 2501 tiles = 2.44 rounds of 1024, the workgroups start in three waves
-    // (profiles/r03_phase_stamps_final.log: start percentiles 0.1 / 10.1 / 19.3 us).  A tile of up to 48 steps with the same R fixes
-    // the number of rounds, the steps are spread evenly over them: 40 steps = 2001 tiles, 28.3 -> 26.9 us, optimized pattern
-    // 20.3 -> 17.9; N = 200 000: 79.9 -> 74.3 (profiles/r03_experiments.md).  Only ever a LARGER tile than the rule's.
-    const bool long_mid = mo.L.sc == SC_MIDPOINT && mo.L.cs == 1;      // midpoint and both Euler schemes (one point per step): long-grid rule only
-    if (desc->device >= 0 && !h->rt && env_int("CTD_TILE", 0) <= 0 && mo.nch_dyn <= 1 && (mo.L.sc == SC_IRK || long_mid) && h->tile >= 16) {
-        DeviceGuard dgq(desc->device);
-        if (dgq.err == hipSuccess) {
-            auto resident = [&](int tile, size_t& lds) {
-                KParams kq;
-                mo.fill_kparams(kq, h->step_begin, h->step_end, tile);
-                lds = (size_t)lds_doubles(kq) * sizeof(double);
-                int r = 0;
-                for_problem(mo.problem, [&](auto tag) { r = occupancy_cons_jac<typename decltype(tag)::type>(kq, h->block, lds); });
-                (void)hipGetLastError();
-                return r;
-            };
-            size_t l0 = 0;
-            const int r0 = resident(h->tile, l0);
-            const int64_t ns = h->step_end - h->step_begin, cap = 256 * (int64_t)r0;
-            // VERY long grids (8 rounds of resident workgroups and more: from ~half a million steps; crossover measured in
-            // profiles/r04_long_grid_crossover.log: 2^18 steps +-5 % either way, 2^19 +3 .. +15 %, 2^20 +5 .. +18 %) are bandwidth-bound, the rounds no
-            // longer quantise anything, and what is left per tile is its fixed cost -- launch slot, argument pinning, time table,
-            // prologue latency.  Eight waves per workgroup and the largest tile whose records fit 64 KiB of LDS (two workgroups
-            // per CU) amortise it: Goddard GL2, 4 194 304 steps 930 -> 795 us (0.59 -> 0.69 of 8 TB/s), GL3 1333 -> 1297,
-            // double integrator + path GL2 508 -> 460, double integrator free t0 / tf GL3 915 -> 800, goddard_all GL2 (2 M steps,
-            // staged driver) 598 -> 556; the midpoint scheme (records up to 74 KiB): double integrator + path, 8 M steps 506 -> 421, Goddard 4 M 350 -> 283, explicit / implicit Euler 335 -> 288 / 294, DI + path Euler 8 M 455 -> 367;
-            // trapeze: flat, left alone (profiles/r04_tiles_long_grids.log; CTD_LONG_GRID=0: off; CTD_LONG_GRID_ROUNDS: the threshold, for tests)
-            if (r0 > 0 && (ns + h->tile - 1) / h->tile >= env_int("CTD_LONG_GRID_ROUNDS", 8) * cap && maxb >= 512 && env_int("CTD_BLOCK", 0) <= 0 &&
-                env_int("CTD_LONG_GRID", 1)) {
-                int tbest = h->tile;
-                for (int tt = h->tile + 1; tt <= 256; ++tt) {
-                    KParams kq;
-                    mo.fill_kparams(kq, h->step_begin, h->step_end, tt);
-                    if ((size_t)lds_doubles(kq) * sizeof(double) > (long_mid ? 74u : 64u) * 1024) break;
-                    tbest = tt;
-                }
-                if (tbest > h->tile) {
-                    h->tile = tbest;
-                    h->block = 512;
-                    mo.fill_kparams(h->kp, h->step_begin, h->step_end, h->tile);
-                    h->lds_bytes = (size_t)lds_doubles(h->kp) * sizeof(double);
-                }
-            } else if (mo.L.sc == SC_IRK && r0 > 0 && (ns + h->tile - 1) / h->tile > cap) {
-                int tmax = 48;
-                for (; tmax > h->tile; --tmax) { size_t l = 0; if (resident(tmax, l) >= r0 && l <= lds_cap) break; }
-                const int64_t rounds = (ns + (int64_t)tmax * cap - 1) / ((int64_t)tmax * cap);
-                const int64_t tb = (ns + rounds * cap - 1) / (rounds * cap);
-                if (tb > h->tile && tb <= tmax) {
-                    h->tile = (int)tb;
-                    mo.fill_kparams(h->kp, h->step_begin, h->step_end, h->tile);
-                    h->lds_bytes = (size_t)lds_doubles(h->kp) * sizeof(double);
-                }
-            }
-        }
-    }
-    h->grid = h->kp.ntiles + h->kp.has_edge;
-    h->kp.debug_stop = debug_stop;
-    h->out_mb = 8.0 * ((double)(h->step_end - h->step_begin) * (mo.L.cb + mo.Lseg + (double)mo.L.nv * mo.vr)) / 1.0e6;
-    h->kp.wt_store = h->out_mb <= kWtMB ? 1 : 0;
-    if (const int wt = env_int("CTD_WT_STORE", -1); wt >= 0) h->kp.wt_store = wt ? 1 : 0;      // (tests: either store flavour on any grid)
     h->device = desc->device;
+    Resident resident;
+    int cus = 256;
     if (h->device >= 0) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || h->device >= ndev)
             return fail(nullptr, CTD_ENODEVICE, "ctd_create: HIP device not available");
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
+        resident = [hp = h.get()](const KParams& kp, int block, size_t lds_bytes) { return resident_cons_jac(hp, kp, block, lds_bytes); };
+    }
+    if (const int pst = plan_cons_jac(mo, h->step_begin, h->step_end, plan_knobs_from_env(), resident, cus, kMultiTileLoop, h->plan, err))
+        return fail(nullptr, pst, err);
+    if (h->device >= 0) {
         ctd_handle* hp = h.get();
-        if (h->lds_bytes > 160 * 1024) return fail(nullptr, CTD_EINVAL, "ctd_create: tile does not fit the 160 KiB LDS");
+        KParams& kp = hp->plan.kp;
         DeviceGuard dg_(hp->device); HIP_TRY(nullptr, dg_.err);
         if (desc->stream_mode == CTD_STREAM_GIVEN) { hp->stream = (hipStream_t)desc->stream; hp->own_stream = false; }
         else { HIP_TRY(nullptr, hipStreamCreateWithFlags(&hp->stream, hipStreamNonBlocking)); hp->own_stream = true; }
@@ -679,67 +600,23 @@ int32_t ctd_create(const ctd_desc* desc, ctd_handle** out) {
         HIP_TRY(nullptr, upload(hp->d_vtmpl, mo.vtmpl));
         HIP_TRY(nullptr, upload(hp->d_edge_idx, mo.edge_idx));
         HIP_TRY(nullptr, upload(hp->d_edge_code, mo.edge_code));
-        hp->kp.tau = hp->d_tau.p;
-        hp->kp.tmpl = hp->d_tmpl.p;
-        hp->kp.vtmpl = hp->d_vtmpl.p;
-        // early emission (ctd_layout.hpp KParams::pos): direct tiles of the Gauss-Legendre schemes, when the lead wave can hold one
-        // lane per early output of a step and the late positions fit the workgroup.  OFF by default (CTD_EARLY=1 switches it on):
-        // measured on MI355X it LOSES -- Goddard GL2 N = 10 000: 8.4 us against 6.2, GL3 optimized pattern 28.8 against 20.1
-        // (profiles/r03_experiments.md) -- the early and the late stores each write PARTS of the same 128-byte lines (the state
-        // rows and the stage rows of one CSC column interleave), and two partial-line writes cost more than the overlap gains
-        {
-            const int S = mo.L.s, r_dyn = S * mo.nch_dyn, r_path = mo.nch_path;
-            int lgT = 0;
-            while ((1 << lgT) < hp->tile) ++lgT;
-            const int leadbase = (((r_dyn + r_path) << lgT) + 63) & ~63;
-            const int early_lanes = mo.n_early + mo.c_early + mo.L.nv * mo.vr_early;
-            if (env_int("CTD_EARLY", 0) && mo.n_early > 0 && !hp->rt && mo.fused && hp->tile <= 32 && leadbase + 64 <= hp->block && early_lanes <= 64 &&
-                mo.n_late > 0 && mo.n_late <= hp->block) {
-                HIP_TRY(nullptr, upload(hp->d_pos, mo.pos_order));
-                hp->kp.pos = hp->d_pos.p;
-                hp->kp.n_late = mo.n_late; hp->kp.n_early = mo.n_early; hp->kp.c_early = mo.c_early; hp->kp.vr_early = mo.vr_early;
-                hp->kp.div_late = make_fastdiv((uint32_t)mo.n_late);
-            }
+        kp.tau = hp->d_tau.p;
+        kp.tmpl = hp->d_tmpl.p;
+        kp.vtmpl = hp->d_vtmpl.p;
+        if (hp->plan.early) {
+            HIP_TRY(nullptr, upload(hp->d_pos, mo.pos_order));
+            kp.pos = hp->d_pos.p;
         }
-        hp->kp.edge_idx = hp->d_edge_idx.p;
-        hp->kp.edge_code = hp->d_edge_code.p;
+        kp.edge_idx = hp->d_edge_idx.p;
+        kp.edge_code = hp->d_edge_code.p;
         hp->obj_blocks = 256;
         HIP_TRY(nullptr, hp->d_partial.ensure(hp->obj_blocks));
         HIP_TRY(nullptr, hp->d_obj.ensure(1));
         HIP_TRY(nullptr, hipEventCreate(&hp->ev0));
         HIP_TRY(nullptr, hipEventCreate(&hp->ev1));
         if (hp->rt) {
-            if (hp->lds_bytes > 64 * 1024) return fail(nullptr, CTD_EINVAL, "ctd_create: one step of this run-time OCP does not fit 64 KiB of LDS");
             const int32_t jst = jit_load(hp, JIT_FIRST);
             if (jst) return jst;
-        }
-        // Multi-tile workgroups (staged driver only; KParams::wg_stride): when the tiles need several rounds of resident
-        // workgroups, launch ONE round and let every workgroup walk its share of the tiles -- templates / v / codes fetched once
-        // per workgroup, the next tile's x slice in flight during the emission.  The round is what the runtime says is resident
-        // (registers and LDS of this very kernel).  EXPERIMENT: builds with -DCTD_MULTI_TILE_LOOP=1 and CTD_MULTI_TILE=1 (k > 1: k
-        // workgroups per CU) only -- measured slower than the hardware's own dispatch of one tile per workgroup (ctd_kernels.hpp).
-        {
-            const bool direct = mo.fused && mo.L.sc != SC_TRAPEZE;
-            const int mt = env_int("CTD_MULTI_TILE", 0);
-            if (!direct && mt > 0 && kMultiTileLoop && !hp->rt) {
-                int per_cu = mt > 1 ? mt : 0, cus = 256;
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hp->device) != hipSuccess) cus = 256;
-                if (per_cu == 0) {
-                    if (hp->rt) {
-                        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hp->jit[JIT_FIRST][0].f[0], hp->block, hp->lds_bytes) != hipSuccess) per_cu = 0;
-                    } else {
-                        for_problem(mo.problem, [&](auto tag) {
-                            using P = typename decltype(tag)::type;
-                            per_cu = occupancy_cons_jac<P>(hp->kp, hp->block, hp->lds_bytes);
-                        });
-                    }
-                }
-                const int64_t cap = (int64_t)per_cu * cus - hp->kp.has_edge;      // (the edge blocks hold slots of their own)
-                if (cap > 0 && hp->kp.ntiles > cap) {
-                    hp->kp.wg_stride = (int)cap;
-                    hp->grid = hp->kp.wg_stride + hp->kp.has_edge;
-                }
-            }
         }
     }
     *out = h.release();
@@ -943,7 +820,7 @@ int32_t ctd_set_x_shards(ctd_handle* h, int32_t n_shards, const int64_t* step_be
     if (!h) return CTD_EINVAL;
     if (h->device < 0) return fail(h, CTD_ENODEVICE, "host-only handle");
     if (n_shards <= 0 || !step_begin || !x_bufs) {         // back to "x holds everything this handle reads"
-        h->kp.halo = nullptr;
+        h->plan.kp.halo = nullptr;
         h->halo_host.G = 0;
         return CTD_OK;
     }
@@ -961,14 +838,14 @@ int32_t ctd_set_x_shards(ctd_handle* h, int32_t n_shards, const int64_t* step_be
         t.x[k] = k == self ? nullptr : x_bufs[k];
     }
     t.vbegin[n_shards] = L.v_off;       // the last shard also owns the final node; v is replicated
-    if (h->kp.halo && std::memcmp(&t, &h->halo_host, sizeof(XHalo)) == 0) return CTD_OK;
+    if (h->plan.kp.halo && std::memcmp(&t, &h->halo_host, sizeof(XHalo)) == 0) return CTD_OK;
     DeviceGuard dg_(h->device); HIP_TRY(h, dg_.err);
     HIP_TRY(h, h->d_halo.ensure(1));
     HIP_TRY(h, hipStreamSynchronize(h->stream));           // launches in flight still read the old table
     HIP_TRY(h, hipMemcpy(h->d_halo.p, &t, sizeof(XHalo), hipMemcpyHostToDevice));
     h->halo_host = t;
-    h->kp.halo = h->d_halo.p;
-    h->kp.near = make_xnear(t, L.blk, L.N, L.v_off);
+    h->plan.kp.halo = h->d_halo.p;
+    h->plan.kp.near = make_xnear(t, L.blk, L.N, L.v_off);
     return CTD_OK;
 }
 
@@ -1104,25 +981,12 @@ int32_t ctd_ipc_close(int32_t device, void* base) {
 
 int32_t ctd_launch_info(const ctd_handle* h, int64_t* o) {
     if (!h || !o) return CTD_EINVAL;
-    o[0] = h->grid; o[1] = h->block; o[2] = (int64_t)h->lds_bytes; o[3] = h->tile; o[4] = h->model.Lseg;
+    o[0] = h->plan.grid; o[1] = h->plan.block; o[2] = (int64_t)h->plan.lds_bytes; o[3] = h->plan.tile; o[4] = h->model.Lseg;
     o[5] = (int64_t)h->model.edge_idx.size();
     o[6] = (h->model.fused && h->model.L.sc != SC_TRAPEZE) ? 1 : 0;      // DirectTile<P, SC>
     // resident workgroups per CU of the kernel this handle launches, as the runtime computes it from the kernel's registers and
     // LDS (0: host-only handle / query failed): the tiles' rounds = grid / (o[7] * CUs)
-    o[7] = 0;
-    if (h->device >= 0) {
-        DeviceGuard dg(h->device);
-        int per_cu = 0;
-        if (dg.err == hipSuccess) {
-            if (h->rt) { if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit[JIT_FIRST][0].f[0], h->block, h->lds_bytes) != hipSuccess) per_cu = 0; }
-            else for_problem(h->model.problem, [&](auto tag) {
-                using P = typename decltype(tag)::type;
-                per_cu = occupancy_cons_jac<P>(h->kp, h->block, h->lds_bytes);
-            });
-        }
-        (void)hipGetLastError();
-        o[7] = per_cu;
-    }
+    o[7] = h->device >= 0 ? resident_cons_jac(h, h->plan.kp, h->plan.block, h->plan.lds_bytes) : 0;
     return CTD_OK;
 }
 
@@ -1139,33 +1003,33 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
     const OnDevice on(h);
     if (on.st) return on.st;
     if (!x_dev) return fail(h, CTD_EINVAL, "x is null");
-    KParams kp = h->kp;
+    KParams kp = h->plan.kp;
     kp.c = c_dev;
     kp.vals = vals_dev;
     hipError_t e = hipErrorInvalidValue;
     if (bt) {      // the batched instantiation of the kernel: grid (tiles, members)
         BatchLd bl{bt->ldx, bt->ldc, bt->ldv};
-        // write-through stores by the rule of ctd_create, applied to what the whole LAUNCH writes (all members)
-        kp.wt_store = h->out_mb * bt->n <= kWtMB ? 1 : 0;
+        // write-through stores by the rule of the plan (plan_cons_jac), applied to what the whole LAUNCH writes (all members)
+        kp.wt_store = write_through(h->plan.out_mb * bt->n);
         if (h->rt) {
             if (const int32_t jst = jit_load(h, JIT_BATCH)) return jst;
             void* args[] = {&kp, &x_dev, &bl};
-            e = jit_launch(h->jit[JIT_BATCH][0].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
+            e = jit_launch(h->jit[JIT_BATCH][0].f[0], h->plan.grid, h->plan.block, h->plan.lds_bytes, h->stream, args, nullptr, nullptr, bt->n);
         }
         for_problem(h->model.problem, [&](auto tag) {
             using P = typename decltype(tag)::type;
-            e = launch_cons_jac_batch<P>(kp, x_dev, bl, h->grid, h->block, h->lds_bytes, h->stream, bt->n);
+            e = launch_cons_jac_batch<P>(kp, x_dev, bl, h->plan.grid, h->plan.block, h->plan.lds_bytes, h->stream, bt->n);
         });
         if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
         return CTD_OK;
     }
     if (h->rt) {
         void* args[] = {&kp, &x_dev};
-        e = jit_launch(h->jit[JIT_FIRST][0].f[0], h->grid, h->block, h->lds_bytes, h->stream, args, te0, te1);
+        e = jit_launch(h->jit[JIT_FIRST][0].f[0], h->plan.grid, h->plan.block, h->plan.lds_bytes, h->stream, args, te0, te1);
     }
     for_problem(h->model.problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
-        e = launch_cons_jac<P>(kp, x_dev, h->grid, h->block, h->lds_bytes, h->stream, te0, te1, h->lean_ok);
+        e = launch_cons_jac<P>(kp, x_dev, h->plan.grid, h->plan.block, h->plan.lds_bytes, h->stream, te0, te1, h->plan.lean_ok);
     });
     if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return CTD_OK;
@@ -1278,8 +1142,8 @@ static int fill_obj_params(ctd_handle* h, double* f_dev, ObjParams& op) {
     op.add_mayer = last ? 1 : 0;
     op.partial = h->d_partial.p;
     op.out = f_dev;
-    op.halo = h->kp.halo;
-    op.near = h->kp.near;
+    op.halo = h->plan.kp.halo;
+    op.near = h->plan.kp.near;
     const int64_t units = op.unit_end - op.unit_begin;
     int blocks = (int)((units + 255) / 256);
     if (blocks > h->obj_blocks) blocks = h->obj_blocks;
@@ -1344,7 +1208,7 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
     gp.unit_begin = ub; gp.unit_end = ue;
     gp.owns_first = (!shard || first) ? 1 : 0;
     gp.owns_last = (!shard || last) ? 1 : 0;
-    if (shard) { gp.halo = h->kp.halo; gp.near = h->kp.near; }
+    if (shard) { gp.halo = h->plan.kp.halo; gp.near = h->plan.kp.near; }
     if (only_params) { gp.nblocks = h->model.info.lagrange ? blocks : 0; *only_params = gp; return CTD_OK; }
     // With a Lagrange cost the per-step kernel writes every entry of the step blocks (owner computes), only the tail
     // (final state, variables) needs zeroing before the finish kernel adds the Mayer part; a Mayer-only gradient is zero
@@ -1403,7 +1267,7 @@ int32_t ctd_grad(ctd_handle* h, const double* x, double* g) {
 static int32_t mf_check(const OnDevice& on, ctd_handle* h, const MfCall& c, std::initializer_list<const double*> req,
                         std::initializer_list<const double*> opt, std::initializer_list<const double*> out) {
     if (on.st) return on.st;
-    if (!c.shard() && (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo))
+    if (!c.shard() && (h->step_begin != 0 || h->step_end != h->model.L.N || h->plan.kp.halo))
         return fail(h, CTD_EINVAL, std::string(c.fn()) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
                                    "step_end, ctd_set_x_shards) is out of scope for this call: a shard handle calls " + c.op.name[MF_SHARD]);
     for (const auto& ptrs : {req, out})
@@ -1435,7 +1299,7 @@ static ProdParams prod_params(const ctd_handle* h, const MfCall& c, const double
     pp.unit_end = last ? N + 1 : h->step_end;
     pp.owns_first = first ? 1 : 0;
     pp.owns_last = last ? 1 : 0;
-    if (shard) { pp.halo = h->kp.halo; pp.near = h->kp.near; }
+    if (shard) { pp.halo = h->plan.kp.halo; pp.near = h->plan.kp.near; }
     return pp;
 }
 
@@ -1652,7 +1516,7 @@ static bool mr_structs_ok(ctd_handle* h, const char* fn, const ctd_kkt_system* s
 static int32_t mr_check(const OnDevice& on, ctd_handle* h, const MfCall& c, const ctd_kkt_system* sys, const double* rhs, const double* z,
                         bool with_rhs) {
     if (on.st) return on.st;
-    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->plan.kp.halo)
         return fail(h, CTD_EINVAL, std::string(c.fn()) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
                                    "step_end, ctd_set_x_shards) is out of scope: the solve has no shard form yet (it needs the "
                                    "all-reduce of ctd_kktprod_shard_dev_async's partial sums and of the inner products)");
@@ -1816,17 +1680,17 @@ int32_t ctd_debug_stamps(ctd_handle* h, const double* x_dev, double* c_dev, doub
     if (!h || !out) return CTD_EINVAL;
     const OnDevice on(h);
     if (on.st) return on.st;
-    int64_t words = (int64_t)h->grid * 12;
+    int64_t words = (int64_t)h->plan.grid * 12;
     if (cap < words) return fail(h, CTD_EINVAL, "stamp buffer too small");
-    if (cap >= (int64_t)h->grid * 28) words = (int64_t)h->grid * 28;      // + sub-stamps of experiment builds (CTD_SUBSTAMPS)
+    if (cap >= (int64_t)h->plan.grid * 28) words = (int64_t)h->plan.grid * 28;      // + sub-stamps of experiment builds (CTD_SUBSTAMPS)
     unsigned long long* d_st = nullptr;
     HIP_TRY(h, hipMalloc((void**)&d_st, sizeof(unsigned long long) * words));
     HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(unsigned long long) * words, h->stream));
     int32_t st = enqueue_cons_jac(h, x_dev, c_dev, vals_dev);     // warm, no stamps
     if (st == CTD_OK) {
-        h->kp.stamps = d_st;
+        h->plan.kp.stamps = d_st;
         st = enqueue_cons_jac(h, x_dev, c_dev, vals_dev);
-        h->kp.stamps = nullptr;
+        h->plan.kp.stamps = nullptr;
     }
     if (st == CTD_OK) {
         hipError_t e = hipMemcpyAsync(out, d_st, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, h->stream);
@@ -1971,7 +1835,7 @@ static int32_t ensure_hess(ctd_handle* h) {
     // V x V partials: added in a fixed order by a second, one-workgroup kernel (a last-workgroup finish inside the main
     // kernel measured 2-7x slower on MI355X, profiles/r01_hessian_kernel.md: device-scope release per workgroup)
     hp.debug_stop = env_int("CTD_HESS_STOP", 0);
-    // write-through value stores for small Hessians (as for the constraint / Jacobian kernel, ctd_create)
+    // write-through value stores for small Hessians (as for the constraint / Jacobian kernel, plan_cons_jac)
     hp.wt_store = 8.0 * (double)(h->hp.step_end - h->hp.step_begin) * (double)H.Lseg / 1.0e6 <= kHessWtMB ? 1 : 0;
     if (h->hess_step) {
         HIP_TRY(h, upload(h->d_hssrc, ssrc));
@@ -2033,8 +1897,8 @@ static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_
     if (bt) { hp.ldx = bt->ldx; hp.ldy = bt->ldy; hp.ldh = bt->ldh; hp.part_stride = h->hpart_member; }
     hp.obj_weight = obj_weight;
     hp.vals = vals_dev;
-    hp.halo = h->kp.halo;
-    hp.near = h->kp.near;
+    hp.halo = h->plan.kp.halo;
+    hp.near = h->plan.kp.near;
     if (hp.halo) { hp.own_lo = h->halo_host.vbegin[h->halo_host.self]; hp.own_hi = h->halo_host.vbegin[h->halo_host.self + 1]; }
     hipError_t e = hipErrorInvalidValue;
     if (h->rt) {
@@ -2091,7 +1955,7 @@ constexpr int32_t kMaxBatch = 65535;       // the grid's y limit
 static int32_t batch_check(const OnDevice& on, ctd_handle* h, const char* fn, int32_t batch, const double* x_dev, int64_t ldx) {
     if (on.st) return on.st;
     if (batch < 1 || batch > kMaxBatch) return fail(h, CTD_EINVAL, std::string(fn) + ": batch must be in [1, 65535], got " + std::to_string(batch));
-    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->kp.halo)
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->plan.kp.halo)
         return fail(h, CTD_EINVAL, std::string(fn) + ": batched calls need a handle of the whole grid; a shard handle (step_begin / step_end, "
                                    "ctd_set_x_shards) evaluates one iterate per call");
     if (!x_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": x is null");
@@ -2171,10 +2035,10 @@ int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double*
     IterParams ip;
     std::memset(&ip, 0, sizeof(ip));
     size_t lds = 4 * kMaxNV * sizeof(double) + 64;
-    ip.kp = h->kp;       // (Layout is read from kp / hp / gp / op by the respective bodies)
+    ip.kp = h->plan.kp;       // (Layout is read from kp / hp / gp / op by the respective bodies)
     ip.hp = h->hp;
-    ip.hp.halo = h->kp.halo;
-    ip.hp.near = h->kp.near;
+    ip.hp.halo = h->plan.kp.halo;
+    ip.hp.near = h->plan.kp.near;
     if (ip.hp.halo) { ip.hp.own_lo = h->halo_host.vbegin[h->halo_host.self]; ip.hp.own_hi = h->halo_host.vbegin[h->halo_host.self + 1]; }
     // The fused grid always carries the TILE body of the Hessian, also on handles whose stand-alone hess_coord runs the
     // lane-per-step kernel (Gauss-Legendre 2 from 9 000 steps, 3 from 28 000: ensure_hess).  Measured with the fused first-order
@@ -2189,8 +2053,8 @@ int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double*
     if (c_dev || vals_dev) {
         ip.kp.c = c_dev;
         ip.kp.vals = vals_dev;
-        ip.nb_cj = h->grid;
-        lds = std::max(lds, h->lds_bytes);
+        ip.nb_cj = h->plan.grid;
+        lds = std::max(lds, h->plan.lds_bytes);
     }
     if (g_dev) {
         st = enqueue_grad(h, x_dev, g_dev, &ip.gp);          // fills the parameters only (and sizes the partials buffer)
@@ -2456,7 +2320,7 @@ int32_t ctd_cons_jac_sharded_dev_async(ctd_sharded* s, double* const* x_dev, dou
             sb[G] = N;
         }
         for (int k = 0; k < G; ++k) {
-            const int32_t st = peer ? ctd_set_x_shards(s->h[k], G, sb, x_dev, k) : (s->h[k]->kp.halo ? ctd_set_x_shards(s->h[k], 0, nullptr, nullptr, 0) : CTD_OK);
+            const int32_t st = peer ? ctd_set_x_shards(s->h[k], G, sb, x_dev, k) : (s->h[k]->plan.kp.halo ? ctd_set_x_shards(s->h[k], 0, nullptr, nullptr, 0) : CTD_OK);
             if (st) return sfail(s, st, ctd_last_error(s->h[k]));
         }
         // ... and the cheap half of the copying protocol stays: every shard marks the point of ITS stream behind which its buffer holds

@@ -1107,6 +1107,155 @@ void Model::fill_kparams(KParams& kp, int64_t step_begin, int64_t step_end, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// launch plan of the constraint / Jacobian kernel
+// ------------------------------------------------------------------------------------------------------
+PlanKnobs plan_knobs_from_env() {
+    auto env_int = [](const char* name, int dflt) {
+        const char* s = std::getenv(name);
+        return (s && *s) ? std::atoi(s) : dflt;
+    };
+    PlanKnobs k;
+    k.tile = env_int("CTD_TILE", k.tile);
+    k.block = env_int("CTD_BLOCK", k.block);
+    k.lean = env_int("CTD_LEAN", k.lean);
+    k.static_emit = env_int("CTD_STATIC_EMIT", k.static_emit);
+    k.long_grid = env_int("CTD_LONG_GRID", k.long_grid);
+    k.long_grid_rounds = env_int("CTD_LONG_GRID_ROUNDS", k.long_grid_rounds);
+    k.wt_store = env_int("CTD_WT_STORE", k.wt_store);
+    k.early = env_int("CTD_EARLY", k.early);
+    k.multi_tile = env_int("CTD_MULTI_TILE", k.multi_tile);
+    k.debug_stop = env_int("CTD_DEBUG_STOP", k.debug_stop);
+    return k;
+}
+
+// write-through stores (emit_store) for launches whose outputs are small: what a kernel leaves dirty in the XCDs' L2s is written
+// back at its end, serial with the next launch.  Outputs up to these many megabytes (MI355X sweeps, profiles/r03_experiments.md)
+constexpr double kWtMB = 64.0;
+int write_through(double out_mb) { return out_mb <= kWtMB ? 1 : 0; }
+
+// early emission (ctd_layout.hpp KParams::pos): direct tiles of the Gauss-Legendre schemes, when the lead wave can hold one
+// lane per early output of a step and the late positions fit the workgroup.  OFF by default (CTD_EARLY=1 switches it on):
+// measured on MI355X it LOSES -- Goddard GL2 N = 10 000: 8.4 us against 6.2, GL3 optimized pattern 28.8 against 20.1
+// (profiles/r03_experiments.md) -- the early and the late stores each write PARTS of the same 128-byte lines (the state
+// rows and the stage rows of one CSC column interleave), and two partial-line writes cost more than the overlap gains
+bool early_emission_fits(const Model& mo, int tile, int block) {
+    const int S = mo.L.s, r_dyn = S * mo.nch_dyn, r_path = mo.nch_path;
+    int lgT = 0;
+    while ((1 << lgT) < tile) ++lgT;
+    const int leadbase = (((r_dyn + r_path) << lgT) + 63) & ~63;
+    const int early_lanes = mo.n_early + mo.c_early + mo.L.nv * mo.vr_early;
+    return mo.n_early > 0 && mo.fused && tile <= 32 && leadbase + 64 <= block && early_lanes <= 64 && mo.n_late > 0 && mo.n_late <= block;
+}
+void set_early_emission(const Model& mo, KParams& kp) {
+    kp.n_late = mo.n_late; kp.n_early = mo.n_early; kp.c_early = mo.c_early; kp.vr_early = mo.vr_early;
+    kp.div_late = make_fastdiv((uint32_t)mo.n_late);
+}
+
+int plan_cons_jac(const Model& mo, int64_t step_begin, int64_t step_end, const PlanKnobs& knobs, const Resident& resident, int cus,
+                  bool multi_tile_loop, LaunchPlan& pl, std::string& err) {
+    const int64_t ns = step_end - step_begin;
+    const RtOcp* rt = runtime_ocp(mo.problem);
+    int maxb = 256;
+    for_problem(mo.problem, [&](auto tag) { maxb = decltype(tag)::type::MAXB; });
+    if (rt) maxb = rt->maxb;
+    // the kernel arguments and the LDS bytes of a tile size
+    auto tile_params = [&](int tile, KParams& kp) {
+        mo.fill_kparams(kp, step_begin, step_end, tile);
+        return (size_t)lds_doubles(kp) * sizeof(double);
+    };
+    auto use_tile = [&](int tile) { pl.tile = tile; pl.lds_bytes = tile_params(tile, pl.kp); };
+    pl.lean_ok = knobs.lean ? 1 : 0;
+    // bit 1: the static-emit form of the lean kernel (launch_variant) -- registry OCPs, manual pattern in CSC order, the whole grid
+    if (pl.lean_ok && knobs.static_emit && !rt && mo.pattern_mode == 0 && mo.order == 0 && step_begin == 0 && step_end == mo.L.N)
+        pl.lean_ok |= 2;
+    pl.tile = knobs.tile > 0 ? knobs.tile : default_tile(mo, ns);
+    pl.block = knobs.block;
+    if (pl.block <= 0) {
+        // 256 lanes, or 320 on small grids (everything resident at once) when a fifth wave lets the emit phase hold one more
+        // replica of the CSC period: 10 000-step Goddard / GL2, period 102: 3 x 102 = 306 of 320 lanes, 7.5 us vs 7.8 us
+        pl.block = 256;
+        const int64_t ntl = (ns + pl.tile - 1) / pl.tile;
+        // (not for the wide OCPs: their kernels keep fewer workgroups resident with five waves each -- 8-state quadrotor, 2 controls per
+        // step, optimized pattern, 40-step tiles: 501 workgroups no longer start together, 14.4 us against 8.8)
+        if (ntl <= 512 && mo.nch_dyn <= 1 && mo.Lseg > 0 && 320 / mo.Lseg > 256 / mo.Lseg && mo.Lseg * (320 / mo.Lseg) * 10 >= 320 * 9) pl.block = 320;
+        // (a fifth wave for the symbolic path rows of the wide OCPs was measured slower -- quadrotor12 midpoint N = 20 000 30.1 us
+        // against 24.4 -- and is gone: profiles/r03_experiments.md)
+    }
+    if (pl.block < 64 || (pl.block % 64)) pl.block = 256;
+    if (pl.block > maxb) pl.block = maxb;
+    use_tile(pl.tile);
+    const size_t lds_cap = rt ? 64 * 1024 : 80 * 1024;   // module-API kernels stay inside the default 64 KiB of dynamic LDS
+    while (pl.lds_bytes > lds_cap && pl.tile > 1)        // a requested tile that does not fit (2 workgroups / CU) is shrunk, not rejected
+        use_tile((pl.tile + 1) / 2);
+    // Gauss-Legendre schemes of the narrow OCPs on long grids: the kernel keeps R workgroups per CU resident (R from the runtime:
+    // registers and LDS of the instantiation), a round of 256 R tiles, and its time follows rounds x steps per tile -- Goddard GL3,
+    // N = 80 000 at the 32 steps of default_tile: 2501 tiles = 2.44 rounds of 1024, the workgroups start in three waves
+    // (profiles/r03_phase_stamps_final.log: start percentiles 0.1 / 10.1 / 19.3 us).  A tile of up to 48 steps with the same R fixes
+    // the number of rounds, the steps are spread evenly over them: 40 steps = 2001 tiles, 28.3 -> 26.9 us, optimized pattern
+    // 20.3 -> 17.9; N = 200 000: 79.9 -> 74.3 (profiles/r03_experiments.md).  Only ever a LARGER tile than the rule's.
+    const bool long_mid = mo.L.sc == SC_MIDPOINT && mo.L.cs == 1;      // midpoint and both Euler schemes (one point per step): long-grid rule only
+    if (resident && !rt && knobs.tile <= 0 && mo.nch_dyn <= 1 && (mo.L.sc == SC_IRK || long_mid) && pl.tile >= 16) {
+        auto resident_at = [&](int tile, size_t& lds) {
+            KParams kq;
+            lds = tile_params(tile, kq);
+            return resident(kq, pl.block, lds);
+        };
+        size_t l0 = 0;
+        const int r0 = resident_at(pl.tile, l0);
+        const int64_t cap = 256 * (int64_t)r0;
+        // VERY long grids (8 rounds of resident workgroups and more: from ~half a million steps; crossover measured in
+        // profiles/r04_long_grid_crossover.log: 2^18 steps +-5 % either way, 2^19 +3 .. +15 %, 2^20 +5 .. +18 %) are bandwidth-bound, the rounds no
+        // longer quantise anything, and what is left per tile is its fixed cost -- launch slot, argument pinning, time table,
+        // prologue latency.  Eight waves per workgroup and the largest tile whose records fit 64 KiB of LDS (two workgroups
+        // per CU) amortise it: Goddard GL2, 4 194 304 steps 930 -> 795 us (0.59 -> 0.69 of 8 TB/s), GL3 1333 -> 1297,
+        // double integrator + path GL2 508 -> 460, double integrator free t0 / tf GL3 915 -> 800, goddard_all GL2 (2 M steps,
+        // staged driver) 598 -> 556; the midpoint scheme (records up to 74 KiB): double integrator + path, 8 M steps 506 -> 421, Goddard 4 M 350 -> 283, explicit / implicit Euler 335 -> 288 / 294, DI + path Euler 8 M 455 -> 367;
+        // trapeze: flat, left alone (profiles/r04_tiles_long_grids.log; CTD_LONG_GRID=0: off; CTD_LONG_GRID_ROUNDS: the threshold, for tests)
+        if (r0 > 0 && (ns + pl.tile - 1) / pl.tile >= knobs.long_grid_rounds * cap && maxb >= 512 && knobs.block <= 0 && knobs.long_grid) {
+            int tbest = pl.tile;
+            for (int tt = pl.tile + 1; tt <= 256; ++tt) {
+                KParams kq;
+                if (tile_params(tt, kq) > (long_mid ? 74u : 64u) * 1024) break;
+                tbest = tt;
+            }
+            if (tbest > pl.tile) {
+                pl.block = 512;
+                use_tile(tbest);
+            }
+        } else if (mo.L.sc == SC_IRK && r0 > 0 && (ns + pl.tile - 1) / pl.tile > cap) {
+            int tmax = 48;
+            for (; tmax > pl.tile; --tmax) { size_t l = 0; if (resident_at(tmax, l) >= r0 && l <= lds_cap) break; }
+            const int64_t rounds = (ns + (int64_t)tmax * cap - 1) / ((int64_t)tmax * cap);
+            const int64_t tb = (ns + rounds * cap - 1) / (rounds * cap);
+            if (tb > pl.tile && tb <= tmax) use_tile((int)tb);
+        }
+    }
+    pl.grid = pl.kp.ntiles + pl.kp.has_edge;
+    pl.kp.debug_stop = knobs.debug_stop;
+    pl.out_mb = 8.0 * ((double)ns * (mo.L.cb + mo.Lseg + (double)mo.L.nv * mo.vr)) / 1.0e6;
+    pl.kp.wt_store = knobs.wt_store >= 0 ? (knobs.wt_store ? 1 : 0) : write_through(pl.out_mb);      // (tests: either store flavour on any grid)
+    if (resident && pl.lds_bytes > 160 * 1024) { err = "ctd_create: tile does not fit the 160 KiB LDS"; return ST_EINVAL; }
+    if (resident && rt && pl.lds_bytes > 64 * 1024) { err = "ctd_create: one step of this run-time OCP does not fit 64 KiB of LDS"; return ST_EINVAL; }
+    pl.early = knobs.early && !rt && early_emission_fits(mo, pl.tile, pl.block);
+    if (pl.early) set_early_emission(mo, pl.kp);
+    // Multi-tile workgroups (staged driver only; KParams::wg_stride): when the tiles need several rounds of resident
+    // workgroups, launch ONE round and let every workgroup walk its share of the tiles -- templates / v / codes fetched once
+    // per workgroup, the next tile's x slice in flight during the emission.  The round is what the runtime says is resident
+    // (registers and LDS of this very kernel).  EXPERIMENT: builds with -DCTD_MULTI_TILE_LOOP=1 and CTD_MULTI_TILE=1 (k > 1: k
+    // workgroups per CU) only -- measured slower than the hardware's own dispatch of one tile per workgroup (ctd_kernels.hpp).
+    const bool direct = mo.fused && mo.L.sc != SC_TRAPEZE;
+    if (resident && !direct && knobs.multi_tile > 0 && multi_tile_loop && !rt) {
+        const int per_cu = knobs.multi_tile > 1 ? knobs.multi_tile : resident(pl.kp, pl.block, pl.lds_bytes);
+        const int64_t cap = (int64_t)per_cu * cus - pl.kp.has_edge;      // (the edge blocks hold slots of their own)
+        if (cap > 0 && pl.kp.ntiles > cap) {
+            pl.kp.wg_stride = (int)cap;
+            pl.grid = pl.kp.wg_stride + pl.kp.has_edge;
+        }
+    }
+    return ST_OK;
+}
+
 int build_model(const HostDesc& d, Model& mo, std::string& err) {
     mo.problem = d.problem;
     mo.pattern_mode = d.pattern_mode;

@@ -3,6 +3,7 @@
 // (get_docp, src/collocation.jl:57-73).
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -159,5 +160,34 @@ struct InitSamples { int64_t n = 0; const double* t = nullptr; const double* sta
 void model_initial_guess(const Model& m, double* x0, bool use_problem_default, const double* state, const double* control,
                          const double* variable, const InitSamples& samples = InitSamples{});
 int default_tile(const Model& m, int64_t nsteps = 0);
+
+// ---- launch plan of the constraint / Jacobian kernel -------------------------------------------------------------------
+// The CTD_* knobs of the plan, as plan_knobs_from_env reads them -- once per plan.  tile, block: > 0 pins the value (a pinned tile
+// switches both device rules off, a pinned block the long-grid rule, which sets its own); wt_store: -1 = by the rule, 0 / 1 = that store flavour on any grid (tests)
+struct PlanKnobs {
+    int tile = 0, block = 0, lean = 1, static_emit = 1, long_grid = 1, long_grid_rounds = 8, wt_store = -1, early = 0, multi_tile = 0,
+        debug_stop = 0;
+};
+PlanKnobs plan_knobs_from_env();
+// Workgroups of `block` lanes and `lds_bytes` of LDS that one CU keeps resident, 0: unknown.  Empty: a host-only handle, which
+// gets everything of the plan but the device rules and the device limits
+using Resident = std::function<int(const KParams& kp, int block, size_t lds_bytes)>;
+struct LaunchPlan {
+    int tile = 0, block = 256, grid = 0;
+    int lean_ok = 1;            // bit 0: the lean variant of the kernel may be launched, bit 1: its static-emit form (launch_variant)
+    size_t lds_bytes = 0;
+    double out_mb = 0.0;        // megabytes of constraint / Jacobian outputs of one evaluation (write_through)
+    KParams kp;                 // host fields; the device pointers are the handle's to fill in
+    bool early = false;         // early emission is on: kp.pos wants the device copy of Model::pos_order
+};
+int write_through(double out_mb);      // KParams::wt_store of a launch that writes out_mb megabytes (all members of a batched one)
+// The early-emission geometry (ctd_layout.hpp KParams::pos) fits tiles of `tile` steps in workgroups of `block` lanes
+bool early_emission_fits(const Model& m, int tile, int block);
+void set_early_emission(const Model& m, KParams& kp);      // (all of it but kp.pos)
+// Tile, workgroup, grid and kernel form for the steps [step_begin, step_end) of the model.  cus: the device's compute units and
+// multi_tile_loop: the kernels were built with the multi-tile loop (kMultiTileLoop) -- the multi-tile experiment only.
+// Status codes as build_model
+int plan_cons_jac(const Model& m, int64_t step_begin, int64_t step_end, const PlanKnobs& knobs, const Resident& resident, int cus,
+                  bool multi_tile_loop, LaunchPlan& plan, std::string& err);
 
 }  // namespace ctd

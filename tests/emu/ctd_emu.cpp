@@ -104,6 +104,38 @@ static std::string g_err;
 static int g_control_steps = 1;          // DOCP(..., control_steps, ...) of the models built below (tests set it around a call)
 static int g_value_order = 0;            // ctd_desc.value_order of the models built below (0 CSC, 1 CSR)
 
+static int env_int(const char* name, int dflt) {
+    const char* s = std::getenv(name);
+    return (s && *s) ? std::atoi(s) : dflt;
+}
+
+// The kernel arguments of an emulated launch over the steps [step_begin, step_end) with nthr lanes per workgroup, the tables read
+// from the model.  tile <= 0: the tile of the engine's host-only launch plan (plan_cons_jac without a residency).
+// CTD_EMU_WG_STRIDE: multi-tile workgroups; CTD_EMU_EARLY=1: early emission, where the engine's own predicate lets it on
+static KParams emu_kparams(const Model& mo, int64_t step_begin, int64_t step_end, int tile, int nthr, double* c, double* vals) {
+    if (tile <= 0) {
+        LaunchPlan pl;
+        std::string err;
+        (void)plan_cons_jac(mo, step_begin, step_end, plan_knobs_from_env(), Resident{}, 256, false, pl, err);      // (host-only: no limit to miss)
+        tile = pl.tile;
+    }
+    KParams kp;
+    mo.fill_kparams(kp, step_begin, step_end, tile);
+    kp.wg_stride = env_int("CTD_EMU_WG_STRIDE", 0);
+    kp.tau = mo.uniform ? nullptr : mo.tau.data();
+    kp.tmpl = mo.tmpl.data();
+    kp.vtmpl = mo.vtmpl.data();
+    kp.edge_idx = mo.edge_idx.data();
+    kp.edge_code = mo.edge_code.data();
+    kp.c = c;
+    kp.vals = vals;
+    if (env_int("CTD_EMU_EARLY", 0) && early_emission_fits(mo, tile, nthr)) {
+        set_early_emission(mo, kp);
+        kp.pos = mo.pos_order.data();
+    }
+    return kp;
+}
+
 extern "C" {
 
 void emu_set_control_steps(int cs) { g_control_steps = cs < 1 ? 1 : cs; }
@@ -178,28 +210,7 @@ int emu_cons_jac(int problem, int scheme, int pattern_mode, int64_t N, const dou
     int st = build_model(d, mo, g_err);
     if (st) return st;
     if (step_end <= 0) { step_begin = 0; step_end = mo.L.N; }
-    if (tile <= 0) tile = default_tile(mo);
-    KParams kp;
-    mo.fill_kparams(kp, step_begin, step_end, tile);
-    if (const char* e = std::getenv("CTD_EMU_WG_STRIDE")) kp.wg_stride = std::atoi(e);      // multi-tile workgroups
-    kp.tau = mo.uniform ? nullptr : mo.tau.data();
-    kp.tmpl = mo.tmpl.data();
-    kp.vtmpl = mo.vtmpl.data();
-    kp.edge_idx = mo.edge_idx.data();
-    kp.edge_code = mo.edge_code.data();
-    kp.c = c;
-    kp.vals = vals;
-    // early emission as ctd_create switches it on (CTD_EMU_EARLY=1; the same conditions on the launch geometry)
-    if (std::getenv("CTD_EMU_EARLY") && std::atoi(std::getenv("CTD_EMU_EARLY")) && mo.n_early > 0 && mo.fused && tile <= 32) {
-        int lgT = 0;
-        while ((1 << lgT) < tile) ++lgT;
-        const int leadbase = ((((mo.L.s * mo.nch_dyn + mo.nch_path) << lgT)) + 63) & ~63;
-        if (leadbase + 64 <= nthr && mo.n_early + mo.c_early + mo.L.nv * mo.vr_early <= 64 && mo.n_late > 0 && mo.n_late <= nthr) {
-            kp.pos = mo.pos_order.data();
-            kp.n_late = mo.n_late; kp.n_early = mo.n_early; kp.c_early = mo.c_early; kp.vr_early = mo.vr_early;
-            kp.div_late = make_fastdiv((uint32_t)mo.n_late);
-        }
-    }
+    const KParams kp = emu_kparams(mo, step_begin, step_end, tile, nthr, c, vals);
     bool ok = for_problem(problem, [&](auto tag) {
         using P = typename decltype(tag)::type;
         switch (mo.L.sc) {
@@ -230,7 +241,6 @@ int emu_cons_jac_sharded(int problem, int scheme, int pattern_mode, int64_t N, c
     if (st) return st;
     const Layout& L = mo.L;
     if (G < 1 || G > kMaxShards || G > L.N) { g_err = "bad shard count"; return 97; }
-    if (tile <= 0) tile = default_tile(mo);
     std::vector<int64_t> sb(G + 1);
     const int64_t base = L.N / G, rem = L.N % G;
     for (int k = 0; k <= G; ++k) sb[k] = k * base + (k < rem ? k : rem);
@@ -245,16 +255,7 @@ int emu_cons_jac_sharded(int problem, int scheme, int pattern_mode, int64_t N, c
         hl.G = G; hl.self = k;
         for (int j = 0; j < G; ++j) { hl.vbegin[j] = sb[j] * L.blk; hl.x[j] = j == k ? nullptr : xs[j].data(); }
         hl.vbegin[G] = L.v_off;
-        KParams kp;
-        mo.fill_kparams(kp, sb[k], sb[k + 1], tile);
-        if (const char* e = std::getenv("CTD_EMU_WG_STRIDE")) kp.wg_stride = std::atoi(e);
-        kp.tau = mo.uniform ? nullptr : mo.tau.data();
-        kp.tmpl = mo.tmpl.data();
-        kp.vtmpl = mo.vtmpl.data();
-        kp.edge_idx = mo.edge_idx.data();
-        kp.edge_code = mo.edge_code.data();
-        kp.c = c;
-        kp.vals = vals;
+        KParams kp = emu_kparams(mo, sb[k], sb[k + 1], tile, nthr, c, vals);
         kp.halo = &hl;
         kp.near = make_xnear(hl, L.blk, L.N, L.v_off);
         const double* xk = xs[k].data();
@@ -277,6 +278,35 @@ int emu_cons_jac_sharded(int problem, int scheme, int pattern_mode, int64_t N, c
         if (!ok) return 5;
     }
     return 0;
+}
+
+// The engine's launch plan (plan_cons_jac) of the steps [step_begin, step_end) -- 0, 0: the whole grid -- with the knobs given
+// (knobs[0..9]: the fields of PlanKnobs in their order), on a device of `cus` compute units that keeps `resident` workgroups per CU
+// whatever the tile (0: the query failed, < 0: a host-only handle).  out[0..9] = tile, block, grid, lds_bytes, lean_ok, wt_store,
+// has_edge, ntiles, wg_stride, early
+int emu_plan(int problem, int scheme, int pattern_mode, int64_t N, const double* tg, int64_t tglen, int64_t step_begin, int64_t step_end,
+             const int* knobs, int resident, int cus, int multi_tile_loop, int64_t* out) {
+    Model mo;
+    HostDesc d{problem, scheme, pattern_mode, N, tg, tglen, g_control_steps, g_value_order};
+    int st = build_model(d, mo, g_err);
+    if (st) return st;
+    if (step_end <= 0) { step_begin = 0; step_end = mo.L.N; }
+    const int* k = knobs;
+    const PlanKnobs kn{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9]};
+    Resident res;
+    if (resident >= 0) res = [resident](const KParams&, int, size_t) { return resident; };
+    LaunchPlan pl;
+    st = plan_cons_jac(mo, step_begin, step_end, kn, res, cus, multi_tile_loop != 0, pl, g_err);
+    if (st) return st;
+    const int64_t o[10] = {pl.tile, pl.block, pl.grid, (int64_t)pl.lds_bytes, pl.lean_ok, pl.kp.wt_store, pl.kp.has_edge, pl.kp.ntiles, pl.kp.wg_stride, pl.early};
+    std::memcpy(out, o, sizeof(o));
+    return 0;
+}
+// knobs[0..9] = the defaults of PlanKnobs, or what the environment sets (plan_knobs_from_env)
+void emu_plan_knobs(int from_env, int* knobs) {
+    const PlanKnobs kn = from_env ? plan_knobs_from_env() : PlanKnobs{};
+    const int o[10] = {kn.tile, kn.block, kn.lean, kn.static_emit, kn.long_grid, kn.long_grid_rounds, kn.wt_store, kn.early, kn.multi_tile, kn.debug_stop};
+    std::memcpy(knobs, o, sizeof(o));
 }
 
 // index map of ctd_stitch_c's unpack kernel (ctd_layout.hpp stitch_src): out[r] = position of global row r in the gathered blocks
@@ -408,16 +438,7 @@ int emu_user_cons_jac(int problem, int scheme, int pattern_mode, int64_t N, int 
     if (st) return st;
     if (sizes) { sizes[0] = mo.L.nvar; sizes[1] = mo.L.ncon; sizes[2] = mo.nnzj; }
     if (!x) return 0;
-    if (tile <= 0) tile = default_tile(mo);
-    KParams kp;
-    mo.fill_kparams(kp, 0, mo.L.N, tile);
-    kp.tau = mo.uniform ? nullptr : mo.tau.data();
-    kp.tmpl = mo.tmpl.data();
-    kp.vtmpl = mo.vtmpl.data();
-    kp.edge_idx = mo.edge_idx.data();
-    kp.edge_code = mo.edge_code.data();
-    kp.c = c;
-    kp.vals = vals;
+    const KParams kp = emu_kparams(mo, 0, mo.L.N, tile, nthr, c, vals);
     using P = UserOCP;
     switch (mo.L.sc) {
         case SC_TRAPEZE: run_blocks<P, SC_TRAPEZE, 1>(kp, x, nthr); break;

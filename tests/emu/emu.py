@@ -114,6 +114,35 @@ def cons_jac_sharded(problem, scheme, mode, N, x, G, time_grid=None, tile=0, nth
     return c, vals
 
 
+_KNOBS = ("tile", "block", "lean", "static_emit", "long_grid", "long_grid_rounds", "wt_store", "early", "multi_tile", "debug_stop")
+_PLAN = ("tile", "block", "grid", "lds_bytes", "lean_ok", "wt_store", "has_edge", "ntiles", "wg_stride", "early")
+
+
+def plan_knobs(from_env=False):
+    """The knobs of the launch plan (PlanKnobs, ctd_host.hpp): their defaults, or what the CTD_* environment sets"""
+    k = np.zeros(len(_KNOBS), dtype=np.int32)
+    lib().emu_plan_knobs(int(from_env), k.ctypes.data_as(C.c_void_p))
+    return dict(zip(_KNOBS, (int(v) for v in k)))
+
+
+def plan(problem, scheme, mode, N, resident=-1, cus=256, step_begin=0, step_end=0, time_grid=None, multi_tile_loop=False, **knobs):
+    """The engine's launch plan of the constraint / Jacobian kernel (plan_cons_jac) as a dict of _PLAN, on a device of `cus`
+    compute units that keeps `resident` workgroups per CU whatever the tile (0: the query failed; negative: a host-only handle).
+    knobs: fields of PlanKnobs other than their defaults -- the environment is not read"""
+    tg, n = _tg(time_grid)
+    k = plan_knobs()
+    assert set(knobs) <= set(k), knobs
+    k.update(knobs)
+    ka = np.array([k[name] for name in _KNOBS], dtype=np.int32)
+    out = np.zeros(len(_PLAN), dtype=np.int64)
+    st = lib().emu_plan(problem, scheme, mode, C.c_int64(N or 0), tg.ctypes.data_as(C.c_void_p) if tg is not None else None, C.c_int64(n),
+                        C.c_int64(step_begin), C.c_int64(step_end), ka.ctypes.data_as(C.c_void_p), int(resident), int(cus),
+                        int(multi_tile_loop), out.ctypes.data_as(C.c_void_p))
+    if st:
+        raise RuntimeError(f"emu status {st}: {lib().emu_last_error().decode()}")
+    return dict(zip(_PLAN, (int(v) for v in out)))
+
+
 def hess_csc(problem, scheme, mode, N, time_grid=None):
     nvar = sizes(problem, scheme, mode, N, time_grid)[0]
     tg, n = _tg(time_grid)

@@ -64,7 +64,12 @@ int se_cons_jac(int problem, int scheme, int64_t N, const double* tg, int64_t tg
     HostDesc d{problem, scheme, 0, N, tg, tglen, control_steps < 1 ? 1 : control_steps, 0};
     int st = build_model(d, mo, g_err);
     if (st) return st;
-    if (tile <= 0) tile = default_tile(mo);
+    if (tile <= 0) {      // the tile of the engine's host-only launch plan
+        LaunchPlan pl;
+        std::string err;
+        (void)plan_cons_jac(mo, 0, mo.L.N, plan_knobs_from_env(), Resident{}, 256, false, pl, err);
+        tile = pl.tile;
+    }
     KParams kp;
     mo.fill_kparams(kp, 0, mo.L.N, tile);
     kp.tau = mo.uniform ? nullptr : mo.tau.data();

@@ -221,7 +221,7 @@ def test_early_emission_knob_stays_bit_identical(monkeypatch):
                                            ("goddard", "midpoint", 199), ("goddard_all", "gauss_legendre_2", 85), ("goddard", "euler_implicit", 199),
                                            ("double_integrator_freet0tf", "gauss_legendre_3", 112)])
 def test_emulated_long_grid_geometry(prob, sch, tile):
-    """The launch geometry `ctd_create` takes on grids of 8 rounds of resident workgroups and more (round 4: eight waves per workgroup, the
+    """The launch geometry `plan_cons_jac` takes on grids of 8 rounds of resident workgroups and more (round 4: eight waves per workgroup, the
     largest tile whose records fit 64 / 74 KiB -- the tile sizes of profiles/r04_tiles_long_grids.log), here in the serial emulator of the
     same phase templates: 512 lanes, 84 - 254 steps per tile, a grid of several tiles with a ragged last one, both value orders, against
     the oracle (GPU: tests/test_gpu_max_sizes.py)."""
