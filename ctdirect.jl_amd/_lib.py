@@ -53,6 +53,16 @@ class ctd_minres_info(C.Structure):
                 ("Anorm", C.c_double), ("ynorm", C.c_double), ("beta1", C.c_double)]
 
 
+# CTD_KKT_MINRES_SHARD_SLOT and the layout query of the shard form of the solve (ctd_kkt_minres_shard_layout)
+KKT_MINRES_SHARD_SLOT = 2080
+
+
+class ctd_minres_shard_layout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(nm, C.c_int64) for nm in (
+        "n", "n_ranks", "var_begin", "var_end", "tail_begin", "tail_end", "row_begin", "row_end", "n_own", "n_dot", "nwg", "chunk",
+        "slot", "off_v", "off_kv", "off_send_a", "off_send_b", "off_gathered_a", "off_gathered_b", "off_state", "workspace")]
+
+
 # every symbol include/ctdirect_hip.h declares: name -> (restype, argtypes)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -136,6 +146,15 @@ SYMBOLS = {
                                        C.POINTER(ctd_minres_info)]),
     "ctd_kkt_minres": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _dp, _dp, C.c_double, C.c_int64, C.c_int64,
                                    C.POINTER(ctd_minres_info)]),
+    # ... and its shard form: the phases between the caller's all-gathers
+    "ctd_kkt_minres_shard_layout": (C.c_int32, [_vp, C.c_int32, C.POINTER(ctd_minres_shard_layout)]),
+    "ctd_kkt_minres_shard_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double,
+                                                         C.c_int64]),
+    "ctd_kkt_minres_shard_begin_dev_async": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_shard_alfa_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_shard_lanczos_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_shard_update_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_shard_info": (C.c_int32, [_vp, _vp, C.c_int32, C.POINTER(ctd_minres_info)]),
     "ctd_jprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

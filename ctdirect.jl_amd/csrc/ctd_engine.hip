@@ -28,6 +28,7 @@
 #include "ctd_kkt_kernels.hpp"
 #include "ctd_diag_kernels.hpp"
 #include "ctd_krylov_kernels.hpp"
+#include "ctd_krylov_shard_kernels.hpp"
 #include "ctd_jit.hpp"
 
 using namespace ctd;
@@ -1667,6 +1668,155 @@ int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* r
                          return mr_drive(h, c, dev, h->d_mrrhs.p, h->d_mrz.p, rtol, max_iter, check_every, info);
                      },
                      {{z, h->d_mrz, n}});
+}
+
+// ---- the solve on a shard of the grid (ownership, slots and summation order: ctd_krylov_shard_kernels.hpp) ------------------------
+// The phases between which the caller exchanges the send slots: one launch each, no collective, no per-solve state in the handle.
+static_assert(kKrylovSlot == CTD_KKT_MINRES_SHARD_SLOT, "the slot length of the header");
+static_assert(kMaxNV <= kKrylovTailMax, "the nv tail entries fit a slot");
+static void mrs_geom(int64_t n, int32_t* nwg, int64_t* chunk) {
+    const KrylovGeom g = krylov_geom(n);
+    *nwg = g.nwg;
+    *chunk = g.chunk;
+}
+static KrylovShardPlan mrs_plan(const ctd_handle* h) { return plan_krylov_shard(h->model.L, h->step_begin, h->step_end, mrs_geom); }
+
+// n_ranks, rank and the handle's steps: the steps must be able to be block `rank` of n_ranks ascending blocks of the grid
+static int32_t mrs_check_rank(ctd_handle* h, const char* fn, int32_t n_ranks, int32_t rank, bool with_rank) {
+    const int64_t N = h->model.L.N, sb = h->step_begin, se = h->step_end;
+    if (n_ranks < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": n_ranks = " + std::to_string(n_ranks) + ", must be at least 1");
+    if (n_ranks > N)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": n_ranks = " + std::to_string(n_ranks) + " exceeds the " + std::to_string(N) + " steps of the grid");
+    if (!with_rank) return CTD_OK;
+    if (rank < 0 || rank >= n_ranks)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": rank = " + std::to_string(rank) + " is outside [0, n_ranks = " + std::to_string(n_ranks) + ")");
+    if ((rank == 0) != (sb == 0) || (rank == n_ranks - 1) != (se == N) || sb < rank || N - se < n_ranks - 1 - rank)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the handle's steps [" + std::to_string(sb) + ", " + std::to_string(se) + ") of " +
+                                       std::to_string(N) + " cannot be block rank = " + std::to_string(rank) + " of n_ranks = " +
+                                       std::to_string(n_ranks) + " ascending blocks of the grid");
+    return CTD_OK;
+}
+static int32_t mrs_check_ptr(ctd_handle* h, const char* fn, const char* name, const void* p) {
+    if (!p) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (" + name + " is required)");
+    if ((uintptr_t)p % sizeof(double)) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " is not aligned to 8 bytes");
+    return CTD_OK;
+}
+// [a, a + na) and [b, b + nb) share an entry (null: no range)
+static bool mrs_overlap(const double* a, int64_t na, const double* b, int64_t nb) { return a && b && a < b + nb && b < a + na; }
+// z (n entries) and the workspace (CTD_KKT_MINRES_SHARD_WORKSPACE(n, n_ranks) doubles) as ranges: they must be disjoint
+static int32_t mrs_check_disjoint(ctd_handle* h, const char* fn, const double* z, const double* ws, int32_t n_ranks) {
+    const int64_t n = h->model.L.nvar + h->model.L.ncon;
+    if (mrs_overlap(z, n, ws, krylov_shard_workspace(n, n_ranks)))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
+    return CTD_OK;
+}
+static KrylovShardParams mrs_params(const ctd_handle* h, double* ws, double* z, int32_t n_ranks) {
+    const KrylovShardPlan pl = mrs_plan(h);
+    const KrylovOwn own{pl.var_lo, pl.var_hi - pl.var_lo, pl.tail_lo, pl.tail_hi - pl.tail_lo, pl.row_lo, pl.last, n_ranks};
+    return krylov_shard_params(ws, pl.n, pl.n_own, own, z);
+}
+static int32_t mrs_launched(ctd_handle* h, const char* fn, hipError_t e) {
+    return e == hipSuccess ? CTD_OK : fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+}
+
+int32_t ctd_kkt_minres_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out) {
+    const char* fn = "ctd_kkt_minres_shard_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_minres_shard_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_minres_shard_layout) = " +
+                                       std::to_string(sizeof(ctd_minres_shard_layout)));
+    if (const int32_t st = mrs_check_rank(h, fn, n_ranks, 0, false)) return st;
+    const KrylovShardPlan pl = mrs_plan(h);
+    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks);
+    out->reserved = 0;
+    out->n = pl.n; out->n_ranks = n_ranks;
+    out->var_begin = pl.var_lo; out->var_end = pl.var_hi;
+    out->tail_begin = pl.tail_lo; out->tail_end = pl.tail_hi;
+    out->row_begin = pl.row_lo; out->row_end = pl.row_hi;
+    out->n_own = pl.n_own; out->n_dot = pl.n_dot; out->nwg = pl.nwg; out->chunk = pl.chunk;
+    out->slot = kKrylovSlot;
+    out->off_v = l.v; out->off_kv = l.kv;
+    out->off_send_a = l.send_a; out->off_send_b = l.send_b;
+    out->off_gathered_a = l.gathered_a; out->off_gathered_b = l.gathered_b;
+    out->off_state = l.pend;
+    out->workspace = krylov_shard_workspace(pl.n, n_ranks);
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_minres_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev,
+                                             double* ws_dev, int32_t n_ranks, int32_t rank, double rtol, int64_t max_iter) {
+    const char* fn = "ctd_kkt_minres_shard_start_dev_async";
+    int32_t st;
+    if (!mr_structs_ok(h, fn, sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
+    if ((st = mrs_check_ptr(h, fn, "rhs", rhs_dev)) || (st = mrs_check_ptr(h, fn, "z", z_dev)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev)))
+        return st;
+    if (!sys->px != !sys->pc)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": px and pc are given both (M = diag(1 / px, 1 / pc)) or neither (no preconditioner)");
+    if (sys->px && ((st = mrs_check_ptr(h, fn, "px", sys->px)) || (st = mrs_check_ptr(h, fn, "pc", sys->pc)))) return st;
+    {   // the inputs as ranges against the two output ranges, then the outputs against each other
+        const Layout& L = h->model.L;
+        const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks);
+        const std::pair<const double*, int64_t> ins[] = {{rhs_dev, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
+        for (const auto& in : ins)
+            if (mrs_overlap(in.first, in.second, z_dev, n) || mrs_overlap(in.first, in.second, ws_dev, wlen))
+                return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (z and ws) must not overlap an input buffer");
+    }
+    if ((st = mrs_check_disjoint(h, fn, z_dev, ws_dev, n_ranks))) return st;
+    if (!(rtol >= 0.0)) return fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
+    if (max_iter < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": max_iter = " + std::to_string(max_iter) + ", must be at least 1");
+    return mrs_launched(h, fn, krylov_shard_start(mrs_params(h, ws_dev, z_dev, n_ranks), rhs_dev, sys->px, sys->pc, h->model.L.nvar, rtol,
+                                                  max_iter, h->stream));
+}
+
+// the prologue of begin and of the phases: z may be absent (begin)
+static int32_t mrs_phase(ctd_handle* h, const char* fn, double* z_dev, bool with_z, double* ws_dev, int32_t n_ranks, int32_t rank,
+                         hipError_t (*launch)(const KrylovShardParams&, hipStream_t)) {
+    if (!h) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
+    if (with_z && (st = mrs_check_ptr(h, fn, "z", z_dev))) return st;
+    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    if (with_z && (st = mrs_check_disjoint(h, fn, z_dev, ws_dev, n_ranks))) return st;
+    return mrs_launched(h, fn, launch(mrs_params(h, ws_dev, z_dev, n_ranks), h->stream));
+}
+int32_t ctd_kkt_minres_shard_begin_dev_async(ctd_handle* h, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    return mrs_phase(h, "ctd_kkt_minres_shard_begin_dev_async", nullptr, false, ws_dev, n_ranks, rank, krylov_shard_begin);
+}
+int32_t ctd_kkt_minres_shard_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    return mrs_phase(h, "ctd_kkt_minres_shard_alfa_dev_async", z_dev, true, ws_dev, n_ranks, rank, krylov_shard_alfa);
+}
+int32_t ctd_kkt_minres_shard_lanczos_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    return mrs_phase(h, "ctd_kkt_minres_shard_lanczos_dev_async", z_dev, true, ws_dev, n_ranks, rank, krylov_shard_lanczos);
+}
+int32_t ctd_kkt_minres_shard_update_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    return mrs_phase(h, "ctd_kkt_minres_shard_update_dev_async", z_dev, true, ws_dev, n_ranks, rank, krylov_shard_update);
+}
+
+int32_t ctd_kkt_minres_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info) {
+    const char* fn = "ctd_kkt_minres_shard_info";
+    if (!h) return CTD_EINVAL;
+    if (!info || info->struct_size != sizeof(ctd_minres_info))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
+                                       std::to_string(sizeof(ctd_minres_info)));
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, 0, false)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    KrylovState s;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks).pend, sizeof(s), hipMemcpyDeviceToHost));
+    info->status = s.status;
+    info->iterations = s.itn;
+    info->phibar = s.phibar;
+    info->Anorm = s.Anorm;
+    info->ynorm = s.ynorm;
+    info->beta1 = s.beta1;
+    return CTD_OK;
 }
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {

@@ -1256,6 +1256,25 @@ int plan_cons_jac(const Model& mo, int64_t step_begin, int64_t step_end, const P
     return ST_OK;
 }
 
+// The owned entries of a shard's Krylov vectors: the write sets of ctd_kktprod_shard_dev_async (rx: the variables of the shard's
+// steps, the last shard up to v_off, and the nv tail; rc: its rows, the last shard also the tail rows), variables first
+KrylovShardPlan plan_krylov_shard(const Layout& L, int64_t step_begin, int64_t step_end, KrylovGeomRule geom) {
+    KrylovShardPlan pl{};
+    const bool last = step_end == L.N;
+    pl.n = L.nvar + L.ncon;
+    pl.last = last ? 1 : 0;
+    pl.var_lo = step_begin * (int64_t)L.blk;
+    pl.var_hi = last ? L.v_off : step_end * (int64_t)L.blk;
+    pl.tail_lo = L.v_off;
+    pl.tail_hi = L.nvar;
+    pl.row_lo = L.nvar + step_begin * (int64_t)L.cb;
+    pl.row_hi = L.nvar + (last ? L.ncon : step_end * (int64_t)L.cb);
+    pl.n_own = (pl.var_hi - pl.var_lo) + (pl.tail_hi - pl.tail_lo) + (pl.row_hi - pl.row_lo);
+    pl.n_dot = pl.n_own - (last ? 0 : pl.tail_hi - pl.tail_lo);
+    geom(pl.n_own, &pl.nwg, &pl.chunk);
+    return pl;
+}
+
 int build_model(const HostDesc& d, Model& mo, std::string& err) {
     mo.problem = d.problem;
     mo.pattern_mode = d.pattern_mode;

@@ -190,4 +190,17 @@ void set_early_emission(const Model& m, KParams& kp);      // (all of it but kp.
 int plan_cons_jac(const Model& m, int64_t step_begin, int64_t step_end, const PlanKnobs& knobs, const Resident& resident, int cus,
                   bool multi_tile_loop, LaunchPlan& plan, std::string& err);
 
+// ---- ownership and geometry of the shard form of the MINRES vector kernels (ctd_krylov_shard_kernels.hpp) -----------------------------
+// What the shard of the steps [step_begin, step_end) owns of a Krylov vector of n = nvar + ncon entries (variables first), in
+// ascending global index: its variables [var_lo, var_hi), the replicated nv tail [tail_lo, tail_hi) = [v_off, nvar), its rows
+// [row_lo, row_hi) (indices into the n-vector: nvar + the row).  n_own: the entries it updates; n_dot: those it counts in an inner
+// product (the tail on the last shard only).  nwg, chunk: `geom` (krylov_geom) of n_own, applied to the compacted list of owned
+// indices: workgroup b owns the positions [b chunk, (b + 1) chunk) of that list.  The whole grid: the list is 0 .. n - 1.
+struct KrylovShardPlan {
+    int64_t n, var_lo, var_hi, tail_lo, tail_hi, row_lo, row_hi, n_own, n_dot, chunk;
+    int32_t nwg, last;
+};
+using KrylovGeomRule = void (*)(int64_t n, int32_t* nwg, int64_t* chunk);
+KrylovShardPlan plan_krylov_shard(const Layout& L, int64_t step_begin, int64_t step_end, KrylovGeomRule geom);
+
 }  // namespace ctd

@@ -144,6 +144,164 @@ def reduce_hessian_vv(vals, vv_idx, group=None):
     return vals
 
 
+def _shard_dims(d):
+    """The block sizes of a handle's transcription that the halo exchanges are built from: (blk variables per step, cb rows per
+    step, eqs state / stage rows per step, n states, m controls, halo_w = n (+ m on the trapeze: the next node's control too))"""
+    disc = d.discretization
+    eqs = disc._state_stage_eqs_block
+    n, m = d.dims.NLP_x, d.dims.NLP_u
+    return disc._step_variables_block, eqs + disc._step_pathcons_block, eqs, n, m, n + (m if getattr(disc, "_final_control", False) else 0)
+
+
+def _kkt_halo_ranges(b, e, N, n, w, blk, cb, eqs, ncon):
+    """THE read set of ctd_kktprod_shard_dev_async's directions (dx, dy) outside what the shard of the steps [b, e) owns
+    (include/ctdirect_hip.h), stated once for `ShardedDOCP.exchange_kkt_halo` and `minres_shards`: (start, length) ranges of dx owned
+    by lower shards (X_1, the whole block b - 1) and by higher ones (the first node of block e, X_{N+1}), then of dy owned by lower
+    shards (the state / stage rows of step b - 1) and by higher ones (the path rows of node e, the tail rows)."""
+    lo_x = [(0, n), ((b - 1) * blk, blk)] if b > 0 else []
+    hi_x = [(e * blk, w), (N * blk, n)] if e < N else []
+    lo_c = [((b - 1) * cb, eqs)] if b > 0 else []
+    hi_c = [(e * cb + eqs, cb - eqs), (N * cb, ncon - N * cb)] if e < N else []
+    return lo_x, hi_x, lo_c, hi_c
+
+
+class _MinresRank:
+    """One rank of a sharded MINRES solve: the shard handle, its rank, its workspace and iterate, the operator's arguments"""
+    __slots__ = ("docp", "rank", "w", "z", "x", "y", "sigma", "sx", "sc", "rhs", "precond")
+
+    def __init__(self, docp, rank, w, z, x, y, sigma, sx, sc, rhs, precond):
+        self.docp, self.rank, self.w, self.z, self.x, self.y, self.sigma = docp, rank, w, z, x, y, float(sigma)
+        self.sx, self.sc, self.rhs, self.precond = sx, sc, rhs, precond
+
+
+class MinresPhases:
+    """THE phase order of the sharded MINRES solve (ctd_kkt_minres_shard_*, include/ctdirect_hip.h), written once for both drivers:
+    `ShardedDOCP.kkt_minres` (one rank per process, the gathers are collectives of the process group) and `kkt_minres_shards` (every
+    rank in this process, the gathers are device copies).  ranks: the _MinresRank of every rank this process drives; halo(): fills
+    the halo of every rank's Lanczos vector (w.v_x, w.v_c); gather(which): fills every rank's w.gathered_a / w.gathered_b ("a" / "b")
+    from the ranks' send slots.  Everything is enqueued on one stream; nothing here waits for the host except `infos`."""
+
+    def __init__(self, ranks, halo, gather):
+        self.ranks, self.halo, self.gather = ranks, halo, gather
+
+    def start(self, rtol, max_iter):
+        for r in self.ranks:
+            r.docp.kkt_minres_shard_start(r.rhs, r.z, r.w, r.rank, precond=r.precond, rtol=rtol, max_iter=max_iter)
+        self.gather("a")
+        for r in self.ranks:
+            r.docp.kkt_minres_shard_begin(r.w, r.rank)
+
+    def iterate(self, k):
+        """k iterations: per iteration the halo of v, K v (two launches per rank), (A), the gather of slot A, (B), the gather of
+        slot B, (C)"""
+        for _ in range(k):
+            self.halo()
+            for r in self.ranks:
+                r.docp.kktprod_shard(r.x, r.y, r.w.v_x, r.w.v_c, r.sigma, r.sx, r.sc, out=(r.w.kv_x, r.w.kv_c))
+                r.docp.kkt_minres_shard_alfa(r.z, r.w, r.rank)
+            self.gather("a")
+            for r in self.ranks:
+                r.docp.kkt_minres_shard_lanczos(r.z, r.w, r.rank)
+            self.gather("b")
+            for r in self.ranks:
+                r.docp.kkt_minres_shard_update(r.z, r.w, r.rank)
+
+    def infos(self):
+        """every rank's MinresInfo: the one host read per chunk"""
+        return [r.docp.kkt_minres_shard_info(r.w) for r in self.ranks]
+
+    def solve(self, rtol, max_iter, check_every, on_chunk=None):
+        """start, then chunks of check_every iterations with one read of the state between chunks.  Every rank's state has the
+        same bytes (every cross-rank sum is formed from the same gathered slots in the same order on every rank), so the first
+        rank's status decides for all of them."""
+        if check_every < 1 or max_iter < 1:
+            raise ValueError("check_every and max_iter must be at least 1")
+        self.start(rtol, max_iter)
+        done = 0
+        while True:
+            self.iterate(check_every)
+            done += check_every
+            infos = self.infos()
+            if on_chunk is not None:
+                on_chunk(self, infos)
+            if infos[0].status != "running" or done >= max_iter:
+                return infos
+
+
+def _kkt_halo_index(d, lay):
+    """`_kkt_halo_ranges` of the handle d's shard as one sorted index tensor (CPU) into an (nvar + ncon)-vector, without the
+    entries the shard owns (lay: its ctd_minres_shard_layout)"""
+    blk, cb, eqs, n, _, w = _shard_dims(d)
+    nvar, ncon = d.dim_NLP_variables, d.dim_NLP_constraints
+    lo_x, hi_x, lo_c, hi_c = _kkt_halo_ranges(d.shard.step_begin, d.shard.step_end, d.time.steps, n, w, blk, cb, eqs, ncon)
+    parts = [s + torch.arange(k) for s, k in lo_x + hi_x] + [nvar + s + torch.arange(k) for s, k in lo_c + hi_c]
+    if not parts:
+        return torch.zeros(0, dtype=torch.long)
+    idx = torch.unique(torch.cat(parts))
+    own = ((idx >= lay.var_begin) & (idx < lay.var_end)) | ((idx >= lay.row_begin) & (idx < lay.row_end)) | \
+          ((idx >= lay.tail_begin) & (idx < lay.tail_end))
+    return idx[~own]
+
+
+def minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond=None, out=None, workspaces=None):
+    """The MinresPhases of a solve whose shards are ALL in this process: `handles` are the shard handles of one transcription in
+    ascending order of their steps (one whole-grid handle: the single shard), on one GPU and one stream (torch's current one).
+    xs: one x per handle (a shard's own entries and the halo it reads valid, or the table of `set_x_shards` set); y, rhs, sx, sc:
+    full-length tensors shared by the shards, or one per shard (a list); precond: None, a pair (px, pc) or one pair per shard.
+    out / workspaces: one z / one MinresShardWorkspace per shard, allocated when None.  The gathers are device copies of every
+    send slot into every shard's gathered area; the halo of the Lanczos vector is copied from the owners' vectors."""
+    G = len(handles)
+    dev = xs[0].device
+    per = lambda a: list(a) if isinstance(a, (list, tuple)) else [a] * G      # noqa: E731
+    ys, rhss, sxs, scs = per(y), per(rhs), per(sx), per(sc)
+    pres = list(precond) if precond is not None and isinstance(precond[0], (list, tuple)) else [precond] * G
+    cur = torch.cuda.current_stream(dev).cuda_stream
+    ranks = []
+    for k, h in enumerate(handles):
+        if h._stream_raw != cur:
+            h.set_stream(cur)
+        w = workspaces[k] if workspaces is not None else h.kkt_minres_shard_workspace(G)
+        z = out[k] if out is not None else torch.empty(w.layout.n, dtype=torch.float64, device=dev)
+        ranks.append(_MinresRank(h, k, w, z, xs[k], ys[k], obj_weight, sxs[k], scs[k], rhss[k], pres[k]))
+    if G == 1:
+        return MinresPhases(ranks, lambda: None, lambda which: None)
+    n = ranks[0].w.layout.n
+    full = torch.empty(n, dtype=torch.float64, device=dev)
+    vs = [r.w.ws[r.w.layout.off_v:r.w.layout.off_v + n] for r in ranks]
+    halos = [_kkt_halo_index(r.docp, r.w.layout).to(dev) for r in ranks]
+    slot = ranks[0].w.layout.slot
+
+    def halo():
+        for r, v in zip(ranks, vs):
+            lay = r.w.layout
+            full[lay.var_begin:lay.var_end].copy_(v[lay.var_begin:lay.var_end])
+            full[lay.row_begin:lay.row_end].copy_(v[lay.row_begin:lay.row_end])
+        for v, idx in zip(vs, halos):
+            if idx.numel():
+                v.index_copy_(0, idx, full.index_select(0, idx))
+
+    def gather(which):
+        for r in ranks:
+            send = r.w.send_a if which == "a" else r.w.send_b
+            for q in ranks:
+                (q.w.gathered_a if which == "a" else q.w.gathered_b)[r.rank * slot:(r.rank + 1) * slot].copy_(send)
+
+    return MinresPhases(ranks, halo, gather)
+
+
+def kkt_minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10, max_iter=None, check_every=16,
+                      out=None, workspaces=None, on_chunk=None):
+    """Preconditioned MINRES on K z = rhs over several shard handles of ONE process (`minres_shards` describes the arguments): the
+    in-process counterpart of `ShardedDOCP.kkt_minres`, for hosts that drive all GPUs from one process.  The same phase order
+    (MinresPhases) issues the same kernel launches on the same bytes as one process per rank does.  Returns (zs, infos): every
+    shard's full-length z (its owned entries and the nv tail valid) and MinresInfo; on_chunk(phases, infos) is called after every
+    chunk of check_every iterations."""
+    ph = minres_shards(handles, xs, y, rhs, obj_weight, sx, sc, precond, out, workspaces)
+    n = ph.ranks[0].w.layout.n
+    infos = ph.solve(float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every), on_chunk)
+    return [r.z for r in ph.ranks], infos
+
+
 class ShardedDOCP:
     """One rank's view of a grid-sharded transcription.  `make_docp(steps=(begin, end))` builds the engine handle
     (ctdirect DOCP) for the rank's block of steps."""
@@ -157,10 +315,7 @@ class ShardedDOCP:
         self.docp = make_docp(steps=self.steps)
         d = self.docp
         disc = d.discretization
-        self.cb = disc._state_stage_eqs_block + disc._step_pathcons_block
-        self.blk = disc._step_variables_block
-        self.n, self.m = d.dims.NLP_x, d.dims.NLP_u
-        self.halo_w = self.n + (self.m if getattr(disc, "_final_control", False) else 0)     # trapeze: the next node's control too
+        self.blk, self.cb, _, self.n, self.m, self.halo_w = _shard_dims(d)                   # (halo_w: trapeze: the next node's control too)
         # one-point schemes (midpoint, Euler): the residual of the step BEFORE this rank's first one depends on this rank's
         # first state, and the rank owns those Jacobian entries: it needs that step's block too
         self.halo_lo = self.blk if (disc.stage == 0 and not getattr(disc, "_final_control", False)) else 0
@@ -175,6 +330,7 @@ class ShardedDOCP:
         self._phalo = {}                    # (layout, device) -> index sets and buffers of exchange_product_halo / _rows
         self._vv = None
         self._f = None
+        self._minres_ws = None              # the workspace of `kkt_minres`, kept between solves
         self._peer = None                   # data_ptr of the x buffer the peer table is ACTIVE for (enable_peer_x), None: off
         self._peer_tables = {}              # x data_ptr -> (the tensor itself, mapped pointers of the other ranks' buffers): the
                                             # tensor is kept alive so the allocator cannot hand its address to another buffer
@@ -362,16 +518,15 @@ class ShardedDOCP:
             # my first node | last block | final state || my first node's path rows | last step's state / stage rows | tail
             pack_x = [b * blk + ar(w), (e - 1) * blk + ar(blk), N * blk + ar(n)]
             pack_c = [b * cb + eqs + ar(p), (e - 1) * cb + ar(eqs), N * cb + ar(tail)]
-            dst_x, src_x, dst_c, src_c = [], [], [], []
+            # where the entries go: the read set, stated once (rank r > 0 <=> b > 0, r + 1 < G <=> e < N); where they come from
+            lo_x, hi_x, lo_c, hi_c = _kkt_halo_ranges(b, e, N, n, w, blk, cb, eqs, self.docp.dim_NLP_constraints)
+            at = lambda ranges: [s + ar(k) for s, k in ranges]      # noqa: E731
+            dst_x, dst_c, src_x, src_c = at(lo_x) + at(hi_x), at(lo_c) + at(hi_c), [], []
             if r > 0:
-                dst_x += [ar(n), (b - 1) * blk + ar(blk)]
                 src_x += [ar(n), (r - 1) * L + w + ar(blk)]
-                dst_c.append((b - 1) * cb + ar(eqs))
                 src_c.append((r - 1) * L + Lx + p + ar(eqs))
             if r + 1 < G:
-                dst_x += [e * blk + ar(w), N * blk + ar(n)]
                 src_x += [(r + 1) * L + ar(w), (G - 1) * L + w + blk + ar(n)]
-                dst_c += [e * cb + eqs + ar(p), N * cb + ar(tail)]
                 src_c += [(r + 1) * L + Lx + ar(p), (G - 1) * L + Lx + p + eqs + ar(tail)]
             cat = lambda parts: (torch.cat(parts) if parts else torch.zeros(0, dtype=torch.long)).to(dx.device)      # noqa: E731
             ent = self._phalo[("kkt", dx.device)] = (cat(pack_x), cat(pack_c), cat(dst_x), cat(src_x), cat(dst_c), cat(src_c), Lx,
@@ -681,6 +836,48 @@ class ShardedDOCP:
             r0, r1 = self.owned_constraints()
             pc[r0:r1] += sc[r0:r1]
         return px, pc
+
+    def kkt_minres(self, x, y, rhs, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10, max_iter=None, check_every=16,
+                   out=None, x_halo_valid=False, y_halo_valid=False):
+        """`DOCP.kkt_minres` of the sharded transcription: preconditioned MINRES on K z = rhs with K the operator of `kktprod`,
+        device-resident, every rank working on its own entries of the Krylov vectors (`ctd_kkt_minres_shard_*`).  Every tensor
+        is full-length with this rank's own entries valid (x, rhs, px: + the nv tail; sx: the nv tail on the last rank only; y, sx,
+        sc may be None).  precond: None, a pair (px, pc), or "diag": the pair of `kkt_diag_precond`.  Returns (z, MinresInfo): z
+        full-length, this rank's own entries and the nv tail valid (`out`: z).
+        The halos of x and y are exchanged once before the loop (`x_halo_valid`, `y_halo_valid`: as in `kktprod`).  Per iteration:
+        the halo of the Lanczos vector (`exchange_kkt_halo`), the two launches of `kktprod_shard`, three vector launches and two
+        more small all-gathers (the send slots); NO all-reduce: every cross-rank sum is an all-gather followed by a sum in rank
+        order on the device, so the bits depend on the split of the grid only.  Everything runs on torch's current stream; the
+        host reads the state once per `check_every` iterations.
+        NO COLLECTIVE AGREES ON STOPPING, and none is needed: every rank forms every scalar from the same gathered bytes in the
+        same order, so the state every rank reads has the same bytes, every rank leaves the loop after the same chunk, and the
+        collective counts match."""
+        d = self.docp
+        n = d.dim_NLP_variables + d.dim_NLP_constraints
+        if x is None or rhs is None:
+            raise ValueError(("x" if x is None else "rhs") + " is required")
+        self._product_x(x, "kkt_minres", x_halo_valid)
+        if y is not None and not y_halo_valid:
+            self.exchange_product_rows(y)
+        if isinstance(precond, str):
+            if precond != "diag":
+                raise ValueError(f'precond is None, a pair (px, pc) or "diag", not {precond!r}')
+            precond = self.kkt_diag_precond(x, y, obj_weight, sx, sc, x_halo_valid=True, y_halo_valid=True)
+        collective = self.world > 1 or _FORCE
+        w = self._minres_ws
+        if w is None or w.ws.device != x.device:
+            w = self._minres_ws = d.kkt_minres_shard_workspace(self.world)
+        z = torch.empty(n, dtype=torch.float64, device=x.device) if out is None else out
+
+        def gather(which):
+            # (one rank and no rehearsal: the layout makes the gathered areas the send slots)
+            if collective:
+                _all_gather_into(w.gathered_a if which == "a" else w.gathered_b, w.send_a if which == "a" else w.send_b, self.group)
+
+        ph = MinresPhases([_MinresRank(d, self.rank, w, z, x, y, obj_weight, sx, sc, rhs, precond)],
+                          lambda: self.exchange_kkt_halo(w.v_x, w.v_c), gather)
+        info = ph.solve(float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every))[0]
+        return z, info
 
     def obj(self, x, as_tensor=False):
         """Objective of the whole transcription: the shards' partial sums added with one all-reduce of one double that never

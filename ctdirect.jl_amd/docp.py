@@ -107,6 +107,9 @@ _MF_OPS = {
 # iterations: the completed ones; phibar: the estimate of the M-norm of the residual, beta1 its initial value; Anorm, ynorm: the
 # estimates of |K| and |z| (ctd_minres_info)
 MinresInfo = namedtuple("MinresInfo", "status iterations phibar Anorm ynorm beta1")
+# The caller-owned workspace of a sharded solve (DOCP.kkt_minres_shard_workspace): the tensor, its layout (ctd_minres_shard_layout)
+# and the views the caller exchanges or hands to kktprod_shard
+MinresShardWorkspace = namedtuple("MinresShardWorkspace", "ws layout n_ranks v_x v_c kv_x kv_c send_a send_b gathered_a gathered_b")
 
 
 def _mf_rows(L, nvar, ncon):
@@ -737,6 +740,77 @@ class DOCP:
         """`ctd_kkt_minres_info`: waits for the handle's stream and returns the MinresInfo of the solve started last."""
         info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
         self._ck(_lib.lib().ctd_kkt_minres_info(self._h, C.byref(info)))
+        return self._minres_info(info)
+
+    # ---- the solve on a shard of the grid (ctd_kkt_minres_shard_*): the phases between the caller's all-gathers --------------------
+    def kkt_minres_shard_layout(self, n_ranks):
+        """`ctd_kkt_minres_shard_layout`: what this handle's shard owns of a Krylov vector (var_*, tail_*, row_*: index ranges of an
+        (nvar + ncon)-vector; n_own, n_dot), the launch geometry (nwg, chunk) and the offsets of the workspace, for a split of the
+        grid into n_ranks blocks.  Needs no device."""
+        lay = _lib.ctd_minres_shard_layout(struct_size=C.sizeof(_lib.ctd_minres_shard_layout))
+        self._ck(_lib.lib().ctd_kkt_minres_shard_layout(self._h, int(n_ranks), C.byref(lay)))
+        return lay
+
+    def kkt_minres_shard_workspace(self, n_ranks, ws=None):
+        """The caller-owned workspace of one sharded solve on this handle's GPU (`ws`: the caller's tensor of
+        kkt_minres_shard_layout(n_ranks).workspace doubles, allocated when None): a MinresShardWorkspace with the tensor `ws` and
+        named views of it -- v_x, v_c (the Lanczos vector the operator is applied to), kv_x, kv_c (where `kktprod_shard` puts K v),
+        send_a, send_b (this rank's slots) and gathered_a, gathered_b (n_ranks slots each, rank-major: what the all-gathers
+        fill; with one rank they are the send slots)."""
+        import torch
+        lay = self.kkt_minres_shard_layout(n_ranks)
+        if ws is None:
+            ws = torch.zeros(lay.workspace, dtype=torch.float64, device=torch.device("cuda", self.device))
+        self._dev_ptr(ws, lay.workspace, "ws")
+        nvar, n, slot, G = self.dim_NLP_variables, lay.n, lay.slot, int(n_ranks)
+        cut = lambda off, k: ws[off:off + k]        # noqa: E731
+        return MinresShardWorkspace(ws, lay, G, cut(lay.off_v, nvar), cut(lay.off_v + nvar, n - nvar), cut(lay.off_kv, nvar),
+                                    cut(lay.off_kv + nvar, n - nvar), cut(lay.off_send_a, slot), cut(lay.off_send_b, slot),
+                                    cut(lay.off_gathered_a, G * slot), cut(lay.off_gathered_b, G * slot))
+
+    def _shard_ws_ptr(self, w):
+        return self._dev_ptr(w.ws, w.layout.workspace, "ws")
+
+    def kkt_minres_shard_start(self, rhs, z, w, rank, precond=None, rtol=1e-10, max_iter=None):
+        """`ctd_kkt_minres_shard_start_dev_async` on the workspace w: z = 0 and the vectors on the owned entries, the partial sums
+        of beta1^2 into w.send_a.  precond: None or a pair (px, pc), read now only.  max_iter: default 5 (nvar + ncon)."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        px, pc = (None, None) if precond is None else precond
+        if (px is None) != (pc is None):
+            raise ValueError("px and pc are given both (M = diag(1 / px, 1 / pc)) or neither")
+        for nm, a in (("rhs", rhs), ("z", z)):
+            if a is None:
+                raise ValueError(f"{nm} is required")
+        sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=1.0)
+        if px is not None:
+            sys.px, sys.pc = self._dev_ptr(px, nvar, "px").value, self._dev_ptr(pc, ncon, "pc").value
+        self._ck(_lib.lib().ctd_kkt_minres_shard_start_dev_async(
+            self._h, C.byref(sys), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"), self._shard_ws_ptr(w),
+            w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+
+    def kkt_minres_shard_begin(self, w, rank):
+        """`ctd_kkt_minres_shard_begin_dev_async`: beta1 from w.gathered_a, the first Lanczos vector, the state."""
+        self._ck(_lib.lib().ctd_kkt_minres_shard_begin_dev_async(self._h, self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+
+    def _shard_phase(self, fn, z, w, rank):
+        self._ck(fn(self._h, self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+
+    def kkt_minres_shard_alfa(self, z, w, rank):
+        """`ctd_kkt_minres_shard_alfa_dev_async`: phase (A), after `kktprod_shard` wrote K v into (w.kv_x, w.kv_c)."""
+        self._shard_phase(_lib.lib().ctd_kkt_minres_shard_alfa_dev_async, z, w, rank)
+
+    def kkt_minres_shard_lanczos(self, z, w, rank):
+        """`ctd_kkt_minres_shard_lanczos_dev_async`: phase (B), after w.gathered_a was filled."""
+        self._shard_phase(_lib.lib().ctd_kkt_minres_shard_lanczos_dev_async, z, w, rank)
+
+    def kkt_minres_shard_update(self, z, w, rank):
+        """`ctd_kkt_minres_shard_update_dev_async`: phase (C), after w.gathered_b was filled."""
+        self._shard_phase(_lib.lib().ctd_kkt_minres_shard_update_dev_async, z, w, rank)
+
+    def kkt_minres_shard_info(self, w):
+        """`ctd_kkt_minres_shard_info`: waits for the handle's stream and returns the MinresInfo in the workspace's state."""
+        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        self._ck(_lib.lib().ctd_kkt_minres_shard_info(self._h, self._shard_ws_ptr(w), w.n_ranks, C.byref(info)))
         return self._minres_info(info)
 
     def grad_shard(self, x, g, sync=False):

@@ -508,10 +508,11 @@ int32_t ctd_jsq_cols_dev_async(ctd_handle* h, const double* x_dev, const double*
  * not the one of ctd_kktprod* (a graph captured over ctd_kktprod keeps working); nothing nnzj- or nnzh-sized.  The host form also
  * stages its vectors (3 (nvar + ncon) doubles more).  One solve per handle at a time: a start discards the solve before it.
  * Capturable after one warm start on the handle (run-time OCPs compile their KKT kernels then).
- * OUT OF SCOPE: shard handles (the all-reduce inside the recurrences), several right-hand sides, a nonzero initial guess.
+ * OUT OF SCOPE: several right-hand sides, a nonzero initial guess.  Shard handles are refused by these entry points: the solve on a
+ * shard of the grid is the ctd_kkt_minres_shard_* family below, whose collectives are the caller's.
  * Checks in this order: NULL handle -> CTD_EINVAL; sys (info) NULL or its struct_size not sizeof(ctd_kkt_system)
- * (sizeof(ctd_minres_info)) -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle -> CTD_EINVAL (there is no shard form
- * yet); null x, rhs or z -> CTD_EINVAL; z equal to any input -> CTD_EINVAL; only one of px / pc -> CTD_EINVAL; k, max_iter or
+ * (sizeof(ctd_minres_info)) -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE; shard handle -> CTD_EINVAL (these entry points
+ * have no shard form: ctd_kkt_minres_shard_* below is it); null x, rhs or z -> CTD_EINVAL; z equal to any input -> CTD_EINVAL; only one of px / pc -> CTD_EINVAL; k, max_iter or
  * check_every < 1, or rtol < 0 or NaN -> CTD_EINVAL; iters before any start, or with another z than the start -> CTD_EINVAL.
  * ctd_last_error names the reason, beginning with the entry point that was called. */
 #define CTD_KKT_MINRES_WORKSPACE(n) (8 * (int64_t)(n) + 3072)
@@ -551,6 +552,70 @@ int32_t ctd_kkt_minres_dev(ctd_handle* h, const ctd_kkt_system* sys, const doubl
                            int64_t max_iter, int64_t check_every, ctd_minres_info* info);
 int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs, double* z, double rtol, int64_t max_iter,
                        int64_t check_every, ctd_minres_info* info);
+
+/* ---- the MINRES solve on a shard of the grid ------------------------------------------------------------------------------
+ * The solve above for a grid sharded by time step over `n_ranks` handles (processes, or handles of one process), rank r holding
+ * the r-th block of steps in ascending order: the same recurrences, stopping tests, freeze and launch cut, every rank working on
+ * its own entries of the Krylov vectors.  The LIBRARY ISSUES NO COLLECTIVE and never waits for the host: the entry points below
+ * are the phases between which the CALLER exchanges data -- three small all-gathers per iteration, no all-reduce:
+ *     start;  all-gather slot A;  begin;
+ *     per iteration:  exchange the halo of (v_x, v_c);  ctd_kktprod_shard_dev_async on (v_x, v_c) -> (kv_x, kv_c);  alfa;
+ *                     all-gather slot A;  lanczos;  all-gather slot B;  update
+ * EVERY CROSS-RANK SUM is an all-gather followed by a sum on the device in rank order (csrc/ctd_krylov_shard_kernels.hpp states the
+ * order), done redundantly by every rank: the bits of the iterate and of the state depend on the split of the grid only -- not on a
+ * collective's algorithm, the backend, or whether the shards live in one process or several -- and every rank holds the same
+ * state bytes, so all ranks stop after the same chunk without agreeing on it.  A single shard of the whole grid gives the bits of
+ * ctd_kkt_minres_dev.
+ * OWNED ENTRIES of a rank (ctd_kkt_minres_shard_layout), of every n-vector (n = nvar + ncon, variables first; z, rhs, the
+ * workspace vectors): its variables [var_begin, var_end), the nv tail [tail_begin, tail_end) -- replicated: every rank keeps and
+ * updates it with the same bits, the last rank counts it in the inner products --, its rows [row_begin, row_end).  Nothing else of
+ * z or of a workspace vector is written.  rhs, px, pc must be valid on the owned entries (the tail on every rank).
+ * WORKSPACE, caller-owned: CTD_KKT_MINRES_SHARD_WORKSPACE(n, n_ranks) doubles of device memory, cut by
+ * ctd_kkt_minres_shard_layout: v and kv (n entries each; their halves are dx, dy / rx, rc of ctd_kktprod_shard_dev_async), the two
+ * SEND SLOTS of CTD_KKT_MINRES_SHARD_SLOT doubles each -- what the rank contributes to an all-gather -- and the two GATHERED areas
+ * of n_ranks slots, rank-major, which the caller's all-gather fills (n_ranks == 1: the gathered areas are the send slots, nothing
+ * is to be gathered).  The handle keeps no state of the solve: two solves on two workspaces do not interfere.
+ * Entries read and written per phase (owned entries only; K v at the nv tail is taken from the gathered partial sums of slot A):
+ *   start    reads rhs, px, pc; writes z = 0, every workspace vector, send slot A (partial sums of beta1^2), the padding of both
+ *   begin    reads gathered A; writes v, the state
+ *   alfa     reads v, kv, r1; writes send slot A (partial sums of alfa, the rank's partial sums of the tail of kv)
+ *   lanczos  reads gathered A, kv, z, v, w, w2, minv; writes r1, r2, y, send slot B
+ *   update   reads gathered B, y; writes w, w2, z, v, the state
+ * Once the status is set every phase returns before it stores anything (alfa still commits the state once).
+ * Every handle is accepted: a whole-grid handle is the single shard of a one-rank split.
+ * Checks in this order: NULL handle -> CTD_EINVAL; sys / info / layout NULL or struct_size wrong -> CTD_EINVAL; host-only handle
+ * -> CTD_ENODEVICE (not the layout query, which needs no device); n_ranks < 1 or rank outside [0, n_ranks) -> CTD_EINVAL; a handle
+ * whose steps cannot be block `rank` of a split into n_ranks blocks (n_ranks > N; rank 0 must begin at step 0 and no other rank
+ * does, rank n_ranks - 1 must end at step N and no other rank does; at least rank steps before it and n_ranks - 1 - rank after
+ * it) -> CTD_EINVAL; null or misaligned (8 bytes) pointers -> CTD_EINVAL; z (n entries) overlapping the workspace
+ * (CTD_KKT_MINRES_SHARD_WORKSPACE doubles) anywhere -> CTD_EINVAL; start: z or the workspace overlapping rhs, px or pc, only one of
+ * px / pc, rtol < 0 or NaN, max_iter < 1 -> CTD_EINVAL.  ctd_last_error names the entry point and the argument. */
+#define CTD_KKT_MINRES_SHARD_SLOT 2080
+#define CTD_KKT_MINRES_SHARD_WORKSPACE(n, n_ranks) (8 * (int64_t)(n) + (2 + 2 * (int64_t)(n_ranks)) * CTD_KKT_MINRES_SHARD_SLOT + 96)
+/* struct_size = sizeof(ctd_minres_shard_layout), set by the caller.  Indices into an n-vector: var_*, tail_*, row_* (rows:
+ * nvar + the row); n_own: the entries the rank updates, n_dot: those it counts in a sum; nwg, chunk: the launch geometry over the
+ * compacted list of owned indices; off_*: offsets in doubles into the workspace; workspace: the doubles it needs */
+typedef struct ctd_minres_shard_layout {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t n, n_ranks;
+    int64_t var_begin, var_end, tail_begin, tail_end, row_begin, row_end;
+    int64_t n_own, n_dot, nwg, chunk;
+    int64_t slot;
+    int64_t off_v, off_kv, off_send_a, off_send_b, off_gathered_a, off_gathered_b, off_state;
+    int64_t workspace;
+} ctd_minres_shard_layout;
+int32_t ctd_kkt_minres_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out);
+/* Enqueue-only on the handle's stream, device pointers, one launch each; capturable (run-time OCPs after one warm
+ * ctd_kktprod_shard_dev_async).  start reads sys->px / sys->pc (both or neither) and nothing else of sys */
+int32_t ctd_kkt_minres_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev,
+                                             double* ws_dev, int32_t n_ranks, int32_t rank, double rtol, int64_t max_iter);
+int32_t ctd_kkt_minres_shard_begin_dev_async(ctd_handle* h, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_shard_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_shard_lanczos_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_shard_update_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+/* waits for the handle's stream and reads the state out of the workspace: the one host read per chunk of iterations */
+int32_t ctd_kkt_minres_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info);
 
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of

@@ -199,7 +199,10 @@ def cons_jac_table():
 
 
 # ---- vector kernels of the device-resident MINRES solve (csrc/ctd_krylov.hip; profiles/kkt_minres_resources.md) -----------------
-KRYLOV_KERNELS = ("krylov_init_kernel", "krylov_first_kernel", "krylov_alfa_kernel", "krylov_lanczos_kernel", "krylov_update_kernel")
+KRYLOV_KERNELS = ("krylov_init_kernel", "krylov_first_kernel", "krylov_alfa_kernel", "krylov_lanczos_kernel", "krylov_update_kernel",
+                  # the shard form (csrc/ctd_krylov_shard_kernels.hpp)
+                  "krylov_shard_init_kernel", "krylov_shard_first_kernel", "krylov_shard_alfa_kernel", "krylov_shard_lanczos_kernel",
+                  "krylov_shard_update_kernel")
 
 
 def krylov_table():
