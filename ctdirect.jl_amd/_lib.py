@@ -63,6 +63,15 @@ class ctd_minres_shard_layout(C.Structure):
         "slot", "off_v", "off_kv", "off_send_a", "off_send_b", "off_gathered_a", "off_gathered_b", "off_state", "workspace")]
 
 
+# the layout of the chunked block-tridiagonal Schur preconditioner (ctd_kkt_schur_layout); CTD_KKT_SCHUR_FIXED
+KKT_SCHUR_FIXED = 512
+
+
+class ctd_schur_layout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(nm, C.c_int64) for nm in (
+        "N", "block_rows", "tail_rows", "first_tail_row", "tail_cols", "n_chunks", "chunk_steps", "workspace")]
+
+
 # every symbol include/ctdirect_hip.h declares: name -> (restype, argtypes)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -146,6 +155,14 @@ SYMBOLS = {
                                        C.POINTER(ctd_minres_info)]),
     "ctd_kkt_minres": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _dp, _dp, C.c_double, C.c_int64, C.c_int64,
                                    C.POINTER(ctd_minres_info)]),
+    # chunked block-tridiagonal Schur preconditioner: layout, factor, solve, status, and the solve that carries it
+    "ctd_kkt_schur_layout": (C.c_int32, [_vp, C.c_int64, C.POINTER(ctd_schur_layout)]),
+    "ctd_kkt_schur_factor_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "ctd_kkt_schur_solve_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "ctd_kkt_schur_info": (C.c_int32, [_vp, _vp, _ip]),
+    "ctd_kkt_minres_schur_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_double]),
+    "ctd_kkt_minres_schur_dev": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_double, C.c_int64, C.c_int64,
+                                             C.POINTER(ctd_minres_info)]),
     # ... and its shard form: the phases between the caller's all-gathers
     "ctd_kkt_minres_shard_layout": (C.c_int32, [_vp, C.c_int32, C.POINTER(ctd_minres_shard_layout)]),
     "ctd_kkt_minres_shard_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double,

@@ -29,6 +29,7 @@
 #include "ctd_diag_kernels.hpp"
 #include "ctd_krylov_kernels.hpp"
 #include "ctd_krylov_shard_kernels.hpp"
+#include "ctd_schur_kernels.hpp"
 #include "ctd_jit.hpp"
 
 using namespace ctd;
@@ -139,6 +140,12 @@ struct ctd_handle {
     DevBuf<> d_mrws, d_mrkpartial, d_mrp, d_mrrhs, d_mrz;
     double* mr_z = nullptr;
     bool mr_precond = false;
+    // chunked block-tridiagonal Schur preconditioner (ctd_kkt_schur*): the CSR pattern on the device, uploaded by the first factor;
+    // the pattern check of plan_kkt_schur passed (it is made once); the workspace of the factor the solve started last carries
+    // (null: none, the diagonal or the plain solve)
+    DevBuf<int64_t> d_schur_rowptr, d_schur_colind;
+    bool schur_verified = false;
+    double* mr_schur = nullptr;
     std::string err;
 };
 
@@ -1536,18 +1543,37 @@ static int32_t mr_check_rtol(ctd_handle* h, const MfCall& c, double rtol) {
 }
 
 static KrylovParams mr_params(const ctd_handle* h) {
-    return krylov_params(h->d_mrws.p, h->model.L.nvar + h->model.L.ncon, h->mr_z, h->mr_precond);
+    KrylovParams kp = krylov_params(h->d_mrws.p, h->model.L.nvar + h->model.L.ncon, h->mr_z, h->mr_precond);
+    if (h->mr_schur) {
+        const Layout& L = h->model.L;
+        kp.s_lo = L.nvar;
+        kp.s_hi = L.nvar + L.N * (int64_t)L.cb;
+        kp.s_part = h->mr_schur + kSchurPart;
+        kp.s_nwg = schur_solve_grid(L.N);
+    }
+    return kp;
+}
+// the solve launch of the Schur preconditioner inside the solve: y = T^-1 r2 on the block rows, the partial sums of r2 . y
+static SchurSolveParams mr_schur_params(const ctd_handle* h, const KrylovParams& kp, int32_t mode) {
+    const Layout& L = h->model.L;
+    return SchurSolveParams{L.N, L.cb, mode, h->mr_schur, kp.r2 + L.nvar, kp.y + L.nvar, h->mr_schur + kSchurPart, kp.cur};
 }
 
 // max_iter: the cap the device state carries
 static int32_t mr_enqueue_start(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, const double* rhs_dev, double* z_dev, double rtol,
-                                int64_t max_iter) {
+                                int64_t max_iter, double* schur_ws = nullptr) {
     const Layout& L = h->model.L;
     const int64_t n = L.nvar + L.ncon;
     if (const int32_t st = h->d_mrws.grow(h, krylov_workspace(n), c.fn())) return st;
     h->mr_z = z_dev;
     h->mr_precond = sys.px != nullptr;
-    return c.launched(h, krylov_start(mr_params(h), rhs_dev, sys.px, sys.pc, L.nvar, rtol, max_iter, h->stream));
+    h->mr_schur = schur_ws;
+    const KrylovParams kp = mr_params(h);
+    if (!schur_ws) return c.launched(h, krylov_start(kp, rhs_dev, sys.px, sys.pc, L.nvar, rtol, max_iter, h->stream));
+    hipError_t e = krylov_schur_init(kp, rhs_dev, sys.px, sys.pc, L.nvar, h->stream);
+    if (e == hipSuccess) e = schur_solve(mr_schur_params(h, kp, SCHUR_START), h->stream);
+    if (e == hipSuccess) e = krylov_schur_first(kp, rtol, max_iter, h->stream);
+    return c.launched(h, e);
 }
 
 // k iterations: K v (v and kv are Krylov vectors: dx / dy and rx / rc are their halves), then (A), (B), (C)
@@ -1559,7 +1585,12 @@ static int32_t mr_enqueue_iters(ctd_handle* h, const MfCall& c, const ctd_kkt_sy
                                                h->d_mrkpartial))
             return st;
         hipError_t e = krylov_alfa(kp, h->stream);
-        if (e == hipSuccess) e = krylov_step(kp, h->stream);
+        if (e == hipSuccess && !h->mr_schur) e = krylov_step(kp, h->stream);
+        if (e == hipSuccess && h->mr_schur) {
+            e = krylov_schur_lanczos(kp, h->stream);
+            if (e == hipSuccess) e = schur_solve(mr_schur_params(h, kp, SCHUR_ITER), h->stream);
+            if (e == hipSuccess) e = krylov_schur_update(kp, h->stream);
+        }
         if (e != hipSuccess) return c.launched(h, e);
     }
     return CTD_OK;
@@ -1580,8 +1611,8 @@ static int32_t mr_read_info(ctd_handle* h, ctd_minres_info* info) {
 
 // start, then at most ceil(max_iter / check_every) chunks: the device freezes the solve at max_iter iterations
 static int32_t mr_drive(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, const double* rhs_dev, double* z_dev, double rtol,
-                        int64_t max_iter, int64_t check_every, ctd_minres_info* info) {
-    if (const int32_t st = mr_enqueue_start(h, c, sys, rhs_dev, z_dev, rtol, max_iter)) return st;
+                        int64_t max_iter, int64_t check_every, ctd_minres_info* info, double* schur_ws = nullptr) {
+    if (const int32_t st = mr_enqueue_start(h, c, sys, rhs_dev, z_dev, rtol, max_iter, schur_ws)) return st;
     for (int64_t done = 0; done < max_iter; done += check_every) {
         if (const int32_t st = mr_enqueue_iters(h, c, sys, check_every)) return st;
         if (const int32_t st = mr_read_info(h, info)) return st;
@@ -1668,6 +1699,163 @@ int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* r
                          return mr_drive(h, c, dev, h->d_mrrhs.p, h->d_mrz.p, rtol, max_iter, check_every, info);
                      },
                      {{z, h->d_mrz, n}});
+}
+
+// ---- chunked block-tridiagonal Schur preconditioner (plan: ctd_schur_plan.hpp; kernels, sums and workspace: ctd_schur_kernels.hpp) -----
+static_assert(kSchurFixed == CTD_KKT_SCHUR_FIXED, "the fixed part of the workspace of the header");
+static constexpr int32_t kPlanStatus[] = {CTD_OK, CTD_EINVAL, CTD_EGRID, CTD_ESCHEME, CTD_EPATTERN, CTD_EPROBLEM};
+
+// The checks every entry point of the family shares once the handle (and its device) are known: whole grid, then the plan's own
+// (CSR order, block_rows, chunk_steps, the pattern -- walked once per handle)
+static int32_t schur_plan(ctd_handle* h, const char* fn, int64_t chunk_steps, SchurPlan& pl) {
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->plan.kp.halo)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
+                                   "step_end, ctd_set_x_shards) is refused: the Schur preconditioner has no shard form yet");
+    std::string err;
+    const int st = plan_kkt_schur(h->model, chunk_steps, !h->schur_verified, pl, err);
+    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
+    h->schur_verified = true;
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_layout(ctd_handle* h, int64_t chunk_steps, ctd_schur_layout* out) {
+    const char* fn = "ctd_kkt_schur_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_schur_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_layout) = " +
+                                       std::to_string(sizeof(ctd_schur_layout)));
+    SchurPlan pl;
+    if (const int32_t st = schur_plan(h, fn, chunk_steps, pl)) return st;
+    out->reserved = 0;
+    out->N = pl.N;
+    out->block_rows = pl.block_rows;
+    out->tail_rows = pl.tail_rows;
+    out->first_tail_row = pl.first_tail_row;
+    out->tail_cols = pl.tail_cols;
+    out->n_chunks = pl.n_chunks;
+    out->chunk_steps = pl.chunk_steps;
+    out->workspace = pl.workspace;
+    return CTD_OK;
+}
+
+// the pattern on the device, at the first factor: refused inside a capture like the other first-use allocations
+static int32_t schur_upload_pattern(ctd_handle* h, const char* fn) {
+    if (h->d_schur_rowptr.p && h->d_schur_colind.p) return CTD_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the first factor on a handle uploads the Jacobian pattern, which cannot be done "
+                                   "while the stream is capturing; make one call before the capture");
+    (void)hipGetLastError();
+    const Model& mo = h->model;
+    std::vector<int64_t> rowptr(mo.L.ncon + 1), colind, c;
+    colind.reserve(mo.nnzj);
+    for (int64_t i = 0; i < mo.L.ncon; ++i) {
+        rowptr[i] = (int64_t)colind.size();
+        mo.gen_row(i, c);
+        colind.insert(colind.end(), c.begin(), c.end());
+    }
+    rowptr[mo.L.ncon] = (int64_t)colind.size();
+    if ((int64_t)colind.size() != mo.nnzj) return fail(h, CTD_EPATTERN, std::string(fn) + ": internal: the generated rows disagree with nnzj");
+    HIP_TRY(h, upload(h->d_schur_colind, colind));
+    HIP_TRY(h, upload(h->d_schur_rowptr, rowptr));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_factor_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev, int64_t chunk_steps,
+                                       double* ws_dev) {
+    const char* fn = "ctd_kkt_schur_factor_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurPlan pl;
+    if (const int32_t st = schur_plan(h, fn, chunk_steps, pl)) return st;
+    if (!jvals_dev || !px_dev || !ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
+    if (ws_dev == jvals_dev || ws_dev == px_dev || ws_dev == sc_dev)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    if (const int32_t st = schur_upload_pattern(h, fn)) return st;
+    const SchurFactorParams fp{pl.N, pl.first_tail_col, pl.chunk_steps, pl.n_chunks, (int32_t)pl.block_rows, 0,
+                               h->d_schur_rowptr.p, h->d_schur_colind.p, jvals_dev, px_dev, sc_dev, ws_dev};
+    const hipError_t e = schur_factor(fp, h->stream);
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_solve_dev_async(ctd_handle* h, const double* ws_dev, const double* r_dev, double* out_dev) {
+    const char* fn = "ctd_kkt_schur_solve_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurPlan pl;
+    if (const int32_t st = schur_plan(h, fn, 1, pl)) return st;
+    if (!ws_dev || !r_dev || !out_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
+    if (out_dev == r_dev || out_dev == ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not be an input buffer");
+    const SchurSolveParams sp{pl.N, (int32_t)pl.block_rows, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr};
+    const hipError_t e = schur_solve(sp, h->stream);
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block) {
+    const char* fn = "ctd_kkt_schur_info";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurPlan pl;
+    if (const int32_t st = schur_plan(h, fn, 1, pl)) return st;
+    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int64_t head[5];
+    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
+    if (head[0] != kSchurTag || head[1] != pl.N || head[2] != pl.block_rows || head[4] < 1 || head[4] > pl.N)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle (ctd_kkt_schur_factor_dev_async)");
+    std::vector<int64_t> status((size_t)head[4]);
+    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
+    *first_bad_block = -1;
+    for (int64_t b : status)
+        if (b >= 0 && (*first_bad_block < 0 || b < *first_bad_block)) *first_bad_block = b;
+    return CTD_OK;
+}
+
+// The solve with the factor as its preconditioner: the checks of ctd_kkt_minres_dev, then the family's own
+static constexpr MfOp kMrSchurStart = {{"ctd_kkt_minres_schur_start_dev_async", "ctd_kkt_minres_schur_start_dev_async", "ctd_kkt_minres_schur_start_dev_async"},
+                                       JIT_KKT, 0, false, false, false, "sys->x, rhs and z", "z"},
+                      kMrSchurDev = {{"ctd_kkt_minres_schur_dev", "ctd_kkt_minres_schur_dev", "ctd_kkt_minres_schur_dev"},
+                                     JIT_KKT, 0, false, false, false, "sys->x, rhs and z", "z"};
+static int32_t mr_schur_check(ctd_handle* h, const MfCall& c, const ctd_kkt_system* sys, const double* ws, const double* rhs, const double* z) {
+    if (!sys->px || !sys->pc || !ws)
+        return fail(h, CTD_EINVAL, std::string(c.fn()) + ": null argument (sys->px, sys->pc and schur_ws are required)");
+    for (const double* p : {sys->x, sys->y, sys->sx, sys->sc, sys->px, sys->pc, rhs, z})
+        if (p == ws) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": the workspace (schur_ws) must not be another argument's buffer");
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_minres_schur_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
+                                             double* z_dev, double rtol) {
+    const MfCall c{kMrSchurStart, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if (on.st) return on.st;
+    SchurPlan pl;
+    if ((st = schur_plan(h, c.fn(), 1, pl))) return st;             // (whole grid, CSR order, the block size)
+    if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
+    if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
+    if ((st = mr_check_rtol(h, c, rtol))) return st;
+    return mr_enqueue_start(h, c, *sys, rhs_dev, z_dev, rtol, INT64_MAX, schur_ws_dev);
+}
+
+int32_t ctd_kkt_minres_schur_dev(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev, double* z_dev,
+                                 double rtol, int64_t max_iter, int64_t check_every, ctd_minres_info* info) {
+    const MfCall c{kMrSchurDev, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, true, info, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if (on.st) return on.st;
+    SchurPlan pl;
+    if ((st = schur_plan(h, c.fn(), 1, pl))) return st;             // (whole grid, CSR order, the block size)
+    if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
+    if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
+    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c, "check_every", check_every)))
+        return st;
+    return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info, schur_ws_dev);
 }
 
 // ---- the solve on a shard of the grid (ownership, slots and summation order: ctd_krylov_shard_kernels.hpp) ------------------------

@@ -4,6 +4,7 @@
 #include "ctd_kernel_body.hpp"
 #include "ctd_hess_body.hpp"
 #include "ctd_jit.hpp"
+#include "ctd_schur_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -1273,6 +1274,47 @@ KrylovShardPlan plan_krylov_shard(const Layout& L, int64_t step_begin, int64_t s
     pl.n_dot = pl.n_own - (last ? 0 : pl.tail_hi - pl.tail_lo);
     geom(pl.n_own, &pl.nwg, &pl.chunk);
     return pl;
+}
+
+// The plan of the chunked block-tridiagonal Schur preconditioner (ctd_schur_plan.hpp): the blocks are the steps' constraint blocks
+// of the layout (cb rows each), the tail what follows them, the tail columns the nv optimisation variables
+int plan_kkt_schur(const Model& mo, int64_t chunk_steps, bool verify, SchurPlan& out, std::string& err) {
+    const Layout& L = mo.L;
+    if (mo.order != 1) { err = "the Schur preconditioner needs a handle with value_order = CTD_ORDER_CSR (the order GPU KKT consumers take)"; return ST_EINVAL; }
+    if (L.cb > kSchurMaxBlock) {
+        err = "block_rows = " + std::to_string(L.cb) + " exceeds " + std::to_string(kSchurMaxBlock) + " (one lane of a wave per row of a block)";
+        return ST_EINVAL;
+    }
+    if (chunk_steps < 1) { err = "chunk_steps = " + std::to_string(chunk_steps) + ", must be at least 1"; return ST_EINVAL; }
+    out = SchurPlan{};
+    out.N = L.N;
+    out.block_rows = L.cb;
+    out.first_tail_row = L.N * (int64_t)L.cb;
+    out.tail_rows = L.ncon - out.first_tail_row;
+    out.tail_cols = L.nv;
+    out.first_tail_col = L.v_off;
+    out.chunk_steps = chunk_steps < L.N ? chunk_steps : L.N;
+    out.n_chunks = (L.N + out.chunk_steps - 1) / out.chunk_steps;
+    out.workspace = schur_workspace(L.N, L.cb);
+    if (!verify) return ST_OK;
+    // block of the first block row seen in every non-tail column; rows come in ascending block order, so a later row of the column
+    // must lie in that block or the next one
+    std::vector<int64_t> first(L.v_off, -1);
+    std::vector<int64_t> cols;
+    for (int64_t r = 0; r < out.first_tail_row; ++r) {
+        const int64_t k = r / L.cb;
+        mo.gen_row(r, cols);
+        for (int64_t c : cols) {
+            if (c >= L.v_off) continue;
+            if (first[c] < 0) first[c] = k;
+            else if (k - first[c] > 1) {
+                err = "row " + std::to_string(r) + " (block " + std::to_string(k) + ") shares column " + std::to_string(c) +
+                      " with a row of block " + std::to_string(first[c]) + ": the Schur complement is not block tridiagonal";
+                return ST_EPATTERN;
+            }
+        }
+    }
+    return ST_OK;
 }
 
 int build_model(const HostDesc& d, Model& mo, std::string& err) {

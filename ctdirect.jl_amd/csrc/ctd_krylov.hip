@@ -25,6 +25,9 @@ __device__ __forceinline__ bool first_lane() { return blockIdx.x == 0 && threadI
 __device__ __forceinline__ bool bad_beta2(double b2) { return !(b2 >= 0.0) || !__builtin_isfinite(b2); }
 
 // start, first launch: the vectors and the partial sums of beta1^2 = rhs . M rhs
+// SCHUR (every kernel below that has it): the instantiation for the block-tridiagonal Schur preconditioner; false compiles to the
+// code without it
+template <bool SCHUR>
 __global__ void __launch_bounds__(kKrylovBlock) krylov_init_kernel(const KrylovParams kp, const double* rhs, const double* px,
                                                                    const double* pc, const int64_t nvar) {
     __shared__ double wsum[kWaves];
@@ -38,22 +41,26 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_init_kernel(const KrylovP
             kp.minv[i] = m;
             yv = m * r;
         }
+        const bool solved = SCHUR && i >= kp.s_lo && i < kp.s_hi;        // y and its term: the solve launch's
         kp.r1[i] = r;
         kp.r2[i] = r;
-        kp.y[i] = yv;
+        if (!solved) kp.y[i] = yv;
         kp.v[i] = 0.0;
         kp.kv[i] = 0.0;
         kp.w[i] = 0.0;
         kp.w2[i] = 0.0;
         kp.z[i] = 0.0;
-        acc += r * yv;
+        if (!solved) acc += r * yv;
     }
     block_partial_sums<1, 1>(&acc, wsum, kp.part + blockIdx.x);
 }
 
 // start, second launch: beta1, the first Lanczos vector v = y / beta1, both copies of the state
+template <bool SCHUR>
 __global__ void __launch_bounds__(kKrylovBlock) krylov_first_kernel(const KrylovParams kp, const double rtol, const int64_t max_iter) {
-    const double b2 = ordered_sum(kp.part, kp.nwg, 1);
+    double b2 = ordered_sum(kp.part, kp.nwg, 1);
+    if (SCHUR)
+        for (int b = 0; b < kp.s_nwg; ++b) b2 += kp.s_part[b];
     KrylovState t{};
     t.cs = -1.0;
     t.rtol = rtol;
@@ -107,6 +114,7 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_alfa_kernel(const KrylovP
 }
 
 // (B)
+template <bool SCHUR>
 __global__ void __launch_bounds__(kKrylovBlock) krylov_lanczos_kernel(const KrylovParams kp) {
     __shared__ double wsum[kWaves * 4];
     const KrylovState s = *kp.cur;
@@ -135,9 +143,10 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_lanczos_kernel(const Kryl
         r1[i] = r2v;
         r2[i] = yv;
         const double my = precond ? minv[i] * yv : yv;
-        y[i] = my;
+        const bool solved = SCHUR && i >= kp.s_lo && i < kp.s_hi;
+        if (!solved) y[i] = my;
         const double zv = z[i], u = (v[i] - oldeps * w2[i]) - delta * w[i];
-        acc[0] += yv * my;
+        if (!solved) acc[0] += yv * my;
         acc[1] += zv * zv;
         acc[2] += zv * u;
         acc[3] += u * u;
@@ -146,6 +155,7 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_lanczos_kernel(const Kryl
 }
 
 // (C)
+template <bool SCHUR>
 __global__ void __launch_bounds__(kKrylovBlock) krylov_update_kernel(const KrylovParams kp) {
     const KrylovState s = *kp.cur;
     if (s.status != KRYLOV_RUNNING) return;
@@ -157,6 +167,10 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_update_kernel(const Krylo
         zz += p[1];
         zu += p[2];
         uu += p[3];
+    }
+    if (SCHUR) {
+#pragma unroll 8
+        for (int b = 0; b < kp.s_nwg; ++b) b2 += kp.s_part[b];
     }
     const double alfa = *kp.alfa;
     KrylovState t = s;
@@ -219,10 +233,10 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_update_kernel(const Krylo
 
 hipError_t krylov_start(const KrylovParams& kp, const double* rhs, const double* px, const double* pc, int64_t nvar, double rtol,
                         int64_t max_iter, hipStream_t st) {
-    hipLaunchKernelGGL(krylov_init_kernel, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp, rhs, px, pc, nvar);
+    hipLaunchKernelGGL(krylov_init_kernel<false>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp, rhs, px, pc, nvar);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(krylov_first_kernel, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp, rtol, max_iter);
+    hipLaunchKernelGGL(krylov_first_kernel<false>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp, rtol, max_iter);
     return hipGetLastError();
 }
 
@@ -232,10 +246,27 @@ hipError_t krylov_alfa(const KrylovParams& kp, hipStream_t st) {
 }
 
 hipError_t krylov_step(const KrylovParams& kp, hipStream_t st) {
-    hipLaunchKernelGGL(krylov_lanczos_kernel, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp);
+    hipLaunchKernelGGL(krylov_lanczos_kernel<false>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(krylov_update_kernel, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp);
+    hipLaunchKernelGGL(krylov_update_kernel<false>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp);
+    return hipGetLastError();
+}
+
+hipError_t krylov_schur_init(const KrylovParams& kp, const double* rhs, const double* px, const double* pc, int64_t nvar, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_init_kernel<true>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp, rhs, px, pc, nvar);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_first(const KrylovParams& kp, double rtol, int64_t max_iter, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_first_kernel<true>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp, rtol, max_iter);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_lanczos(const KrylovParams& kp, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_lanczos_kernel<true>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_update(const KrylovParams& kp, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_update_kernel<true>, dim3((unsigned)kp.nwg), dim3(kKrylovBlock), 0, st, kp);
     return hipGetLastError();
 }
 

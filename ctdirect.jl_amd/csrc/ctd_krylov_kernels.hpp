@@ -85,6 +85,11 @@ struct KrylovParams {
     double* part;                       // kKrylovSums x kKrylovMaxWg partial sums
     double* alfa;                       // alfa of the iteration, stored by (B) for (C)
     KrylovState *cur, *pend;
+    // the SCHUR instantiations only (ctd_schur_kernels.hpp): the block rows [s_lo, s_hi) of an n-vector, whose y the solve launch
+    // writes, and its s_nwg partial sums of r2 . y
+    int64_t s_lo, s_hi;
+    const double* s_part;
+    int32_t s_nwg;
 };
 
 // the workspace `ws` (krylov_workspace(n) doubles) cut into the kernels' arguments
@@ -111,5 +116,13 @@ hipError_t krylov_start(const KrylovParams& kp, const double* rhs, const double*
                         int64_t max_iter, hipStream_t st);
 hipError_t krylov_alfa(const KrylovParams& kp, hipStream_t st);
 hipError_t krylov_step(const KrylovParams& kp, hipStream_t st);
+// The same with the block-tridiagonal Schur preconditioner (kp.s_*): SCHUR instantiations of the same kernels, in which y = M r2
+// and its term of the inner product are left to the solve launch on the block rows, and the kernel that adds the partial sums of
+// beta^2 (beta1^2) adds the solve's after (B)'s (the init kernel's), in ascending workgroup order.  The caller enqueues the solve
+// launch between krylov_schur_init and krylov_schur_first, and between krylov_schur_lanczos (B) and krylov_schur_update (C)
+hipError_t krylov_schur_init(const KrylovParams& kp, const double* rhs, const double* px, const double* pc, int64_t nvar, hipStream_t st);
+hipError_t krylov_schur_first(const KrylovParams& kp, double rtol, int64_t max_iter, hipStream_t st);
+hipError_t krylov_schur_lanczos(const KrylovParams& kp, hipStream_t st);
+hipError_t krylov_schur_update(const KrylovParams& kp, hipStream_t st);
 
 }  // namespace ctd

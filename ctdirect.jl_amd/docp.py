@@ -109,6 +109,9 @@ _MF_OPS = {
 MinresInfo = namedtuple("MinresInfo", "status iterations phibar Anorm ynorm beta1")
 # The caller-owned workspace of a sharded solve (DOCP.kkt_minres_shard_workspace): the tensor, its layout (ctd_minres_shard_layout)
 # and the views the caller exchanges or hands to kktprod_shard
+# The chunked block-tridiagonal Schur preconditioner of DOCP.kkt_schur_precond: the pair (px, pc) of kkt_diag_precond it was built
+# from, the factor's workspace (a device tensor of layout.workspace doubles) and the layout (ctd_schur_layout)
+SchurPrecond = namedtuple("SchurPrecond", "px pc ws layout")
 MinresShardWorkspace = namedtuple("MinresShardWorkspace", "ws layout n_ranks v_x v_c kv_x kv_c send_a send_b gathered_a gathered_b")
 
 
@@ -633,6 +636,77 @@ class DOCP:
             pc = pc + np.asarray(sc, dtype=np.float64)
         return px, pc
 
+    # ---- chunked block-tridiagonal Schur preconditioner (ctd_kkt_schur*) -----------------------------------------------------------
+    @staticmethod
+    def _tensors_only(fn, **named):
+        for nm, a in named.items():
+            if a is not None and not _is_tensor(a):
+                raise ValueError(f"{fn}: {nm} must be a device tensor on the handle's GPU; NumPy inputs are not accepted (the Schur "
+                                 "preconditioner has no host path)")
+
+    def kkt_schur_layout(self, chunk_steps=None):
+        """`ctd_kkt_schur_layout`: N, block_rows (m), tail_rows, first_tail_row, tail_cols (nv), n_chunks, the effective chunk_steps
+        and the workspace in doubles of the chunked block-tridiagonal Schur preconditioner; chunk_steps = None: one chunk.  Checks
+        the handle's Jacobian pattern (rows sharing a non-tail column lie in the same or adjacent blocks).  Needs a CSR handle
+        (value_order="csr") of the whole grid; works on host-only handles."""
+        lay = _lib.ctd_schur_layout(struct_size=C.sizeof(_lib.ctd_schur_layout))
+        self._ck(_lib.lib().ctd_kkt_schur_layout(self._h, int((1 << 62) if chunk_steps is None else chunk_steps), C.byref(lay)))
+        return lay
+
+    def kkt_schur_precond(self, x, y, obj_weight=1.0, sx=None, sc=None, chunk_steps=None, floor=1e-8, jvals=None):
+        """The chunked block-tridiagonal Schur preconditioner of the operator `kktprod`:
+            M^-1 = blkdiag(diag(px), T_0, T_1, ..., diag(pc_tail)),   T_c = Jt_c diag(1 / px) Jt_c' + Sc_c
+        with (px, pc) the pair of `kkt_diag_precond(x, y, obj_weight, sx, sc, floor)`, Jt the Jacobian without the nv tail columns
+        and chunk c the constraint rows of chunk_steps consecutive time steps (None: one chunk, the whole grid); couplings between
+        chunks are dropped.  Unlike the diagonal it sees the coupling of neighbouring steps through J, which is what the iteration
+        count of MINRES on a collocation KKT system grows with.  jvals: the Jacobian values at x of this (CSR) handle, computed
+        with `cons_jac` when None.  Runs the factor (`ctd_kkt_schur_factor_dev_async`, two launches) and returns a SchurPrecond
+        (px, pc, ws, layout) for `kkt_minres(..., precond=P)`, `kkt_schur_solve` and `kkt_schur_info`.  Device tensors only."""
+        self._tensors_only("kkt_schur_precond", x=x, y=y, sx=sx, sc=sc, jvals=jvals)
+        import torch
+        self._check_x(x)
+        lay = self.kkt_schur_layout(chunk_steps)
+        px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc, floor)
+        if jvals is None:
+            _, jvals = self.cons_jac(x)
+        ws = torch.empty(lay.workspace, dtype=torch.float64, device=x.device)
+        return self.kkt_schur_factor(jvals, px, pc, sc, lay.chunk_steps, ws)
+
+    def kkt_schur_factor(self, jvals, px, pc, sc, chunk_steps, ws):
+        """`ctd_kkt_schur_factor_dev_async` on the caller's tensors (enqueue-only): the factor of T built from jvals, 1 / px and sc
+        (None: zero) into ws (kkt_schur_layout(chunk_steps).workspace doubles).  Returns the SchurPrecond (px, pc, ws, layout)."""
+        self._tensors_only("kkt_schur_factor", jvals=jvals, px=px, pc=pc, sc=sc, ws=ws)
+        lay = self.kkt_schur_layout(chunk_steps)
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        self._ck(_lib.lib().ctd_kkt_schur_factor_dev_async(
+            self._h, self._dev_ptr(jvals, self.nnzj, "jvals"), self._dev_ptr(px, nvar, "px"), self._dev_ptr(sc, ncon, "sc"),
+            int(lay.chunk_steps), self._dev_ptr(ws, lay.workspace, "ws")))
+        self._dev_ptr(pc, ncon, "pc")
+        return SchurPrecond(px, pc, ws, lay)
+
+    def kkt_schur_solve(self, P, r, out=None, sync=True):
+        """`ctd_kkt_schur_solve_dev_async`: out = blkdiag(T_c)^-1 r on the block rows (the first layout.first_tail_row entries); the
+        tail rows of out are left untouched (zero in a tensor allocated here).  r, out: ncon entries, out must not be r."""
+        self._tensors_only("kkt_schur_solve", r=r, out=out, ws=P.ws)
+        ncon = self.dim_NLP_constraints
+        if out is None:
+            import torch
+            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+        self._ck(_lib.lib().ctd_kkt_schur_solve_dev_async(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), self._dev_ptr(r, ncon, "r"),
+                                                         self._dev_ptr(out, ncon, "out")))
+        if sync:
+            self.sync()
+        return out
+
+    def kkt_schur_info(self, P):
+        """`ctd_kkt_schur_info`: waits for the handle's stream; -1 when every pivot of the factor was positive, otherwise the first
+        block (time step) whose pivot was not positive or not finite -- the preconditioner is then unusable (MINRES: "breakdown")."""
+        self._tensors_only("kkt_schur_info", ws=P.ws)
+        bad = C.c_int64(0)
+        self._ck(_lib.lib().ctd_kkt_schur_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
+        return bad.value
+
     # ---- device-resident preconditioned MINRES solve of K z = rhs (ctd_kkt_minres*) ---------------------------------------------
     def _kkt_system(self, fn, vecs, obj_weight, host_ok):
         """The ctd_kkt_system of a solve and the pointers of its other vectors.  vecs: (name, array, layout, required) rows, x
@@ -686,8 +760,10 @@ class DOCP:
         scalar recurrences and the stopping tests included; the host reads the status once per `check_every` iterations.  rhs
         and z have nvar + ncon entries, z0 = 0.  The recurrences and the stopping tests (rtol) are those of
         scipy.sparse.linalg.minres, so iteration counts are comparable with it.
-        precond: None; a pair (px, pc), M = diag(1 / px, 1 / pc), which must be positive; or "diag": the pair of
-        `kkt_diag_precond(x, y, obj_weight, sx, sc)`.  max_iter: default 5 (nvar + ncon), scipy's.
+        precond: None; a pair (px, pc), M = diag(1 / px, 1 / pc), which must be positive; "diag": the pair of
+        `kkt_diag_precond(x, y, obj_weight, sx, sc)`; a SchurPrecond P of `kkt_schur_precond` (device tensors only:
+        `ctd_kkt_minres_schur_dev`, one more launch per iteration); or "schur": that of `kkt_schur_precond(x, y, obj_weight, sx,
+        sc)`, one chunk.  max_iter: default 5 (nvar + ncon), scipy's.
         Returns (z, info), info a MinresInfo: status "converged", "max_iter" or "breakdown" (M not positive definite, a NaN, or
         the Krylov space exhausted), the iterations done, phibar, Anorm, ynorm, beta1.  Iterations enqueued after the status was
         set change nothing: z does not depend on check_every.  Results are reproducible bit for bit.  NumPy inputs use the host
@@ -696,12 +772,19 @@ class DOCP:
         n = self.dim_NLP_variables + self.dim_NLP_constraints
         if x is None or rhs is None:
             raise ValueError(("x" if x is None else "rhs") + " is required")
+        schur = None
         if isinstance(precond, str):
-            if precond != "diag":
-                raise ValueError(f'precond is None, a pair (px, pc) or "diag", not {precond!r}')
+            if precond not in ("diag", "schur"):
+                raise ValueError(f'precond is None, a pair (px, pc), a SchurPrecond, "diag" or "schur", not {precond!r}')
             self._check_x(x)
-            px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc)
-        else:
+            if precond == "schur":
+                precond = self.kkt_schur_precond(x, y, obj_weight, sx, sc)
+            else:
+                px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc)
+        if isinstance(precond, SchurPrecond):
+            self._tensors_only("kkt_minres with a Schur preconditioner", x=x, y=y, rhs=rhs, sx=sx, sc=sc, out=out)
+            schur, px, pc = precond, precond.px, precond.pc
+        elif not isinstance(precond, str):
             px, pc = (None, None) if precond is None else precond
         dev = hasattr(x, "is_cuda")
         if out is None:
@@ -714,6 +797,11 @@ class DOCP:
                 ("px", px, "v", False), ("pc", pc, "c", False), ("out", out, "k", True))
         dev, sys, p, keep = self._kkt_system("kkt_minres", rows, obj_weight, True)
         info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        if schur is not None:
+            self._ck(L.ctd_kkt_minres_schur_dev(self._h, C.byref(sys), self._dev_ptr(schur.ws, schur.layout.workspace, "ws"), p["rhs"],
+                                                p["out"], float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every),
+                                                C.byref(info)))
+            return out, self._minres_info(info)
         fn = L.ctd_kkt_minres_dev if dev else L.ctd_kkt_minres
         rhs_p, out_p = (p["rhs"], p["out"]) if dev else (C.cast(p["rhs"], C.POINTER(C.c_double)), C.cast(p["out"], C.POINTER(C.c_double)))
         self._ck(fn(self._h, C.byref(sys), rhs_p, out_p, float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every),
@@ -722,11 +810,17 @@ class DOCP:
 
     def kkt_minres_start(self, x, y, rhs, z, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10):
         """`ctd_kkt_minres_start_dev_async`: enqueues the initialisation of a solve on the device tensors (z = 0, the state) on the
-        handle's stream; precond: None or a pair (px, pc), read now only.  No iteration cap.  See `kkt_minres`."""
-        px, pc = (None, None) if precond is None else precond
+        handle's stream; precond: None or a pair (px, pc), read now only, or a SchurPrecond
+        (`ctd_kkt_minres_schur_start_dev_async`: its workspace is read by every iteration).  No iteration cap.  See `kkt_minres`."""
+        schur = precond if isinstance(precond, SchurPrecond) else None
+        px, pc = (None, None) if precond is None else ((precond.px, precond.pc) if schur else precond)
         rows = (("x", x, "v", True), ("y", y, "c", False), ("rhs", rhs, "k", True), ("z", z, "k", True), ("sx", sx, "v", False),
                 ("sc", sc, "c", False), ("px", px, "v", False), ("pc", pc, "c", False))
         _, sys, p, _ = self._kkt_system("kkt_minres_start", rows, obj_weight, False)
+        if schur:
+            self._ck(_lib.lib().ctd_kkt_minres_schur_start_dev_async(
+                self._h, C.byref(sys), self._dev_ptr(schur.ws, schur.layout.workspace, "ws"), p["rhs"], p["z"], float(rtol)))
+            return
         self._ck(_lib.lib().ctd_kkt_minres_start_dev_async(self._h, C.byref(sys), p["rhs"], p["z"], float(rtol)))
 
     def kkt_minres_iters(self, x, y, z, k, obj_weight=1.0, sx=None, sc=None):

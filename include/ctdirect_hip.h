@@ -617,6 +617,67 @@ int32_t ctd_kkt_minres_shard_update_dev_async(ctd_handle* h, double* z_dev, doub
 /* waits for the handle's stream and reads the state out of the workspace: the one host read per chunk of iterations */
 int32_t ctd_kkt_minres_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info);
 
+/* ---- chunked block-tridiagonal Schur preconditioner of the KKT MINRES solve ----------------------------------------------------
+ * The constraint rows come in N consecutive blocks of block_rows = m rows (block k: the rows of step k -- state equation, stage
+ * equations, path rows of node k), followed by tail_rows rows (final path rows, boundary rows); the last tail_cols = nv variables
+ * (free t0 / tf, parameters) are the tail columns.  With Jt = J without the tail columns, w = 1 / px and a chunk length L >= 1
+ * (chunk_steps), chunk c covers the blocks [c L, min((c + 1) L, N)) and
+ *     T_c = Jt_c diag(w) Jt_c' + Sc_c            (Jt_c: the rows of chunk c; block tridiagonal, m x m blocks)
+ *     M^-1 = blkdiag(diag(px), T_0, T_1, ..., diag(pc_tail)).
+ * The preconditioner applied is M: variables divided by px, tail rows by their pc, the rows of chunk c solved with the Cholesky
+ * factor of T_c.  Couplings between chunks are dropped: chunks are independent, each T_c is a principal submatrix of a positive
+ * semidefinite matrix plus Sc.  L >= N is one chunk (the effective chunk_steps is min(L, N)).
+ * The kernels do not depend on the OCP (compiled once, strict rounding); plain stores, no atomics, kernel boundaries are the only
+ * synchronisation between workgroups, the number of launches is fixed by the arguments, results are reproducible bit for bit: the
+ * order of every sum is stated in csrc/ctd_schur_kernels.hpp.
+ * LAYOUT (ctd_kkt_schur_layout; works on host-only handles): derived from the handle's layout, and checked on the handle's own
+ * Jacobian pattern: two rows that share a non-tail column lie in the same or in adjacent blocks (tail rows exempt), otherwise
+ * CTD_EPATTERN with the row in the message.  Refused: block_rows > 64 (CTD_EINVAL), chunk_steps < 1 (CTD_EINVAL), shard handles
+ * (CTD_EINVAL: there is no shard form yet), handles whose value_order is not CTD_ORDER_CSR (CTD_EINVAL).
+ * WORKSPACE, caller-owned: CTD_KKT_SCHUR_WORKSPACE(N, m) doubles of device memory: 512 fixed (a header, the partial sums of the
+ * solve inside MINRES), N words of per-chunk status, N m^2 for the diagonal blocks D_k -> L_k, N m^2 for the couplings E_k -> F_k.
+ * Checks in this order: NULL handle -> CTD_EINVAL; struct sizes -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE (not the layout);
+ * shard handle -> CTD_EINVAL; value_order not CSR -> CTD_EINVAL; block_rows > 64, chunk_steps < 1 -> CTD_EINVAL; the pattern ->
+ * CTD_EPATTERN; null pointers -> CTD_EINVAL; aliasing (an output equal to an input) -> CTD_EINVAL.  ctd_last_error begins with
+ * the entry point that was called. */
+#define CTD_KKT_SCHUR_FIXED 512
+#define CTD_KKT_SCHUR_WORKSPACE(N, m) (CTD_KKT_SCHUR_FIXED + (int64_t)(N) + 2 * (int64_t)(N) * (m) * (m))
+/* struct_size = sizeof(ctd_schur_layout), set by the caller.  first_tail_row = N block_rows; chunk_steps: the effective one */
+typedef struct ctd_schur_layout {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t N, block_rows, tail_rows, first_tail_row, tail_cols;
+    int64_t n_chunks, chunk_steps;
+    int64_t workspace;          /* doubles */
+} ctd_schur_layout;
+int32_t ctd_kkt_schur_layout(ctd_handle* h, int64_t chunk_steps, ctd_schur_layout* out);
+/* Factor, enqueue-only, two launches (assemble; block Cholesky, one wave per chunk).  jvals_dev: the nnzj Jacobian values as
+ * ctd_cons_jac_dev_async / ctd_jac_coord leave them on a CSR handle; px_dev: nvar entries; sc_dev: ncon entries or NULL (zero);
+ * ws_dev: CTD_KKT_SCHUR_WORKSPACE doubles, written in full.  The first call on a handle uploads the pattern (rowptr / colind) and
+ * is refused while the stream is capturing.  A pivot that is not positive or not finite is recorded in the workspace (the first
+ * bad block of every chunk) and the rest of that chunk's factor is NaN: the solve then yields NaN there, which the breakdown
+ * test of MINRES sees. */
+int32_t ctd_kkt_schur_factor_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev,
+                                       int64_t chunk_steps, double* ws_dev);
+/* out = blkdiag(T_c)^-1 r on the block rows; r, out: ncon entries, the tail rows of out are left untouched; out must not be r.
+ * One launch: a forward and a backward sweep, one wave per chunk.  A workspace that holds no factor of this handle's N and m
+ * is recognised on the device and nothing is stored. */
+int32_t ctd_kkt_schur_solve_dev_async(ctd_handle* h, const double* ws_dev, const double* r_dev, double* out_dev);
+/* waits for the handle's stream; *first_bad_block = -1 when every pivot was positive, otherwise the smallest bad block */
+int32_t ctd_kkt_schur_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block);
+/* The MINRES solve above with M of this section: sys->px and sys->pc are required (px: the one the factor was built from; pc is
+ * read on the tail rows).  Per iteration (B) forms r2 as before and y = M r2 on the variables and the tail rows; ONE ADDED LAUNCH
+ * solves the chunks for y on the block rows and writes one partial sum of r2 . y per workgroup (at most 256, a workgroup serves
+ * several chunks); (C) -- and the start's last kernel, for beta1^2 -- adds (B)'s partial sums in their order and after them the
+ * solve's in ascending workgroup order.  Six launches per iteration (the start: three), no host synchronisation; the freeze
+ * covers the added kernel.  The handle remembers that the solve started last carries a factor: ctd_kkt_minres_iters_dev_async
+ * and ctd_kkt_minres_info continue it unchanged.  The workspace must stay valid for the whole solve; the solve writes the partial sums in its fixed part and nothing else of it.  Checks as
+ * for ctd_kkt_minres_dev, then CSR order, px / pc / schur_ws_dev null, z or the workspace equal to an input. */
+int32_t ctd_kkt_minres_schur_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev,
+                                             const double* rhs_dev, double* z_dev, double rtol);
+int32_t ctd_kkt_minres_schur_dev(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
+                                 double* z_dev, double rtol, int64_t max_iter, int64_t check_every, ctd_minres_info* info);
+
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
  * ctd_sharded_handle included), modelled on ctd_grad_shard_dev_async: enqueue-only on the handle's stream, capturable after one

@@ -205,13 +205,36 @@ KRYLOV_KERNELS = ("krylov_init_kernel", "krylov_first_kernel", "krylov_alfa_kern
                   "krylov_shard_update_kernel")
 
 
+SCHUR_KERNELS = ("schur_assemble_kernel", "schur_factor_kernel", "schur_solve_kernel")
+
+
+def mangled(stem):
+    """the mangled names of the kernels of csrc/<stem>.hip in the order of the compiler's remarks: the template arguments of an
+    instantiation (remarks() keeps the kernel's plain name only)"""
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
+                        "-Rpass-analysis=kernel-resource-usage", "-c", f"{stem}.hip", "-o", os.devnull], cwd=CSRC, capture_output=True, text=True)
+    return re.findall(r"Function Name: (\S+)", r.stderr)
+
+
 def krylov_table():
     ks = remarks("ctd_krylov", "", KRYLOV_KERNELS)
-    assert [k["kernel"] for k in ks] == list(KRYLOV_KERNELS), ks
+    names = [n for n in mangled("ctd_krylov") if re.search("|".join(KRYLOV_KERNELS), n)]
+    assert len(names) == len(ks)
+    for k, n in zip(ks, names):         # the SCHUR = true instantiation of a kernel (its only template argument)
+        if re.search(r"ILb1EE", n):
+            k["kernel"] += "<SCHUR>"
+    assert sorted({k["kernel"].replace("<SCHUR>", "") for k in ks}) == sorted(KRYLOV_KERNELS), ks
+    sch = remarks("ctd_schur", "", SCHUR_KERNELS)
+    for k, n in zip(sch, [n for n in mangled("ctd_schur") if re.search("|".join(SCHUR_KERNELS), n)]):
+        mb = re.search(r"ILi(\d+)EE", n)
+        k["kernel"] += f"<{mb.group(1)}>" if mb else ""
+    ks += sch
     path = os.path.join(ROOT, "profiles", "kkt_minres_resources.md")
     lines = ["# Resources of the MINRES vector kernels (csrc/ctd_krylov.hip)\n\n",
              "From the compiler's remarks for gfx950 (`python profiles/resource_usage.py --krylov`, no GPU needed).  The kernels do not\n"
-             "depend on the OCP: one instantiation each.  The script fails if any of them uses scratch.\n\n",
+             "depend on the OCP: one instantiation each, two (`<SCHUR>`: with the block-tridiagonal Schur preconditioner) of the four whose\n"
+             "code differs with it; below them the kernels of that preconditioner (csrc/ctd_schur.hip), the factor and the solve per\n"
+             "largest block size.  The script fails if any of them uses scratch.\n\n",
              "| kernel | VGPR + AGPR | scratch B/lane | waves/SIMD |\n", "|---|---|---|---|\n"]
     for k in ks:
         assert k["scratch"] == 0, k
