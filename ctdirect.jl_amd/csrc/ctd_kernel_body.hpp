@@ -597,7 +597,10 @@ CTD_HD void fin_lead(const KParams& kp, const BlockCtx& cx, int k, int row = -1)
 // `ev`: the eval block of (slot k, point j) -- its place in the LDS record, or a register copy the caller stores afterwards
 // (r0, rstep): the rows r0, r0 + rstep, ... only -- the lane that evaluated those rows of the dynamics (split evaluation: one
 // part per wave, so the row tests are wave-uniform branches) finishes them itself
-template <class P, int SC, int S, bool LEAN = false>
+// STATIC (the tile of the static-emit kernel, cons_jac_static_body): row r of stage j is SELECTED from the stage blocks the lane
+// has in registers since eval_dynamics (butcher_pick's compare-and-select on j) -- K[j * n + r] at a run-time j is one more
+// global load, and a memory round trip, per row.  The same value.
+template <class P, int SC, int S, bool LEAN = false, bool STATIC = false>
 CTD_HD void fin_stage(const KParams& kp, const BlockCtx& cx, int k, int j, double* ev, int r0 = 0, int rstep = 1) {
     using V = LV<P, SC, S, LEAN>;
     constexpr int n = P::NX, nv = P::NV;
@@ -622,7 +625,7 @@ CTD_HD void fin_stage(const KParams& kp, const BlockCtx& cx, int k, int j, doubl
         // stage rows: K_i^j - f(...)   (irk_stagewise.jl:448-451)
 #pragma unroll
         for (int r = 0; r < n; ++r)
-            if (mine(r)) rec[R.oR + n + j * n + r] = K[j * n + r] - ev[R.of + r];
+            if (mine(r)) rec[R.oR + n + j * n + r] = (STATIC ? butcher_pick<S>(K, j, n, r) : K[j * n + r]) - ev[R.of + r];
 #pragma unroll
         for (int kk = 0; kk < nv; ++kk) {
             // d x_ij / d v_kk = dh * sum_l a_jl K^l  (x_i itself does not depend on v)
@@ -1306,7 +1309,7 @@ template <class P, int SC, int S> CTD_HD int early_leadbase(const KParams& kp) {
     return (((r_dyn + r_path) << lgT) + 63) & ~63;
 }
 
-template <class P, int SC, int S, bool REG = false, int NB = 1, bool B = false, bool LEAN = false>
+template <class P, int SC, int S, bool REG = false, int NB = 1, bool B = false, bool LEAN = false, bool STATIC = false>
 CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr, const EmitPreT<NB>* epre = nullptr,
                        const BatchLd bl = BatchLd{}) {
     constexpr bool FUSED = Dirs<P>::FUSED;
@@ -1523,7 +1526,7 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
                 CTD_SUB(kp, 1);
                 eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, evr);
                 CTD_SUB(kp, 2);
-                fin_stage<P, SC, S, LEAN>(kp, cx, k, j, evr);
+                fin_stage<P, SC, S, LEAN, STATIC>(kp, cx, k, j, evr);
                 CTD_SUB(kp, 3);
                 const int64_t i = slot_index<LEAN>(kp, cx, k);
                 if (i >= 0 && i < kp.L.N) {
@@ -1534,7 +1537,7 @@ CTD_HD void phase_eval(const KParams& kp, const BlockCtx& cx, int tid, int nthr,
             } else {
                 eval_dynamics<P, SC, S, false, LEAN>(kp, cx, k, j, q, ev);
                 // (folded fin: the generated code put every partial of the point on the lane of chunk 0)
-                if (FUSED || (fold_g && q == 0)) fin_stage<P, SC, S, LEAN>(kp, cx, k, j, ev);
+                if (FUSED || (fold_g && q == 0)) fin_stage<P, SC, S, LEAN, STATIC>(kp, cx, k, j, ev);
             }
         } else if (role < r_dyn + r_path) {
             eval_step_path<P, SC, S, REG, LEAN>(kp, cx, k, role - r_dyn);

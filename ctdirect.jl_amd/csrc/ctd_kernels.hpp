@@ -188,35 +188,71 @@ __global__ void __launch_bounds__(P::MAXB, (MinWaves<P, SC, S>::value)) cons_jac
 // <P, SC, S> (manual pattern, CSC order, whole grid), launched with NTHR lanes; WT: the emit phase's stores are write-through
 // (KParams::wt_store as a constant).  The body is chosen ONCE at entry: the edge workgroups run the lean body as it is, so the
 // tile's path -- pin, prefetch, evaluation, barrier, emit -- is one contiguous run of code with the workgroup size a constant.
-// Behind the barrier the tile reads no kernel argument that was not pinned in front of it.
+// Behind the barrier the tile reads no kernel argument at all.
+//
+// The tile arm reads TileArgs (ctd_layout.hpp) and nothing of kp: every one of its fields is named as an input of the empty asm
+// statements at entry, IN FRONT of the edge / tile branch, so the compiler fetches the whole block with a few wide scalar loads
+// behind one another and waits once.  The phase functions take a KParams; the arm hands them a local one filled from TileArgs
+// (tile_kparams) -- every function is inlined, so that struct never exists: each field read becomes the scalar register the
+// entry loads filled, each field the tile does not use a constant zero.  The six values of the emit phase (c, vals, seg_base,
+// reg_first, reg_last, vcol_base) pass through an asm statement as outputs: the compiler can then no longer fetch them a second
+// time behind the evaluation, it has to keep them (in scalar registers, or in lanes of a vector register where those run out).
+template <class P>
+__device__ __forceinline__ KParams tile_kparams(const TileArgs& ta) {
+    KParams tk{};
+    tk.L.N = ta.N; tk.L.v_off = ta.v_off; tk.L.stagewise = ta.stagewise; tk.L.t0 = ta.t0; tk.L.tf = ta.tf;
+    tk.tau = ta.tau; tk.T = ta.T; tk.has_edge = ta.has_edge; tk.step_begin = ta.step_begin; tk.step_end = ta.step_end;
+    tk.tmpl = ta.tmpl; tk.vtmpl = ta.vtmpl;
+    int64_t seg_base = ta.seg_base, reg_first = ta.reg_first, reg_last = ta.reg_last;
+    double *c = ta.c, *vals = ta.vals;
+    int64_t vb[kMaxNV] = {ta.vcol_base[0], ta.vcol_base[1], ta.vcol_base[2], ta.vcol_base[3]};
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the two pointers pass as GLOBAL pointers: a generic one that comes out of an asm statement has lost its address space, and
+    // the emit's stores would become flat ones)
+    using gdouble = __attribute__((address_space(1))) double;
+    gdouble *cg = (gdouble*)c, *vg = (gdouble*)vals;
+    asm volatile("" : "+s"(cg), "+s"(vg), "+s"(seg_base), "+s"(reg_first), "+s"(reg_last));
+    c = (double*)cg; vals = (double*)vg;
+#pragma unroll
+    for (int kk = 0; kk < P::NV; ++kk) asm volatile("" : "+s"(vb[kk]));
+#endif
+    tk.c = c; tk.vals = vals; tk.seg_base = seg_base; tk.reg_first = reg_first; tk.reg_last = reg_last;
+#pragma unroll
+    for (int kk = 0; kk < P::NV; ++kk) tk.vcol_base[kk] = vb[kk];
+    return tk;
+}
 template <class P, int SC, int S, bool DBG, int NTHR, bool WT>
-__device__ __forceinline__ void cons_jac_static_body(const KParams& kp, const double* __restrict__ xu, int block, double* ctd_lds) {
-    if (__builtin_expect(block < kp.has_edge, 0)) {
-        cons_jac_body<P, SC, S, DBG, false, true>(kp, xu, block, ctd_lds);
+__device__ __forceinline__ void cons_jac_static_body(const TileArgs& ta, const KParams& kp, int block, double* ctd_lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" ::"s"(ta.xu), "s"(ta.tau), "s"(ta.tmpl), "s"(ta.vtmpl), "s"(ta.c), "s"(ta.vals), "s"(ta.step_begin), "s"(ta.step_end),
+                 "s"(ta.N), "s"(ta.v_off), "s"(ta.t0), "s"(ta.tf), "s"(ta.seg_base), "s"(ta.reg_first), "s"(ta.reg_last),
+                 "s"(ta.vcol_base[0]), "s"(ta.vcol_base[P::NV > 1 ? 1 : 0]), "s"(ta.vcol_base[P::NV > 2 ? 2 : 0]),
+                 "s"(ta.vcol_base[P::NV > 3 ? 3 : 0]), "s"(ta.has_edge), "s"(ta.T), "s"(ta.stagewise));
+    if constexpr (DBG) asm volatile("" ::"s"(kp.stamps), "s"(kp.debug_stop));      // (diagnostics: in the same round)
+#endif
+    if (__builtin_expect(block < ta.has_edge, 0)) {
+        __builtin_assume(block < kp.has_edge);      // (make_tile_args: the same count -- the lean body's tile path is not compiled here)
+        cons_jac_body<P, SC, S, DBG, false, true>(kp, ta.xu, block, ctd_lds);
         return;
     }
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" ::"s"(kp.has_edge), "s"(kp.T), "s"(kp.HL), "s"(kp.HH), "s"(kp.step_begin), "s"(kp.step_end), "s"(kp.L.N),
-                 "s"(kp.L.v_off), "s"(kp.L.stagewise), "s"(kp.L.euler), "s"(kp.tau), "s"(kp.L.t0), "s"(kp.L.tf), "s"(xu),
-                 "s"(kp.tmpl), "s"(kp.vtmpl));
-#endif
+    const KParams tk = tile_kparams<P>(ta);
+    __builtin_assume(tk.tau != nullptr);        // (make_tile_args: a static tile is never launched without the table, so tau_global
+                                                // is its table load -- the division arm and its test are not compiled)
     ctd_stamp<DBG>(kp, 0);
     if (DBG && kp.debug_stop == 1) return;
     const int tid = (int)threadIdx.x;
-    BlockCtx cx = make_direct_ctx<true>(kp, block, ctd_lds, xu, LV<P, SC, S, true>::blk(kp), P::NV);
+    const double* __restrict__ xu = ta.xu;
+    BlockCtx cx = make_direct_ctx<true>(tk, block, ctd_lds, xu, LV<P, SC, S, true>::blk(tk), P::NV);
     cx.is_edge = 0;          // (this arm)
     cx.edge_part = 0;
-    const EmitPre pre = emit_prefetch_static<P, SC, S, NTHR>(kp, tid);
+    const EmitPre pre = emit_prefetch_static<P, SC, S, NTHR>(tk, tid);
     ctd_stamp<DBG>(kp, 1);
-    phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1, false, true>(kp, cx, tid, NTHR, &pre, BatchLd{});
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" ::"s"(kp.c), "s"(kp.vals), "s"(kp.seg_base), "s"(kp.reg_first), "s"(kp.reg_last), "s"(kp.vcol_base[0]));
-#endif
+    phase_eval<P, SC, S, RegEval<P, SC, S>::value, 1, false, true, true>(tk, cx, tid, NTHR, &pre, BatchLd{});
     __syncthreads();
     ctd_stamp<DBG>(kp, 2);
     ctd_stamp<DBG>(kp, 3);
     if (DBG && kp.debug_stop >= 2 && kp.debug_stop <= 4) return;
-    phase_emit_static<P, SC, S, NTHR, WT>(kp, cx, tid, pre);
+    phase_emit_static<P, SC, S, NTHR, WT>(tk, cx, tid, pre);
     ctd_stamp<DBG>(kp, 4);
     if (DBG && kp.stamps) {
         __builtin_amdgcn_s_waitcnt(0);
@@ -225,9 +261,9 @@ __device__ __forceinline__ void cons_jac_static_body(const KParams& kp, const do
     }
 }
 template <class P, int SC, int S, bool DBG, int NTHR, bool WT>
-__global__ void __launch_bounds__(NTHR, (MinWaves<P, SC, S>::value)) cons_jac_static_kernel(const KParams kp, const double* __restrict__ xu) {
+__global__ void __launch_bounds__(NTHR, (MinWaves<P, SC, S>::value)) cons_jac_static_kernel(const TileArgs ta, const KParams kp) {
     extern __shared__ double ctd_lds[];
-    cons_jac_static_body<P, SC, S, DBG, NTHR, WT>(kp, xu, (int)blockIdx.x, ctd_lds);
+    cons_jac_static_body<P, SC, S, DBG, NTHR, WT>(ta, kp, (int)blockIdx.x, ctd_lds);
 }
 // K iterates per launch (ctd_cons_jac_batch_dev_async): grid (tiles, members), the same bodies with B = true
 template <class P, int SC, int S>
@@ -770,14 +806,16 @@ hipError_t launch_static(const KParams& kp, const double* xu, int grid, size_t l
     if constexpr (StaticEmit<P, SC, S>::template built<NTHR>()) {
         using SE = StaticEmit<P, SC, S>;
         if (kp.Lseg != SE::Lseg || kp.vr != SE::vr || (SC == SC_IRK && S >= 2 && !kp.L.stagewise)) return hipSuccess;
+        const TileArgs ta = make_tile_args(kp, xu);       // (the tile workgroups' argument block: first kernel argument)
+        if (!ta.valid) return hipSuccess;
         done = true;
         auto go = [&](auto kern) -> hipError_t {
             if (lds_bytes > 64 * 1024) {
                 hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
                 if (e != hipSuccess) return e;
             }
-            if (e0 || e1) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), lds_bytes, st, e0, e1, 0, kp, xu);
-            else kern<<<grid, NTHR, lds_bytes, st>>>(kp, xu);
+            if (e0 || e1) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), lds_bytes, st, e0, e1, 0, ta, kp);
+            else kern<<<grid, NTHR, lds_bytes, st>>>(ta, kp);
             return hipGetLastError();
         };
         if (dbg) return kp.wt_store ? go(cons_jac_static_kernel<P, SC, S, true, NTHR, true>) : go(cons_jac_static_kernel<P, SC, S, true, NTHR, false>);

@@ -306,6 +306,47 @@ struct KParams {
     int32_t wg_stride;
     int32_t wt_store;       // 1: the emit phase's stores are write-through (sc1): small launches, see emit_store (ctd_kernel_body.hpp)
 };
+// ---- what a STATIC tile reads at run time (cons_jac_static_kernel, ctd_kernels.hpp) ---------------------------------------
+// The tile workgroups of the static-emit kernel take everything else from their instantiation (StaticLayout, StaticEmit), so their
+// run-time inputs are this short list.  In KParams the same fields lie between bytes 0x0c and 0x300, and the compiler fetched them
+// in four dependent rounds of scalar loads; here they are one contiguous, 64-byte aligned block at the START of the kernel
+// arguments: a few wide scalar loads, issued back to back at entry, one wait.  The Gauss-Legendre tiles need no halo record and
+// no Euler flag (HL = HH = euler = 0: make_tile_args refuses anything else), and they always read the time grid from its table.
+// KParams keeps every field -- the edge workgroups of the same launch run the lean body on it.
+struct alignas(64) TileArgs {
+    const double* xu;               // the iterate of this launch
+    const double* tau;              // normalized grid on device (N + 1): never null
+    const uint32_t* tmpl;
+    const uint32_t* vtmpl;
+    double* c;                      // outputs; either may be null
+    double* vals;
+    int64_t step_begin, step_end;
+    int64_t N;
+    int64_t v_off;
+    double t0, tf;
+    int64_t seg_base;
+    int64_t reg_first, reg_last;
+    int64_t vcol_base[kMaxNV];
+    int32_t has_edge;
+    int32_t T;
+    int32_t stagewise;
+    int32_t valid;                  // 1: filled from a KParams a static tile can run (host side only; no kernel reads it)
+};
+static_assert(sizeof(TileArgs) <= 192 && alignof(TileArgs) == 64, "TileArgs: three 64-byte lines at most, aligned to a line");
+// The one place that fills it.  valid = 0 when kp is not one a static tile can take: no time-grid table, a halo record, an Euler
+// flag, a sharded iterate or early emission -- launch_static then leaves the launch to the lean kernel.
+inline TileArgs make_tile_args(const KParams& kp, const double* xu) {
+    TileArgs ta{};
+    ta.xu = xu; ta.tau = kp.tau; ta.tmpl = kp.tmpl; ta.vtmpl = kp.vtmpl; ta.c = kp.c; ta.vals = kp.vals;
+    ta.step_begin = kp.step_begin; ta.step_end = kp.step_end;
+    ta.N = kp.L.N; ta.v_off = kp.L.v_off; ta.t0 = kp.L.t0; ta.tf = kp.L.tf;
+    ta.seg_base = kp.seg_base; ta.reg_first = kp.reg_first; ta.reg_last = kp.reg_last;
+    for (int k = 0; k < kMaxNV; ++k) ta.vcol_base[k] = kp.vcol_base[k];
+    ta.has_edge = kp.has_edge; ta.T = kp.T; ta.stagewise = kp.L.stagewise;
+    ta.valid = (kp.tau != nullptr && kp.HL == 0 && kp.HH == 0 && kp.L.euler == 0 && kp.L.sc == SC_IRK && kp.halo == nullptr && kp.n_early == 0) ? 1 : 0;
+    return ta;
+}
+
 // BATCHED launches (ctd_cons_jac_batch_dev_async, cons_jac_batch_kernel): workgroup (x, y) evaluates tile x of member y, which reads
 // xu + y * ldx and writes c + y * ldc, vals + y * ldv (leading dimensions in doubles).  A kernel argument of the batched kernel
 // only: the single-iterate kernel's argument block stays as it is (its size is part of every launch)
