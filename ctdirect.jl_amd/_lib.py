@@ -72,6 +72,17 @@ class ctd_schur_layout(C.Structure):
         "N", "block_rows", "tail_rows", "first_tail_row", "tail_cols", "n_chunks", "chunk_steps", "workspace")]
 
 
+# ... and of its log-depth exact form (ctd_kkt_schur_cr_layout)
+class ctd_schur_cr_layout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(nm, C.c_int64) for nm in (
+        "N", "block_rows", "tail_rows", "first_tail_row", "tail_cols", "n_levels", "factor_launches", "solve_launches", "workspace")]
+
+
+def kkt_schur_cr_workspace(N, m):
+    """CTD_KKT_SCHUR_CR_WORKSPACE(N, m)"""
+    return KKT_SCHUR_FIXED + N + 3 * N * m * m + 2 * N * m
+
+
 # every symbol include/ctdirect_hip.h declares: name -> (restype, argtypes)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -163,7 +174,15 @@ SYMBOLS = {
     "ctd_kkt_minres_schur_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_double]),
     "ctd_kkt_minres_schur_dev": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_double, C.c_int64, C.c_int64,
                                              C.POINTER(ctd_minres_info)]),
-    # ... and its shard form: the phases between the caller's all-gathers
+    # log-depth exact block-tridiagonal Schur preconditioner (block cyclic reduction): the same family without a chunk length
+    "ctd_kkt_schur_cr_layout": (C.c_int32, [_vp, C.POINTER(ctd_schur_cr_layout)]),
+    "ctd_kkt_schur_cr_factor_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, _vp]),
+    "ctd_kkt_schur_cr_solve_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "ctd_kkt_schur_cr_info": (C.c_int32, [_vp, _vp, _ip]),
+    "ctd_kkt_minres_schur_cr_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_double]),
+    "ctd_kkt_minres_schur_cr_dev": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_double, C.c_int64, C.c_int64,
+                                                C.POINTER(ctd_minres_info)]),
+    # ... and the shard form of the solve: the phases between the caller's all-gathers
     "ctd_kkt_minres_shard_layout": (C.c_int32, [_vp, C.c_int32, C.POINTER(ctd_minres_shard_layout)]),
     "ctd_kkt_minres_shard_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double,
                                                          C.c_int64]),

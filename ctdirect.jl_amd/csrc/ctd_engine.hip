@@ -29,6 +29,7 @@
 #include "ctd_diag_kernels.hpp"
 #include "ctd_krylov_kernels.hpp"
 #include "ctd_krylov_shard_kernels.hpp"
+#include "ctd_schur_cr_kernels.hpp"
 #include "ctd_schur_kernels.hpp"
 #include "ctd_jit.hpp"
 
@@ -142,10 +143,11 @@ struct ctd_handle {
     bool mr_precond = false;
     // chunked block-tridiagonal Schur preconditioner (ctd_kkt_schur*): the CSR pattern on the device, uploaded by the first factor;
     // the pattern check of plan_kkt_schur passed (it is made once); the workspace of the factor the solve started last carries
-    // (null: none, the diagonal or the plain solve)
+    // (null: none, the diagonal or the plain solve) and its kind (mr_schur_cr: the log-depth exact form, ctd_kkt_schur_cr*)
     DevBuf<int64_t> d_schur_rowptr, d_schur_colind;
     bool schur_verified = false;
     double* mr_schur = nullptr;
+    bool mr_schur_cr = false;
     std::string err;
 };
 
@@ -1558,20 +1560,29 @@ static SchurSolveParams mr_schur_params(const ctd_handle* h, const KrylovParams&
     const Layout& L = h->model.L;
     return SchurSolveParams{L.N, L.cb, mode, h->mr_schur, kp.r2 + L.nvar, kp.y + L.nvar, h->mr_schur + kSchurPart, kp.cur};
 }
+// ... of either kind: the chunked form's one launch, or the launches of the log-depth form (the last one: its partial sums, which
+// lie where the chunked solve leaves its own)
+static hipError_t mr_schur_solve(const ctd_handle* h, const KrylovParams& kp, int32_t mode) {
+    if (!h->mr_schur_cr) return schur_solve(mr_schur_params(h, kp, mode), h->stream);
+    const Layout& L = h->model.L;
+    return schur_cr_solve(SchurCrSolveParams{L.N, L.cb, mode, schur_cr_levels(L.N), 0, h->mr_schur, kp.r2 + L.nvar, kp.y + L.nvar, kp.cur},
+                          h->stream);
+}
 
 // max_iter: the cap the device state carries
 static int32_t mr_enqueue_start(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, const double* rhs_dev, double* z_dev, double rtol,
-                                int64_t max_iter, double* schur_ws = nullptr) {
+                                int64_t max_iter, double* schur_ws = nullptr, bool schur_cr = false) {
     const Layout& L = h->model.L;
     const int64_t n = L.nvar + L.ncon;
     if (const int32_t st = h->d_mrws.grow(h, krylov_workspace(n), c.fn())) return st;
     h->mr_z = z_dev;
     h->mr_precond = sys.px != nullptr;
     h->mr_schur = schur_ws;
+    h->mr_schur_cr = schur_ws && schur_cr;
     const KrylovParams kp = mr_params(h);
     if (!schur_ws) return c.launched(h, krylov_start(kp, rhs_dev, sys.px, sys.pc, L.nvar, rtol, max_iter, h->stream));
     hipError_t e = krylov_schur_init(kp, rhs_dev, sys.px, sys.pc, L.nvar, h->stream);
-    if (e == hipSuccess) e = schur_solve(mr_schur_params(h, kp, SCHUR_START), h->stream);
+    if (e == hipSuccess) e = mr_schur_solve(h, kp, SCHUR_START);
     if (e == hipSuccess) e = krylov_schur_first(kp, rtol, max_iter, h->stream);
     return c.launched(h, e);
 }
@@ -1588,7 +1599,7 @@ static int32_t mr_enqueue_iters(ctd_handle* h, const MfCall& c, const ctd_kkt_sy
         if (e == hipSuccess && !h->mr_schur) e = krylov_step(kp, h->stream);
         if (e == hipSuccess && h->mr_schur) {
             e = krylov_schur_lanczos(kp, h->stream);
-            if (e == hipSuccess) e = schur_solve(mr_schur_params(h, kp, SCHUR_ITER), h->stream);
+            if (e == hipSuccess) e = mr_schur_solve(h, kp, SCHUR_ITER);
             if (e == hipSuccess) e = krylov_schur_update(kp, h->stream);
         }
         if (e != hipSuccess) return c.launched(h, e);
@@ -1611,8 +1622,8 @@ static int32_t mr_read_info(ctd_handle* h, ctd_minres_info* info) {
 
 // start, then at most ceil(max_iter / check_every) chunks: the device freezes the solve at max_iter iterations
 static int32_t mr_drive(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sys, const double* rhs_dev, double* z_dev, double rtol,
-                        int64_t max_iter, int64_t check_every, ctd_minres_info* info, double* schur_ws = nullptr) {
-    if (const int32_t st = mr_enqueue_start(h, c, sys, rhs_dev, z_dev, rtol, max_iter, schur_ws)) return st;
+                        int64_t max_iter, int64_t check_every, ctd_minres_info* info, double* schur_ws = nullptr, bool schur_cr = false) {
+    if (const int32_t st = mr_enqueue_start(h, c, sys, rhs_dev, z_dev, rtol, max_iter, schur_ws, schur_cr)) return st;
     for (int64_t done = 0; done < max_iter; done += check_every) {
         if (const int32_t st = mr_enqueue_iters(h, c, sys, check_every)) return st;
         if (const int32_t st = mr_read_info(h, info)) return st;
@@ -1856,6 +1867,133 @@ int32_t ctd_kkt_minres_schur_dev(ctd_handle* h, const ctd_kkt_system* sys, doubl
         (st = mr_check_count(h, c, "check_every", check_every)))
         return st;
     return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info, schur_ws_dev);
+}
+
+// ---- log-depth exact block-tridiagonal Schur preconditioner (plan: ctd_schur_plan.hpp; kernels, sums and workspace:
+// ctd_schur_cr_kernels.hpp): the entry points of the chunked one, with the same checks in the same order ----------------------------
+static int32_t schur_cr_plan(ctd_handle* h, const char* fn, SchurCrPlan& pl) {
+    if (h->step_begin != 0 || h->step_end != h->model.L.N || h->plan.kp.halo)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
+                                   "step_end, ctd_set_x_shards) is refused: the Schur preconditioner has no shard form yet");
+    std::string err;
+    const int st = plan_kkt_schur_cr(h->model, !h->schur_verified, pl, err);
+    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
+    h->schur_verified = true;
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_layout(ctd_handle* h, ctd_schur_cr_layout* out) {
+    const char* fn = "ctd_kkt_schur_cr_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_schur_cr_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_cr_layout) = " +
+                                       std::to_string(sizeof(ctd_schur_cr_layout)));
+    SchurCrPlan pl;
+    if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
+    static_assert(CTD_KKT_SCHUR_CR_WORKSPACE(7, 9) == kSchurFixed + 7 + 3 * 7 * 81 + 2 * 7 * 9, "the workspace of the header");
+    out->reserved = 0;
+    out->N = pl.N;
+    out->block_rows = pl.block_rows;
+    out->tail_rows = pl.tail_rows;
+    out->first_tail_row = pl.first_tail_row;
+    out->tail_cols = pl.tail_cols;
+    out->n_levels = pl.n_levels;
+    out->factor_launches = pl.factor_launches;
+    out->solve_launches = pl.solve_launches;
+    out->workspace = pl.workspace;
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_factor_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev, double* ws_dev) {
+    const char* fn = "ctd_kkt_schur_cr_factor_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrPlan pl;
+    if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
+    if (!jvals_dev || !px_dev || !ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
+    if (ws_dev == jvals_dev || ws_dev == px_dev || ws_dev == sc_dev)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    if (const int32_t st = schur_upload_pattern(h, fn)) return st;
+    const SchurCrFactorParams fp{pl.N, pl.first_tail_col, (int32_t)pl.block_rows, (int32_t)pl.n_levels,
+                                 h->d_schur_rowptr.p, h->d_schur_colind.p, jvals_dev, px_dev, sc_dev, ws_dev};
+    const hipError_t e = schur_cr_factor(fp, h->stream);
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_solve_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev) {
+    const char* fn = "ctd_kkt_schur_cr_solve_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrPlan pl;
+    if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
+    if (!ws_dev || !r_dev || !out_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
+    if (out_dev == r_dev || out_dev == ws_dev || r_dev == ws_dev)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) and the workspace must not be an input buffer");
+    const SchurCrSolveParams sp{pl.N, (int32_t)pl.block_rows, SCHUR_PLAIN, (int32_t)pl.n_levels, 0, ws_dev, r_dev, out_dev, nullptr};
+    const hipError_t e = schur_cr_solve(sp, h->stream);
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block) {
+    const char* fn = "ctd_kkt_schur_cr_info";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrPlan pl;
+    if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
+    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int64_t head[4];
+    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
+    if (head[0] != kSchurCrTag || head[1] != pl.N || head[2] != pl.block_rows || head[3] != pl.n_levels)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle (ctd_kkt_schur_cr_factor_dev_async)");
+    std::vector<int64_t> status((size_t)pl.N);
+    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
+    *first_bad_block = -1;
+    for (int64_t k = 0; k < pl.N; ++k)
+        if (status[(size_t)k] >= 0) {
+            *first_bad_block = k;
+            break;
+        }
+    return CTD_OK;
+}
+
+static constexpr MfOp kMrSchurCrStart = {{"ctd_kkt_minres_schur_cr_start_dev_async", "ctd_kkt_minres_schur_cr_start_dev_async", "ctd_kkt_minres_schur_cr_start_dev_async"},
+                                         JIT_KKT, 0, false, false, false, "sys->x, rhs and z", "z"},
+                      kMrSchurCrDev = {{"ctd_kkt_minres_schur_cr_dev", "ctd_kkt_minres_schur_cr_dev", "ctd_kkt_minres_schur_cr_dev"},
+                                       JIT_KKT, 0, false, false, false, "sys->x, rhs and z", "z"};
+
+int32_t ctd_kkt_minres_schur_cr_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
+                                                double* z_dev, double rtol) {
+    const MfCall c{kMrSchurCrStart, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if (on.st) return on.st;
+    SchurCrPlan pl;
+    if ((st = schur_cr_plan(h, c.fn(), pl))) return st;             // (whole grid, CSR order, the block size)
+    if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
+    if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
+    if ((st = mr_check_rtol(h, c, rtol))) return st;
+    return mr_enqueue_start(h, c, *sys, rhs_dev, z_dev, rtol, INT64_MAX, schur_ws_dev, true);
+}
+
+int32_t ctd_kkt_minres_schur_cr_dev(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev, double* z_dev,
+                                    double rtol, int64_t max_iter, int64_t check_every, ctd_minres_info* info) {
+    const MfCall c{kMrSchurCrDev, MF_DEV};
+    int32_t st;
+    if (!mr_structs_ok(h, c.fn(), sys, true, info, &st)) return st;
+    const OnDevice on(h, c.fn());
+    if (on.st) return on.st;
+    SchurCrPlan pl;
+    if ((st = schur_cr_plan(h, c.fn(), pl))) return st;             // (whole grid, CSR order, the block size)
+    if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
+    if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
+    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c, "check_every", check_every)))
+        return st;
+    return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info, schur_ws_dev, true);
 }
 
 // ---- the solve on a shard of the grid (ownership, slots and summation order: ctd_krylov_shard_kernels.hpp) ------------------------

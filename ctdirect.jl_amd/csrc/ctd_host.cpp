@@ -1317,6 +1317,24 @@ int plan_kkt_schur(const Model& mo, int64_t chunk_steps, bool verify, SchurPlan&
     return ST_OK;
 }
 
+// ... and of its log-depth exact form: the same blocks, tail and refusals; the levels, the launch counts and the workspace
+int plan_kkt_schur_cr(const Model& mo, bool verify, SchurCrPlan& out, std::string& err) {
+    SchurPlan pl;
+    if (const int st = plan_kkt_schur(mo, mo.L.N > 0 ? mo.L.N : 1, verify, pl, err)) return st;
+    out = SchurCrPlan{};
+    out.N = pl.N;
+    out.block_rows = pl.block_rows;
+    out.tail_rows = pl.tail_rows;
+    out.first_tail_row = pl.first_tail_row;
+    out.tail_cols = pl.tail_cols;
+    out.first_tail_col = pl.first_tail_col;
+    out.n_levels = schur_cr_levels(pl.N);
+    out.factor_launches = schur_cr_factor_launches(pl.N);
+    out.solve_launches = schur_cr_solve_launches(pl.N);
+    out.workspace = schur_cr_workspace(pl.N, pl.block_rows);
+    return ST_OK;
+}
+
 int build_model(const HostDesc& d, Model& mo, std::string& err) {
     mo.problem = d.problem;
     mo.pattern_mode = d.pattern_mode;

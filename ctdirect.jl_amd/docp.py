@@ -112,6 +112,8 @@ MinresInfo = namedtuple("MinresInfo", "status iterations phibar Anorm ynorm beta
 # The chunked block-tridiagonal Schur preconditioner of DOCP.kkt_schur_precond: the pair (px, pc) of kkt_diag_precond it was built
 # from, the factor's workspace (a device tensor of layout.workspace doubles) and the layout (ctd_schur_layout)
 SchurPrecond = namedtuple("SchurPrecond", "px pc ws layout")
+# ... and its log-depth exact form of DOCP.kkt_schur_cr_precond (layout: ctd_schur_cr_layout)
+SchurCrPrecond = namedtuple("SchurCrPrecond", "px pc ws layout")
 MinresShardWorkspace = namedtuple("MinresShardWorkspace", "ws layout n_ranks v_x v_c kv_x kv_c send_a send_b gathered_a gathered_b")
 
 
@@ -707,6 +709,68 @@ class DOCP:
         self._ck(_lib.lib().ctd_kkt_schur_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
         return bad.value
 
+    # ---- log-depth exact block-tridiagonal Schur preconditioner (ctd_kkt_schur_cr*) --------------------------------------------------
+    def kkt_schur_cr_layout(self):
+        """`ctd_kkt_schur_cr_layout`: N, block_rows (m), tail_rows, first_tail_row, tail_cols (nv) as `kkt_schur_layout`, then
+        n_levels = ceil(log2 N), factor_launches, solve_launches and the workspace in doubles of the log-depth exact
+        block-tridiagonal Schur preconditioner.  The same checks and refusals; works on host-only handles."""
+        lay = _lib.ctd_schur_cr_layout(struct_size=C.sizeof(_lib.ctd_schur_cr_layout))
+        self._ck(_lib.lib().ctd_kkt_schur_cr_layout(self._h, C.byref(lay)))
+        return lay
+
+    def kkt_schur_cr_precond(self, x, y, obj_weight=1.0, sx=None, sc=None, floor=1e-8, jvals=None):
+        """The exact block-tridiagonal Schur preconditioner of the operator `kktprod`:
+            M^-1 = blkdiag(diag(px), T, diag(pc_tail)),   T = Jt diag(1 / px) Jt' + Sc
+        the matrix of `kkt_schur_precond` with one chunk -- no coupling is dropped and there is no chunk length to choose --
+        factored by block cyclic reduction: ceil(log2 N) levels of parallel block eliminations instead of a sweep over N blocks.
+        Arguments as `kkt_schur_precond`.  Runs the factor (`ctd_kkt_schur_cr_factor_dev_async`) and returns a SchurCrPrecond
+        (px, pc, ws, layout) for `kkt_minres(..., precond=P)`, `kkt_schur_cr_solve` and `kkt_schur_cr_info`.  Device tensors only."""
+        self._tensors_only("kkt_schur_cr_precond", x=x, y=y, sx=sx, sc=sc, jvals=jvals)
+        import torch
+        self._check_x(x)
+        lay = self.kkt_schur_cr_layout()
+        px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc, floor)
+        if jvals is None:
+            _, jvals = self.cons_jac(x)
+        ws = torch.empty(lay.workspace, dtype=torch.float64, device=x.device)
+        return self.kkt_schur_cr_factor(jvals, px, pc, sc, ws)
+
+    def kkt_schur_cr_factor(self, jvals, px, pc, sc, ws):
+        """`ctd_kkt_schur_cr_factor_dev_async` on the caller's tensors (enqueue-only): the factor of T built from jvals, 1 / px and
+        sc (None: zero) into ws (kkt_schur_cr_layout().workspace doubles).  Returns the SchurCrPrecond (px, pc, ws, layout)."""
+        self._tensors_only("kkt_schur_cr_factor", jvals=jvals, px=px, pc=pc, sc=sc, ws=ws)
+        lay = self.kkt_schur_cr_layout()
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        self._ck(_lib.lib().ctd_kkt_schur_cr_factor_dev_async(
+            self._h, self._dev_ptr(jvals, self.nnzj, "jvals"), self._dev_ptr(px, nvar, "px"), self._dev_ptr(sc, ncon, "sc"),
+            self._dev_ptr(ws, lay.workspace, "ws")))
+        self._dev_ptr(pc, ncon, "pc")
+        return SchurCrPrecond(px, pc, ws, lay)
+
+    def kkt_schur_cr_solve(self, P, r, out=None, sync=True):
+        """`ctd_kkt_schur_cr_solve_dev_async`: out = T^-1 r on the block rows (the first layout.first_tail_row entries); the tail
+        rows of out are left untouched (zero in a tensor allocated here).  r, out: ncon entries, out must not be r; the scratch
+        region of P.ws is written."""
+        self._tensors_only("kkt_schur_cr_solve", r=r, out=out, ws=P.ws)
+        ncon = self.dim_NLP_constraints
+        if out is None:
+            import torch
+            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+        self._ck(_lib.lib().ctd_kkt_schur_cr_solve_dev_async(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"),
+                                                            self._dev_ptr(r, ncon, "r"), self._dev_ptr(out, ncon, "out")))
+        if sync:
+            self.sync()
+        return out
+
+    def kkt_schur_cr_info(self, P):
+        """`ctd_kkt_schur_cr_info`: waits for the handle's stream; -1 when every pivot of the factor was positive, otherwise the
+        smallest block (time step) with a pivot that was not positive or not finite (MINRES: "breakdown")."""
+        self._tensors_only("kkt_schur_cr_info", ws=P.ws)
+        bad = C.c_int64(0)
+        self._ck(_lib.lib().ctd_kkt_schur_cr_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
+        return bad.value
+
     # ---- device-resident preconditioned MINRES solve of K z = rhs (ctd_kkt_minres*) ---------------------------------------------
     def _kkt_system(self, fn, vecs, obj_weight, host_ok):
         """The ctd_kkt_system of a solve and the pointers of its other vectors.  vecs: (name, array, layout, required) rows, x
@@ -763,7 +827,8 @@ class DOCP:
         precond: None; a pair (px, pc), M = diag(1 / px, 1 / pc), which must be positive; "diag": the pair of
         `kkt_diag_precond(x, y, obj_weight, sx, sc)`; a SchurPrecond P of `kkt_schur_precond` (device tensors only:
         `ctd_kkt_minres_schur_dev`, one more launch per iteration); or "schur": that of `kkt_schur_precond(x, y, obj_weight, sx,
-        sc)`, one chunk.  max_iter: default 5 (nvar + ncon), scipy's.
+        sc)`, one chunk; a SchurCrPrecond of `kkt_schur_cr_precond` (`ctd_kkt_minres_schur_cr_dev`) or "schur_cr": the same matrix,
+        factored and applied in ceil(log2 N) levels.  max_iter: default 5 (nvar + ncon), scipy's.
         Returns (z, info), info a MinresInfo: status "converged", "max_iter" or "breakdown" (M not positive definite, a NaN, or
         the Krylov space exhausted), the iterations done, phibar, Anorm, ynorm, beta1.  Iterations enqueued after the status was
         set change nothing: z does not depend on check_every.  Results are reproducible bit for bit.  NumPy inputs use the host
@@ -774,14 +839,16 @@ class DOCP:
             raise ValueError(("x" if x is None else "rhs") + " is required")
         schur = None
         if isinstance(precond, str):
-            if precond not in ("diag", "schur"):
-                raise ValueError(f'precond is None, a pair (px, pc), a SchurPrecond, "diag" or "schur", not {precond!r}')
+            if precond not in ("diag", "schur", "schur_cr"):
+                raise ValueError(f'precond is None, a pair (px, pc), a SchurPrecond, a SchurCrPrecond, "diag", "schur" or "schur_cr", not {precond!r}')
             self._check_x(x)
             if precond == "schur":
                 precond = self.kkt_schur_precond(x, y, obj_weight, sx, sc)
+            elif precond == "schur_cr":
+                precond = self.kkt_schur_cr_precond(x, y, obj_weight, sx, sc)
             else:
                 px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc)
-        if isinstance(precond, SchurPrecond):
+        if isinstance(precond, (SchurPrecond, SchurCrPrecond)):
             self._tensors_only("kkt_minres with a Schur preconditioner", x=x, y=y, rhs=rhs, sx=sx, sc=sc, out=out)
             schur, px, pc = precond, precond.px, precond.pc
         elif not isinstance(precond, str):
@@ -798,9 +865,9 @@ class DOCP:
         dev, sys, p, keep = self._kkt_system("kkt_minres", rows, obj_weight, True)
         info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
         if schur is not None:
-            self._ck(L.ctd_kkt_minres_schur_dev(self._h, C.byref(sys), self._dev_ptr(schur.ws, schur.layout.workspace, "ws"), p["rhs"],
-                                                p["out"], float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every),
-                                                C.byref(info)))
+            drive = L.ctd_kkt_minres_schur_cr_dev if isinstance(schur, SchurCrPrecond) else L.ctd_kkt_minres_schur_dev
+            self._ck(drive(self._h, C.byref(sys), self._dev_ptr(schur.ws, schur.layout.workspace, "ws"), p["rhs"],
+                           p["out"], float(rtol), int(5 * n if max_iter is None else max_iter), int(check_every), C.byref(info)))
             return out, self._minres_info(info)
         fn = L.ctd_kkt_minres_dev if dev else L.ctd_kkt_minres
         rhs_p, out_p = (p["rhs"], p["out"]) if dev else (C.cast(p["rhs"], C.POINTER(C.c_double)), C.cast(p["out"], C.POINTER(C.c_double)))
@@ -811,14 +878,17 @@ class DOCP:
     def kkt_minres_start(self, x, y, rhs, z, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10):
         """`ctd_kkt_minres_start_dev_async`: enqueues the initialisation of a solve on the device tensors (z = 0, the state) on the
         handle's stream; precond: None or a pair (px, pc), read now only, or a SchurPrecond
-        (`ctd_kkt_minres_schur_start_dev_async`: its workspace is read by every iteration).  No iteration cap.  See `kkt_minres`."""
-        schur = precond if isinstance(precond, SchurPrecond) else None
+        or SchurCrPrecond (`ctd_kkt_minres_schur_start_dev_async`, `ctd_kkt_minres_schur_cr_start_dev_async`: its workspace is
+        used by every iteration).  No iteration cap.  See `kkt_minres`."""
+        schur = precond if isinstance(precond, (SchurPrecond, SchurCrPrecond)) else None
         px, pc = (None, None) if precond is None else ((precond.px, precond.pc) if schur else precond)
         rows = (("x", x, "v", True), ("y", y, "c", False), ("rhs", rhs, "k", True), ("z", z, "k", True), ("sx", sx, "v", False),
                 ("sc", sc, "c", False), ("px", px, "v", False), ("pc", pc, "c", False))
         _, sys, p, _ = self._kkt_system("kkt_minres_start", rows, obj_weight, False)
         if schur:
-            self._ck(_lib.lib().ctd_kkt_minres_schur_start_dev_async(
+            start = (_lib.lib().ctd_kkt_minres_schur_cr_start_dev_async if isinstance(schur, SchurCrPrecond)
+                     else _lib.lib().ctd_kkt_minres_schur_start_dev_async)
+            self._ck(start(
                 self._h, C.byref(sys), self._dev_ptr(schur.ws, schur.layout.workspace, "ws"), p["rhs"], p["z"], float(rtol)))
             return
         self._ck(_lib.lib().ctd_kkt_minres_start_dev_async(self._h, C.byref(sys), p["rhs"], p["z"], float(rtol)))

@@ -678,6 +678,56 @@ int32_t ctd_kkt_minres_schur_start_dev_async(ctd_handle* h, const ctd_kkt_system
 int32_t ctd_kkt_minres_schur_dev(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
                                  double* z_dev, double rtol, int64_t max_iter, int64_t check_every, ctd_minres_info* info);
 
+/* ---- log-depth exact block-tridiagonal Schur preconditioner of the KKT MINRES solve --------------------------------------------
+ * The matrix of the section above with ONE chunk, T = Jt diag(1 / px) Jt' + Sc on the N blocks of m rows -- no coupling dropped, no
+ * chunk length to choose --, factored and applied by block odd-even (cyclic) reduction: a block Cholesky of T in the
+ * nested-dissection order of the time axis.  n_levels = ceil(log2 N) levels (0 for N = 1) stand in place of a chain of N blocks:
+ * at level l the blocks that are odd multiples of 2^l are eliminated, all of them in parallel, one wave per block.  The number of
+ * launches is a function of N alone: the factor 2 n_levels + 2 (assemble; per level eliminate and update; the root), the solve
+ * solve_launches = 2 n_levels + 1 (per level one launch down, the root, per level one launch up).  Compiled once, strict rounding,
+ * plain stores, no atomics, kernel boundaries are the only synchronisation between workgroups, results reproducible bit for bit:
+ * the recurrences and the order of every sum are stated in csrc/ctd_schur_cr_kernels.hpp.
+ * LAYOUT, refusals and the order of the checks: those of the section above (there is no chunk_steps).
+ * WORKSPACE, caller-owned: CTD_KKT_SCHUR_CR_WORKSPACE(N, m) doubles of device memory: 512 fixed (a header with a tag of its own, the
+ * partial sums of the solve inside MINRES), N status words (one per block), 3 N m^2 for the blocks, 2 N m of scratch for the solve.
+ * A workspace of one family handed to the other's solve is recognised on the device and nothing is stored; the other's info call
+ * returns CTD_EINVAL. */
+#define CTD_KKT_SCHUR_CR_WORKSPACE(N, m) \
+    (CTD_KKT_SCHUR_FIXED + (int64_t)(N) + 3 * (int64_t)(N) * (m) * (m) + 2 * (int64_t)(N) * (m))
+/* struct_size = sizeof(ctd_schur_cr_layout), set by the caller */
+typedef struct ctd_schur_cr_layout {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t N, block_rows, tail_rows, first_tail_row, tail_cols;
+    int64_t n_levels, factor_launches, solve_launches;
+    int64_t workspace;          /* doubles */
+} ctd_schur_cr_layout;
+/* works on host-only handles */
+int32_t ctd_kkt_schur_cr_layout(ctd_handle* h, ctd_schur_cr_layout* out);
+/* Factor, enqueue-only, factor_launches launches.  Arguments as ctd_kkt_schur_factor_dev_async; ws_dev is written in full.  The
+ * pattern upload is shared with the chunked factor: the first factor of either kind on a handle is refused while the stream is
+ * capturing.  A pivot that is not positive or not finite: its column is recorded in the block's status word, the block's factors
+ * are NaN, and the NaN reaches the later levels by ordinary arithmetic: the solve then yields NaN on the block rows. */
+int32_t ctd_kkt_schur_cr_factor_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev,
+                                          double* ws_dev);
+/* out = T^-1 r on the block rows, solve_launches launches; r, out: ncon entries, the tail rows of out are left untouched, r is not
+ * modified; out must not be r.  ws_dev is not const: the solve keeps the running right-hand side and y in its scratch region.  The
+ * factor part of the workspace is only read. */
+int32_t ctd_kkt_schur_cr_solve_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev);
+/* waits for the handle's stream; *first_bad_block = -1 when every pivot was positive, otherwise the smallest block index with a
+ * recorded pivot */
+int32_t ctd_kkt_schur_cr_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block);
+/* ctd_kkt_minres_schur_start_dev_async / ctd_kkt_minres_schur_dev with this preconditioner: the same Krylov kernels; between (B) and
+ * (C) stand the solve_launches launches of the solve and one small launch that writes at most 256 partial sums of r2 . y over the
+ * block rows (workgroup g of G = min(N, 256): the blocks g, g + G, ... in that order), which (C) adds as it adds the chunked
+ * solve's.  In an iteration every one of these launches stores nothing unless the status is running.  The handle remembers which
+ * kind of factor the solve started last carries: ctd_kkt_minres_iters_dev_async and ctd_kkt_minres_info continue it unchanged.
+ * Capturable in a graph after one warm call. */
+int32_t ctd_kkt_minres_schur_cr_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev,
+                                                const double* rhs_dev, double* z_dev, double rtol);
+int32_t ctd_kkt_minres_schur_cr_dev(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
+                                    double* z_dev, double rtol, int64_t max_iter, int64_t check_every, ctd_minres_info* info);
+
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
  * ctd_sharded_handle included), modelled on ctd_grad_shard_dev_async: enqueue-only on the handle's stream, capturable after one

@@ -206,6 +206,9 @@ KRYLOV_KERNELS = ("krylov_init_kernel", "krylov_first_kernel", "krylov_alfa_kern
 
 
 SCHUR_KERNELS = ("schur_assemble_kernel", "schur_factor_kernel", "schur_solve_kernel")
+# the log-depth exact form (csrc/ctd_schur_cr.hip)
+SCHUR_CR_KERNELS = ("schur_cr_assemble_kernel", "schur_cr_eliminate_kernel", "schur_cr_update_kernel", "schur_cr_down_kernel",
+                    "schur_cr_root_kernel", "schur_cr_up_kernel", "schur_cr_dot_kernel")
 
 
 def mangled(stem):
@@ -224,17 +227,19 @@ def krylov_table():
         if re.search(r"ILb1EE", n):
             k["kernel"] += "<SCHUR>"
     assert sorted({k["kernel"].replace("<SCHUR>", "") for k in ks}) == sorted(KRYLOV_KERNELS), ks
-    sch = remarks("ctd_schur", "", SCHUR_KERNELS)
-    for k, n in zip(sch, [n for n in mangled("ctd_schur") if re.search("|".join(SCHUR_KERNELS), n)]):
-        mb = re.search(r"ILi(\d+)EE", n)
-        k["kernel"] += f"<{mb.group(1)}>" if mb else ""
-    ks += sch
+    for stem, kernels in (("ctd_schur", SCHUR_KERNELS), ("ctd_schur_cr", SCHUR_CR_KERNELS)):
+        sch = remarks(stem, "", kernels)
+        for k, n in zip(sch, [n for n in mangled(stem) if re.search("|".join(kernels), n)]):
+            mb = re.search(r"ILi(\d+)EE", n)
+            k["kernel"] += f"<{mb.group(1)}>" if mb else ""
+        ks += sch
     path = os.path.join(ROOT, "profiles", "kkt_minres_resources.md")
     lines = ["# Resources of the MINRES vector kernels (csrc/ctd_krylov.hip)\n\n",
              "From the compiler's remarks for gfx950 (`python profiles/resource_usage.py --krylov`, no GPU needed).  The kernels do not\n"
              "depend on the OCP: one instantiation each, two (`<SCHUR>`: with the block-tridiagonal Schur preconditioner) of the four whose\n"
              "code differs with it; below them the kernels of that preconditioner (csrc/ctd_schur.hip), the factor and the solve per\n"
-             "largest block size.  The script fails if any of them uses scratch.\n\n",
+             "largest block size, and those of its log-depth exact form (csrc/ctd_schur_cr.hip).  The script fails if any of them uses\n"
+             "scratch.\n\n",
              "| kernel | VGPR + AGPR | scratch B/lane | waves/SIMD |\n", "|---|---|---|---|\n"]
     for k in ks:
         assert k["scratch"] == 0, k
