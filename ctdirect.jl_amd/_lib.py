@@ -78,6 +78,17 @@ class ctd_schur_cr_layout(C.Structure):
         "N", "block_rows", "tail_rows", "first_tail_row", "tail_cols", "n_levels", "factor_launches", "solve_launches", "workspace")]
 
 
+# the shard form of that (ctd_kkt_schur_cr_shard_layout): the rank's blocks and the read set of its factor
+class ctd_schur_cr_shard_layout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(nm, C.c_int64) for nm in (
+        "N", "step_begin", "step_end", "n_blocks", "block_rows", "first_row", "tail_rows", "first_tail_row", "tail_cols", "n_levels",
+        "factor_launches", "solve_launches", "workspace", "jvals_begin", "jvals_end", "px_begin", "px_end")]
+
+
+# CTD_KKT_MINRES_SCHUR_SHARD_SLOT: the slot of the sharded solve that carries it
+KKT_MINRES_SCHUR_SHARD_SLOT = KKT_MINRES_SHARD_SLOT + 256 + 16
+
+
 def kkt_schur_cr_workspace(N, m):
     """CTD_KKT_SCHUR_CR_WORKSPACE(N, m)"""
     return KKT_SCHUR_FIXED + N + 3 * N * m * m + 2 * N * m
@@ -191,6 +202,19 @@ SYMBOLS = {
     "ctd_kkt_minres_shard_lanczos_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
     "ctd_kkt_minres_shard_update_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
     "ctd_kkt_minres_shard_info": (C.c_int32, [_vp, _vp, C.c_int32, C.POINTER(ctd_minres_info)]),
+    # the shard form of the log-depth Schur preconditioner, and the phases of the sharded solve that carries it
+    "ctd_kkt_schur_cr_shard_layout": (C.c_int32, [_vp, C.POINTER(ctd_schur_cr_shard_layout)]),
+    "ctd_kkt_schur_cr_shard_factor_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, _vp]),
+    "ctd_kkt_schur_cr_shard_solve_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "ctd_kkt_schur_cr_shard_info": (C.c_int32, [_vp, _vp, _ip]),
+    "ctd_kkt_minres_schur_cr_shard_layout": (C.c_int32, [_vp, C.c_int32, C.POINTER(ctd_minres_shard_layout)]),
+    "ctd_kkt_minres_schur_cr_shard_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, _vp, C.c_int32, C.c_int32,
+                                                                  C.c_double, C.c_int64]),
+    "ctd_kkt_minres_schur_cr_shard_begin_dev_async": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_shard_alfa_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_shard_lanczos_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_shard_update_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_shard_info": (C.c_int32, [_vp, _vp, C.c_int32, C.POINTER(ctd_minres_info)]),
     "ctd_jprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

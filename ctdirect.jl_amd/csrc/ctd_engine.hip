@@ -1874,7 +1874,8 @@ int32_t ctd_kkt_minres_schur_dev(ctd_handle* h, const ctd_kkt_system* sys, doubl
 static int32_t schur_cr_plan(ctd_handle* h, const char* fn, SchurCrPlan& pl) {
     if (h->step_begin != 0 || h->step_end != h->model.L.N || h->plan.kp.halo)
         return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
-                                   "step_end, ctd_set_x_shards) is refused: the Schur preconditioner has no shard form yet");
+                                   "step_end, ctd_set_x_shards) is refused: this entry point has no shard form (the shard form of the "
+                                   "log-depth preconditioner is ctd_kkt_schur_cr_shard_*)");
     std::string err;
     const int st = plan_kkt_schur_cr(h->model, !h->schur_verified, pl, err);
     if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
@@ -2136,6 +2137,270 @@ int32_t ctd_kkt_minres_shard_info(ctd_handle* h, const double* ws_dev, int32_t n
     KrylovState s;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks).pend, sizeof(s), hipMemcpyDeviceToHost));
+    info->status = s.status;
+    info->iterations = s.itn;
+    info->phibar = s.phibar;
+    info->Anorm = s.Anorm;
+    info->ynorm = s.ynorm;
+    info->beta1 = s.beta1;
+    return CTD_OK;
+}
+
+// ---- the shard form of the log-depth exact Schur preconditioner (plan: ctd_schur_plan.hpp; the kernels of the whole-grid form
+// through offset pointers: ctd_schur_cr_kernels.hpp) and of the solve that carries it (ctd_krylov_shard_kernels.hpp) -----------------
+static_assert(kKrylovSchurSlot == CTD_KKT_MINRES_SCHUR_SHARD_SLOT, "the slot length of the header");
+static_assert(kSlotSchurMax == kSchurMaxWg, "a slot has room for the solve's partial sums");
+static_assert(CTD_KKT_MINRES_SCHUR_SHARD_WORKSPACE(10, 3) == kKrylovVectors * 10 + 8 * kKrylovSchurSlot + 96, "the workspace of the header");
+
+// every handle is accepted; the plan's own refusals (CSR order, block_rows, the pattern -- walked once per handle)
+static int32_t schur_crs_plan(ctd_handle* h, const char* fn, bool ranges, SchurCrShardPlan& pl) {
+    std::string err;
+    const int st = plan_kkt_schur_cr_shard(h->model, h->step_begin, h->step_end, !h->schur_verified, ranges, pl, err);
+    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
+    h->schur_verified = true;
+    return CTD_OK;
+}
+// the rank's blocks as the whole-grid problem of n_blocks blocks: the solve's arguments
+static SchurCrShardSolveParams schur_crs_solve_params(const SchurCrShardPlan& pl, int32_t mode, double* ws, const double* r, double* out,
+                                                      const KrylovState* cur, double* part) {
+    SchurCrShardSolveParams sp{};
+    static_cast<SchurCrSolveParams&>(sp) =
+        SchurCrSolveParams{pl.n_blocks, (int32_t)pl.block_rows, mode, (int32_t)pl.n_levels, 0, ws, r + pl.first_row, out + pl.first_row, cur};
+    sp.first = pl.step_begin;
+    sp.part = part;
+    return sp;
+}
+
+int32_t ctd_kkt_schur_cr_shard_layout(ctd_handle* h, ctd_schur_cr_shard_layout* out) {
+    const char* fn = "ctd_kkt_schur_cr_shard_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_schur_cr_shard_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_cr_shard_layout) = " +
+                                       std::to_string(sizeof(ctd_schur_cr_shard_layout)));
+    SchurCrShardPlan pl;
+    if (const int32_t st = schur_crs_plan(h, fn, true, pl)) return st;
+    out->reserved = 0;
+    out->N = pl.N;
+    out->step_begin = pl.step_begin;
+    out->step_end = pl.step_end;
+    out->n_blocks = pl.n_blocks;
+    out->block_rows = pl.block_rows;
+    out->first_row = pl.first_row;
+    out->tail_rows = pl.tail_rows;
+    out->first_tail_row = pl.first_tail_row;
+    out->tail_cols = pl.tail_cols;
+    out->n_levels = pl.n_levels;
+    out->factor_launches = pl.factor_launches;
+    out->solve_launches = pl.solve_launches;
+    out->workspace = pl.workspace;
+    out->jvals_begin = pl.jvals_begin;
+    out->jvals_end = pl.jvals_end;
+    out->px_begin = pl.px_begin;
+    out->px_end = pl.px_end;
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_shard_factor_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev,
+                                                double* ws_dev) {
+    const char* fn = "ctd_kkt_schur_cr_shard_factor_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrShardPlan pl;
+    if (const int32_t st = schur_crs_plan(h, fn, false, pl)) return st;
+    if (!jvals_dev || !px_dev || !ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
+    if (ws_dev == jvals_dev || ws_dev == px_dev || ws_dev == sc_dev)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    if (const int32_t st = schur_upload_pattern(h, fn)) return st;
+    SchurCrShardFactorParams fp{};
+    static_cast<SchurCrFactorParams&>(fp) =
+        SchurCrFactorParams{pl.n_blocks, pl.first_tail_col, (int32_t)pl.block_rows, (int32_t)pl.n_levels, h->d_schur_rowptr.p + pl.first_row,
+                            h->d_schur_colind.p, jvals_dev, px_dev, sc_dev ? sc_dev + pl.first_row : nullptr, ws_dev};
+    fp.first = pl.step_begin;
+    const hipError_t e = schur_cr_factor(fp, h->stream);
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_shard_solve_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev) {
+    const char* fn = "ctd_kkt_schur_cr_shard_solve_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrShardPlan pl;
+    if (const int32_t st = schur_crs_plan(h, fn, false, pl)) return st;
+    if (!ws_dev || !r_dev || !out_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
+    if (out_dev == r_dev || out_dev == ws_dev || r_dev == ws_dev)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) and the workspace must not be an input buffer");
+    const hipError_t e = schur_cr_solve(schur_crs_solve_params(pl, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr), h->stream);
+    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block) {
+    const char* fn = "ctd_kkt_schur_cr_shard_info";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrShardPlan pl;
+    if (const int32_t st = schur_crs_plan(h, fn, false, pl)) return st;
+    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int64_t head[5];
+    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
+    if (head[0] != kSchurCrTag || head[1] != pl.n_blocks || head[2] != pl.block_rows || head[3] != pl.n_levels || head[4] != pl.step_begin)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle's steps (ctd_kkt_schur_cr_shard_factor_dev_async)");
+    std::vector<int64_t> status((size_t)pl.n_blocks);
+    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
+    *first_bad_block = -1;
+    for (int64_t k = 0; k < pl.n_blocks; ++k)
+        if (status[(size_t)k] >= 0) {
+            *first_bad_block = pl.step_begin + k;
+            break;
+        }
+    return CTD_OK;
+}
+
+// The phases of ctd_kkt_minres_shard_* with slots of kKrylovSchurSlot doubles
+static KrylovSchurShardParams mrss_params(const ctd_handle* h, const SchurCrShardPlan& sc, double* ws, double* z, int32_t n_ranks) {
+    const KrylovShardPlan pl = mrs_plan(h);
+    const KrylovOwn own{pl.var_lo, pl.var_hi - pl.var_lo, pl.tail_lo, pl.tail_hi - pl.tail_lo, pl.row_lo, pl.last, n_ranks};
+    KrylovSchurShardParams sp{};
+    static_cast<KrylovShardParams&>(sp) = krylov_shard_params(ws, pl.n, pl.n_own, own, z, kKrylovSchurSlot);
+    sp.s_lo = h->model.L.nvar + sc.first_row;
+    sp.s_hi = sp.s_lo + sc.n_blocks * sc.block_rows;
+    sp.s_nwg = schur_solve_grid(sc.n_blocks);
+    return sp;
+}
+// z (n entries), the workspace and the factor's workspace as ranges: pairwise disjoint (z may be absent)
+static int32_t mrss_check_disjoint(ctd_handle* h, const char* fn, const double* z, const double* ws, const double* schur_ws, int32_t n_ranks,
+                                   const SchurCrShardPlan* pl) {
+    const int64_t n = h->model.L.nvar + h->model.L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurSlot);
+    if (mrs_overlap(z, n, ws, wlen)) return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
+    if (pl && (mrs_overlap(schur_ws, pl->workspace, ws, wlen) || mrs_overlap(schur_ws, pl->workspace, z, n)))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": schur_ws must not overlap z or the workspace");
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_minres_schur_cr_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_minres_shard_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_minres_shard_layout) = " +
+                                       std::to_string(sizeof(ctd_minres_shard_layout)));
+    if (const int32_t st = mrs_check_rank(h, fn, n_ranks, 0, false)) return st;
+    SchurCrShardPlan sp;
+    if (const int32_t st = schur_crs_plan(h, fn, false, sp)) return st;
+    const KrylovShardPlan pl = mrs_plan(h);
+    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks, kKrylovSchurSlot);
+    out->reserved = 0;
+    out->n = pl.n; out->n_ranks = n_ranks;
+    out->var_begin = pl.var_lo; out->var_end = pl.var_hi;
+    out->tail_begin = pl.tail_lo; out->tail_end = pl.tail_hi;
+    out->row_begin = pl.row_lo; out->row_end = pl.row_hi;
+    out->n_own = pl.n_own; out->n_dot = pl.n_dot; out->nwg = pl.nwg; out->chunk = pl.chunk;
+    out->slot = kKrylovSchurSlot;
+    out->off_v = l.v; out->off_kv = l.kv;
+    out->off_send_a = l.send_a; out->off_send_b = l.send_b;
+    out->off_gathered_a = l.gathered_a; out->off_gathered_b = l.gathered_b;
+    out->off_state = l.pend;
+    out->workspace = krylov_shard_workspace(pl.n, n_ranks, kKrylovSchurSlot);
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_minres_schur_cr_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
+                                                      double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank, double rtol,
+                                                      int64_t max_iter) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_start_dev_async";
+    int32_t st;
+    if (!mr_structs_ok(h, fn, sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
+    SchurCrShardPlan pl;
+    if ((st = schur_crs_plan(h, fn, false, pl))) return st;
+    if ((st = mrs_check_ptr(h, fn, "rhs", rhs_dev)) || (st = mrs_check_ptr(h, fn, "z", z_dev)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev)) ||
+        (st = mrs_check_ptr(h, fn, "px", sys->px)) || (st = mrs_check_ptr(h, fn, "pc", sys->pc)) ||
+        (st = mrs_check_ptr(h, fn, "schur_ws", schur_ws_dev)))
+        return st;
+    {   // the inputs as ranges against the output ranges, then the outputs against each other
+        const Layout& L = h->model.L;
+        const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurSlot);
+        const std::pair<const double*, int64_t> ins[] = {{rhs_dev, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
+        for (const auto& in : ins)
+            if (mrs_overlap(in.first, in.second, z_dev, n) || mrs_overlap(in.first, in.second, ws_dev, wlen) ||
+                mrs_overlap(in.first, in.second, schur_ws_dev, pl.workspace))
+                return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (z, ws and schur_ws) must not overlap an input buffer");
+    }
+    if ((st = mrss_check_disjoint(h, fn, z_dev, ws_dev, schur_ws_dev, n_ranks, &pl))) return st;
+    if (!(rtol >= 0.0)) return fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
+    if (max_iter < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": max_iter = " + std::to_string(max_iter) + ", must be at least 1");
+    const KrylovSchurShardParams sp = mrss_params(h, pl, ws_dev, z_dev, n_ranks);
+    const int64_t nvar = h->model.L.nvar;
+    hipError_t e = krylov_schur_shard_start(sp, rhs_dev, sys->px, sys->pc, nvar, rtol, max_iter, h->stream);
+    if (e == hipSuccess)
+        e = schur_cr_solve(schur_crs_solve_params(pl, SCHUR_START, schur_ws_dev, sp.r2 + nvar, sp.y + nvar, sp.cur, sp.send_a + kSlotSchur),
+                           h->stream);
+    return mrs_launched(h, fn, e);
+}
+
+// the prologue of the phases: z, the factor's workspace may be absent
+static int32_t mrss_phase(ctd_handle* h, const char* fn, double* schur_ws, bool with_schur, double* z_dev, bool with_z, double* ws_dev,
+                          int32_t n_ranks, int32_t rank, SchurCrShardPlan& pl) {
+    if (!h) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
+    if ((st = schur_crs_plan(h, fn, false, pl))) return st;
+    if (with_z && (st = mrs_check_ptr(h, fn, "z", z_dev))) return st;
+    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    if (with_schur && (st = mrs_check_ptr(h, fn, "schur_ws", schur_ws))) return st;
+    return mrss_check_disjoint(h, fn, with_z ? z_dev : nullptr, ws_dev, schur_ws, n_ranks, with_schur ? &pl : nullptr);
+}
+int32_t ctd_kkt_minres_schur_cr_shard_begin_dev_async(ctd_handle* h, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_begin_dev_async";
+    SchurCrShardPlan pl;
+    if (const int32_t st = mrss_phase(h, fn, nullptr, false, nullptr, false, ws_dev, n_ranks, rank, pl)) return st;
+    return mrs_launched(h, fn, krylov_schur_shard_begin(mrss_params(h, pl, ws_dev, nullptr, n_ranks), h->stream));
+}
+int32_t ctd_kkt_minres_schur_cr_shard_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_alfa_dev_async";
+    SchurCrShardPlan pl;
+    if (const int32_t st = mrss_phase(h, fn, nullptr, false, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    return mrs_launched(h, fn, krylov_shard_alfa(mrss_params(h, pl, ws_dev, z_dev, n_ranks), h->stream));
+}
+int32_t ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
+                                                        int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_lanczos_dev_async";
+    SchurCrShardPlan pl;
+    if (const int32_t st = mrss_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    const KrylovSchurShardParams sp = mrss_params(h, pl, ws_dev, z_dev, n_ranks);
+    const int64_t nvar = h->model.L.nvar;
+    hipError_t e = krylov_schur_shard_lanczos(sp, h->stream);
+    if (e == hipSuccess)
+        e = schur_cr_solve(schur_crs_solve_params(pl, SCHUR_ITER, schur_ws_dev, sp.r2 + nvar, sp.y + nvar, sp.cur, sp.send_b + kSlotSchur),
+                           h->stream);
+    return mrs_launched(h, fn, e);
+}
+int32_t ctd_kkt_minres_schur_cr_shard_update_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_update_dev_async";
+    SchurCrShardPlan pl;
+    if (const int32_t st = mrss_phase(h, fn, nullptr, false, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    return mrs_launched(h, fn, krylov_schur_shard_update(mrss_params(h, pl, ws_dev, z_dev, n_ranks), h->stream));
+}
+
+int32_t ctd_kkt_minres_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info) {
+    const char* fn = "ctd_kkt_minres_schur_cr_shard_info";
+    if (!h) return CTD_EINVAL;
+    if (!info || info->struct_size != sizeof(ctd_minres_info))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
+                                       std::to_string(sizeof(ctd_minres_info)));
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, 0, false)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    KrylovState s;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks, kKrylovSchurSlot).pend, sizeof(s),
+                         hipMemcpyDeviceToHost));
     info->status = s.status;
     info->iterations = s.itn;
     info->phibar = s.phibar;

@@ -1335,6 +1335,36 @@ int plan_kkt_schur_cr(const Model& mo, bool verify, SchurCrPlan& out, std::strin
     return ST_OK;
 }
 
+// ... and of the shard form of that: the rank's blocks, and on request the read set of its factor from the model's own rows
+int plan_kkt_schur_cr_shard(const Model& mo, int64_t step_begin, int64_t step_end, bool verify, bool ranges, SchurCrShardPlan& out,
+                            std::string& err) {
+    SchurCrPlan g;
+    if (const int st = plan_kkt_schur_cr(mo, verify, g, err)) return st;
+    if (!schur_cr_shard_range_ok(g.N, step_begin, step_end)) {
+        err = "the steps [" + std::to_string(step_begin) + ", " + std::to_string(step_end) + ") are not a range of the " + std::to_string(g.N) +
+              " steps of the grid";
+        return ST_EINVAL;
+    }
+    out = schur_cr_shard_cut(g, step_begin, step_end);
+    if (!ranges) return ST_OK;
+    const int64_t r0 = out.first_row, r1 = step_end * g.block_rows;
+    out.jvals_begin = mo.row_start(r0);
+    out.jvals_end = r1 < mo.L.ncon ? mo.row_start(r1) : mo.nnzj;
+    int64_t lo = -1, hi = -1;
+    std::vector<int64_t> cols;
+    for (int64_t r = r0; r < r1; ++r) {
+        mo.gen_row(r, cols);
+        for (int64_t c : cols) {
+            if (c >= g.first_tail_col) break;        // (columns ascend)
+            if (lo < 0 || c < lo) lo = c;
+            if (c + 1 > hi) hi = c + 1;
+        }
+    }
+    out.px_begin = lo < 0 ? 0 : lo;
+    out.px_end = hi < 0 ? 0 : hi;
+    return ST_OK;
+}
+
 int build_model(const HostDesc& d, Model& mo, std::string& err) {
     mo.problem = d.problem;
     mo.pattern_mode = d.pattern_mode;

@@ -3,6 +3,7 @@
 // Strict rounding like the products (the Makefile compiles this file with -ffp-contract=off): every expression below rounds as
 // the NumPy expression of scipy.sparse.linalg.minres it transcribes.
 #include <cfloat>
+#include <type_traits>
 
 #include "ctd_common.hpp"
 #include "ctd_krylov_kernels.hpp"
@@ -279,38 +280,63 @@ __device__ __forceinline__ int slot_count(const double* slot) {
     const double c = slot[kSlotCount];
     return c >= 0.0 && c <= (double)kKrylovMaxWg ? (int)c : 0;
 }
-// one running sum from 0.0: ranks ascending, within a rank the workgroups ascending; entry j of rows `stride` doubles apart
-__device__ __forceinline__ double gathered_sum(const double* g, int n_ranks, int stride, int j) {
+// P (here and in the kernels below): the kernels' arguments, KrylovShardParams or, for the Schur form (ctd_krylov_shard_kernels.hpp),
+// KrylovSchurShardParams -- slots of kKrylovSchurSlot doubles, y and its term of the inner product left to the solve's launches on the
+// rows [s_lo, s_hi).  The instantiations for KrylovShardParams compile to the code without it
+template <class P> constexpr bool is_schur() { return std::is_same<P, KrylovSchurShardParams>::value; }
+template <class P> constexpr int slot_len() { return is_schur<P>() ? kKrylovSchurSlot : kKrylovSlot; }
+// one running sum from 0.0: ranks ascending, within a rank the workgroups ascending; entry j of rows `stride` doubles apart; SLOT:
+// the doubles of a slot
+template <int SLOT> __device__ __forceinline__ double gathered_sum(const double* g, int n_ranks, int stride, int j) {
     double s = 0.0;
     for (int r = 0; r < n_ranks; ++r) {
-        const double* slot = g + (int64_t)r * kKrylovSlot;
+        const double* slot = g + (int64_t)r * SLOT;
         const int cnt = slot_count(slot);
 #pragma unroll 16
         for (int b = 0; b < cnt; ++b) s += slot[b * stride + j];
     }
     return s;
 }
+// the Schur form: the solves' partial sums of r2 . y added to the running sum s, ranks ascending, within a rank ascending
+__device__ __forceinline__ double gathered_schur_sum(double s, const double* g, int n_ranks) {
+    for (int r = 0; r < n_ranks; ++r) {
+        const double* slot = g + (int64_t)r * kKrylovSchurSlot;
+        const double c = slot[kSlotSchurCount];
+        const int cnt = c >= 0.0 && c <= (double)kSlotSchurMax ? (int)c : 0;
+#pragma unroll 8
+        for (int b = 0; b < cnt; ++b) s += slot[kSlotSchur + b];
+    }
+    return s;
+}
 // kv at tail entry j: the ranks' partial sums in rank order, starting from rank 0's value
-__device__ __forceinline__ double gathered_kv_tail(const double* g, int n_ranks, int j) {
+template <int SLOT> __device__ __forceinline__ double gathered_kv_tail(const double* g, int n_ranks, int j) {
     double s = g[kSlotTail + j];
-    for (int r = 1; r < n_ranks; ++r) s += g[(int64_t)r * kKrylovSlot + kSlotTail + j];
+    for (int r = 1; r < n_ranks; ++r) s += g[(int64_t)r * SLOT + kSlotTail + j];
     return s;
 }
 __device__ __forceinline__ bool own_tail(const KrylovOwn& o, int64_t p) { return p >= o.n_var && p < o.n_var + o.nv; }
 
 // start: the vectors on the owned entries, the meta block, the padding and the counts of both send slots, the partial sums of
 // beta1^2 = rhs . M rhs (the tail terms on the last rank only) into slot A
-__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_init_kernel(const KrylovShardParams sp, const double* rhs, const double* px,
+template <class P>
+__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_init_kernel(const P sp, const double* rhs, const double* px,
                                                                          const double* pc, const int64_t nvar, const double rtol,
                                                                          const int64_t max_iter) {
     __shared__ double wsum[kWaves];
-    const KrylovShardParams& kp = sp;
+    const P& kp = sp;
     const bool precond = px != nullptr;
     if (blockIdx.x == 0) {
         for (int e = threadIdx.x; e < kKrylovSlot; e += kKrylovBlock) {
             const double c = e == kSlotCount ? (double)kp.nwg : 0.0;
             if (e >= kp.nwg) sp.send_a[e] = c;          // (the entries [0, nwg) are this launch's partial sums)
             sp.send_b[e] = c;
+        }
+        if constexpr (is_schur<P>()) {                  // (the solve's launches write their s_nwg partial sums behind this one)
+            for (int e = kSlotSchur + threadIdx.x; e < kKrylovSchurSlot; e += kKrylovBlock) {
+                const double c = e == kSlotSchurCount ? (double)sp.s_nwg : 0.0;
+                sp.send_a[e] = c;
+                sp.send_b[e] = c;
+            }
         }
         if (threadIdx.x == 0) {
             KrylovShardMeta m{};
@@ -331,23 +357,27 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_init_kernel(const K
             kp.minv[i] = m;
             yv = m * r;
         }
+        bool solved = false;                            // y and its term: the solve's launches'
+        if constexpr (is_schur<P>()) solved = i >= sp.s_lo && i < sp.s_hi;
         kp.r1[i] = r;
         kp.r2[i] = r;
-        kp.y[i] = yv;
+        if (!solved) kp.y[i] = yv;
         kp.v[i] = 0.0;
         kp.kv[i] = 0.0;
         kp.w[i] = 0.0;
         kp.w2[i] = 0.0;
         kp.z[i] = 0.0;
-        if (!own_tail(sp.own, p) || sp.own.last) acc += r * yv;
+        if (!solved && (!own_tail(sp.own, p) || sp.own.last)) acc += r * yv;
     }
     block_partial_sums<1, 1>(&acc, wsum, sp.send_a + blockIdx.x);
 }
 
 // begin: beta1 from the gathered slots, the first Lanczos vector v = y / beta1 on the owned entries, both copies of the state
-__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_first_kernel(const KrylovShardParams sp) {
-    const KrylovShardParams& kp = sp;
-    const double b2 = gathered_sum(sp.gathered_a, sp.own.n_ranks, 1, 0);
+template <class P>
+__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_first_kernel(const P sp) {
+    const P& kp = sp;
+    double b2 = gathered_sum<slot_len<P>()>(sp.gathered_a, sp.own.n_ranks, 1, 0);
+    if constexpr (is_schur<P>()) b2 = gathered_schur_sum(b2, sp.gathered_a, sp.own.n_ranks);
     KrylovState t{};
     t.cs = -1.0;
     t.rtol = sp.meta->rtol;
@@ -406,18 +436,19 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_alfa_kernel(const K
 }
 
 // (B)
-__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_lanczos_kernel(const KrylovShardParams sp) {
+template <class P>
+__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_lanczos_kernel(const P sp) {
     __shared__ double wsum[kWaves * 4];
-    const KrylovShardParams& kp = sp;
+    const P& kp = sp;
     const KrylovState s = *kp.cur;
     if (s.status != KRYLOV_RUNNING) return;
     const int n_ranks = sp.own.n_ranks;
     const bool ortho = s.itn >= 1;
     const double c1 = ortho ? s.beta / s.oldb : 0.0;
-    double alfa = gathered_sum(sp.gathered_a, n_ranks, 1, 0);
+    double alfa = gathered_sum<slot_len<P>()>(sp.gathered_a, n_ranks, 1, 0);
     if (n_ranks > 1)
         for (int j = 0; j < (int)sp.own.nv; ++j)
-            alfa += sp.tail_copy[j] * lanczos_y(gathered_kv_tail(sp.gathered_a, n_ranks, j), sp.tail_copy[kKrylovTailMax + j], ortho, c1);
+            alfa += sp.tail_copy[j] * lanczos_y(gathered_kv_tail<slot_len<P>()>(sp.gathered_a, n_ranks, j), sp.tail_copy[kKrylovTailMax + j], ortho, c1);
     if (first_lane()) *kp.alfa = alfa;
     const double c2 = alfa / s.beta;
     const double oldeps = s.epsln, delta = s.cs * s.dbar + s.sn * alfa;
@@ -437,16 +468,18 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_lanczos_kernel(cons
     for (int64_t p = lo + threadIdx.x; p < hi; p += kKrylovBlock) {
         const int64_t i = krylov_own_index(sp.own, p);
         const bool tail = own_tail(sp.own, p);
-        const double kvv = tail ? gathered_kv_tail(sp.gathered_a, n_ranks, (int)(p - sp.own.n_var)) : kv[i];
+        const double kvv = tail ? gathered_kv_tail<slot_len<P>()>(sp.gathered_a, n_ranks, (int)(p - sp.own.n_var)) : kv[i];
         const double r2v = r2[i];
         const double yv = lanczos_y(kvv, r1[i], ortho, c1) - c2 * r2v;
         r1[i] = r2v;
         r2[i] = yv;
         const double my = precond ? minv[i] * yv : yv;
-        y[i] = my;
+        bool solved = false;
+        if constexpr (is_schur<P>()) solved = i >= sp.s_lo && i < sp.s_hi;
+        if (!solved) y[i] = my;
         const double zv = z[i], u = (v[i] - oldeps * w2[i]) - delta * w[i];
         if (!tail || sp.own.last) {
-            acc[0] += yv * my;
+            if (!solved) acc[0] += yv * my;
             acc[1] += zv * zv;
             acc[2] += zv * u;
             acc[3] += u * u;
@@ -456,13 +489,14 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_lanczos_kernel(cons
 }
 
 // (C)
-__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_update_kernel(const KrylovShardParams sp) {
-    const KrylovShardParams& kp = sp;
+template <class P>
+__global__ void __launch_bounds__(kKrylovBlock) krylov_shard_update_kernel(const P sp) {
+    const P& kp = sp;
     const KrylovState s = *kp.cur;
     if (s.status != KRYLOV_RUNNING) return;
     double b2 = 0.0, zz = 0.0, zu = 0.0, uu = 0.0;
     for (int r = 0; r < sp.own.n_ranks; ++r) {
-        const double* slot = sp.gathered_b + (int64_t)r * kKrylovSlot;
+        const double* slot = sp.gathered_b + (int64_t)r * slot_len<P>();
         const int cnt = slot_count(slot);
 #pragma unroll 8
         for (int b = 0; b < cnt; ++b) {
@@ -473,6 +507,7 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_update_kernel(const
             uu += q[3];
         }
     }
+    if constexpr (is_schur<P>()) b2 = gathered_schur_sum(b2, sp.gathered_b, sp.own.n_ranks);
     const double alfa = *kp.alfa;
     KrylovState t = s;
     if (bad_beta2(b2)) {
@@ -532,11 +567,11 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_update_kernel(const
 
 hipError_t krylov_shard_start(const KrylovShardParams& sp, const double* rhs, const double* px, const double* pc, int64_t nvar,
                               double rtol, int64_t max_iter, hipStream_t st) {
-    hipLaunchKernelGGL(krylov_shard_init_kernel, dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp, rhs, px, pc, nvar, rtol, max_iter);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_init_kernel<KrylovShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp, rhs, px, pc, nvar, rtol, max_iter);
     return hipGetLastError();
 }
 hipError_t krylov_shard_begin(const KrylovShardParams& sp, hipStream_t st) {
-    hipLaunchKernelGGL(krylov_shard_first_kernel, dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_first_kernel<KrylovShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
     return hipGetLastError();
 }
 hipError_t krylov_shard_alfa(const KrylovShardParams& sp, hipStream_t st) {
@@ -544,11 +579,30 @@ hipError_t krylov_shard_alfa(const KrylovShardParams& sp, hipStream_t st) {
     return hipGetLastError();
 }
 hipError_t krylov_shard_lanczos(const KrylovShardParams& sp, hipStream_t st) {
-    hipLaunchKernelGGL(krylov_shard_lanczos_kernel, dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_lanczos_kernel<KrylovShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
     return hipGetLastError();
 }
 hipError_t krylov_shard_update(const KrylovShardParams& sp, hipStream_t st) {
-    hipLaunchKernelGGL(krylov_shard_update_kernel, dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_update_kernel<KrylovShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    return hipGetLastError();
+}
+
+hipError_t krylov_schur_shard_start(const KrylovSchurShardParams& sp, const double* rhs, const double* px, const double* pc, int64_t nvar,
+                                    double rtol, int64_t max_iter, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_init_kernel<KrylovSchurShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp,
+                       rhs, px, pc, nvar, rtol, max_iter);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_shard_begin(const KrylovSchurShardParams& sp, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_first_kernel<KrylovSchurShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_shard_lanczos(const KrylovSchurShardParams& sp, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_lanczos_kernel<KrylovSchurShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_shard_update(const KrylovSchurShardParams& sp, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_update_kernel<KrylovSchurShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
     return hipGetLastError();
 }
 

@@ -35,6 +35,18 @@
 //
 // Per iteration: the two launches of kktprod_shard, (A), (B), (C), and three small all-gathers by the caller (the halo of v, slot A,
 // slot B).  No all-reduce, no host synchronisation.
+//
+// THE SCHUR FORM (ctd_kkt_minres_schur_cr_shard_*): M = blkdiag(diag(1 / px), T_0^-1, .., T_{G-1}^-1, diag(1 / pc_tail)), T_r the rank's
+// own block rows factored by ctd_kkt_schur_cr_shard_factor_dev_async (ctd_schur_cr_kernels.hpp).  Both send slots grow to
+// kKrylovSchurSlot doubles: the slot above, then [kSlotSchur, + kSlotSchurMax) the partial sums of r2 . y over the rank's block rows,
+// padded with +0.0, and [kSlotSchurCount] their number G_r = min(N_r, kSlotSchurMax).  The start's init kernel and (B) leave y and
+// the terms of the inner product open on the rows [s_lo, s_hi) of the rank's blocks; the launches of the solve follow in the same
+// phase, the last of which writes the G_r partial sums into the send slot (workgroup g: the local blocks g, g + G_r, ... in that
+// order).  No gather is added: the partial sums travel in the slot.
+// ORDER OF THE CROSS-RANK SUM of beta1^2 and beta^2 in the Schur form, one running sum from 0.0: first the terms above -- ranks
+// ascending, within a rank the workgroups of the init kernel or of (B) ascending --, then the ranks ascending AGAIN, each rank's G_r
+// partial sums of the solve in ascending workgroup order.  With one rank this is the order of the whole-grid (C) with the log-depth
+// preconditioner.  The three other sums of (B), alfa and the tail of K v are as above.  (A) is the kernel above: it reads no slot.
 #pragma once
 #include "ctd_krylov_kernels.hpp"
 
@@ -44,6 +56,11 @@ constexpr int kKrylovTailMax = 16;                               // room for the
 constexpr int kSlotTail = 4 * kKrylovMaxWg;                      // 2048
 constexpr int kSlotCount = kSlotTail + kKrylovTailMax;           // 2064
 constexpr int kKrylovSlot = kSlotCount + 16;                     // 2080 = CTD_KKT_MINRES_SHARD_SLOT
+// the Schur form's slot: the slot above, the solve's partial sums, their count
+constexpr int kSlotSchur = kKrylovSlot;                          // 2080
+constexpr int kSlotSchurMax = 256;                               // = kSchurMaxWg (ctd_schur_kernels.hpp)
+constexpr int kSlotSchurCount = kSlotSchur + kSlotSchurMax;      // 2336
+constexpr int kKrylovSchurSlot = kSlotSchurCount + 16;           // 2352 = CTD_KKT_MINRES_SCHUR_SHARD_SLOT
 
 // what start records for begin and for (B): the handle keeps no per-solve state
 struct KrylovShardMeta { double rtol; int64_t max_iter; int32_t precond, pad; };
@@ -51,16 +68,16 @@ struct KrylovShardMeta { double rtol; int64_t max_iter; int32_t precond, pad; };
 // Offsets (doubles) into the caller's workspace: the eight vectors of n entries (r1, r2, y, v, kv, w, w2, minv), then the slots,
 // then alfa, the tail copies, the meta block and the two states
 struct KrylovShardLayout { int64_t v, kv, send_a, send_b, gathered_a, gathered_b, alfa, tail_copy, meta, cur, pend, total; };
-inline KrylovShardLayout krylov_shard_layout(int64_t n, int64_t n_ranks) {
+inline KrylovShardLayout krylov_shard_layout(int64_t n, int64_t n_ranks, int64_t slot = kKrylovSlot) {
     KrylovShardLayout l{};
     l.v = 3 * n;
     l.kv = 4 * n;
     l.send_a = kKrylovVectors * n;
-    l.send_b = l.send_a + kKrylovSlot;
+    l.send_b = l.send_a + slot;
     // one rank: nothing to gather, the kernels read the send slots
-    l.gathered_a = n_ranks == 1 ? l.send_a : l.send_b + kKrylovSlot;
-    l.gathered_b = n_ranks == 1 ? l.send_b : l.gathered_a + n_ranks * kKrylovSlot;
-    l.alfa = n_ranks == 1 ? l.send_b + kKrylovSlot : l.gathered_b + n_ranks * kKrylovSlot;
+    l.gathered_a = n_ranks == 1 ? l.send_a : l.send_b + slot;
+    l.gathered_b = n_ranks == 1 ? l.send_b : l.gathered_a + n_ranks * slot;
+    l.alfa = n_ranks == 1 ? l.send_b + slot : l.gathered_b + n_ranks * slot;
     l.tail_copy = l.alfa + 16;
     l.meta = l.tail_copy + 2 * kKrylovTailMax;
     l.cur = l.meta + 16;
@@ -69,7 +86,9 @@ inline KrylovShardLayout krylov_shard_layout(int64_t n, int64_t n_ranks) {
     return l;
 }
 // CTD_KKT_MINRES_SHARD_WORKSPACE(n, n_ranks): an upper bound of krylov_shard_layout(n, n_ranks).total that is one formula
-inline int64_t krylov_shard_workspace(int64_t n, int64_t n_ranks) { return kKrylovVectors * n + (2 + 2 * n_ranks) * kKrylovSlot + 96; }
+inline int64_t krylov_shard_workspace(int64_t n, int64_t n_ranks, int64_t slot = kKrylovSlot) {
+    return kKrylovVectors * n + (2 + 2 * n_ranks) * slot + 96;
+}
 
 // the owned ranges as the kernels take them: positions [0, n_var) -> lo + p, [n_var, n_var + nv) -> v_off + .., then row0 + ..
 struct KrylovOwn {
@@ -97,9 +116,10 @@ struct KrylovShardParams {
 };
 
 // the workspace `ws` cut into the kernels' arguments; n: nvar + ncon, n_own: the rank's positions
-inline KrylovShardParams krylov_shard_params(double* ws, int64_t n, int64_t n_own, const KrylovOwn& own, double* z) {
+inline KrylovShardParams krylov_shard_params(double* ws, int64_t n, int64_t n_own, const KrylovOwn& own, double* z,
+                                             int64_t slot = kKrylovSlot) {
     KrylovShardParams sp{};
-    const KrylovShardLayout l = krylov_shard_layout(n, own.n_ranks);
+    const KrylovShardLayout l = krylov_shard_layout(n, own.n_ranks, slot);
     const KrylovGeom g = krylov_geom(n_own);
     sp.n_own = n_own; sp.chunk = g.chunk; sp.nwg = g.nwg;
     double** vec[] = {&sp.r1, &sp.r2, &sp.y, &sp.v, &sp.kv, &sp.w, &sp.w2, &sp.minv};
@@ -126,5 +146,18 @@ hipError_t krylov_shard_begin(const KrylovShardParams& sp, hipStream_t st);
 hipError_t krylov_shard_alfa(const KrylovShardParams& sp, hipStream_t st);
 hipError_t krylov_shard_lanczos(const KrylovShardParams& sp, hipStream_t st);
 hipError_t krylov_shard_update(const KrylovShardParams& sp, hipStream_t st);
+
+// The Schur form: the arguments above cut with slots of kKrylovSchurSlot doubles, and the rows [s_lo, s_hi) of an n-vector that are
+// the rank's block rows, s_nwg the number of partial sums its solve leaves.  New instantiations of the same kernels, one launch
+// each; the caller enqueues the solve's launches behind start and behind lanczos, in the same phase.  (A) is krylov_shard_alfa
+struct KrylovSchurShardParams : KrylovShardParams {
+    int64_t s_lo, s_hi;
+    int32_t s_nwg, s_pad;
+};
+hipError_t krylov_schur_shard_start(const KrylovSchurShardParams& sp, const double* rhs, const double* px, const double* pc, int64_t nvar,
+                                    double rtol, int64_t max_iter, hipStream_t st);
+hipError_t krylov_schur_shard_begin(const KrylovSchurShardParams& sp, hipStream_t st);
+hipError_t krylov_schur_shard_lanczos(const KrylovSchurShardParams& sp, hipStream_t st);
+hipError_t krylov_schur_shard_update(const KrylovSchurShardParams& sp, hipStream_t st);
 
 }  // namespace ctd

@@ -13,6 +13,13 @@ namespace {
 constexpr int kWave = 64;
 constexpr int64_t kCrMaxGrid = 1 << 16;     // cap of a level's workgroup count (grid-stride: it does not enter any result)
 
+// FP / SP (the kernels below): the argument struct, SchurCrFactorParams / SchurCrSolveParams or their shard forms
+// (ctd_schur_cr_kernels.hpp), which add the global index of block 0 -- word 4 of the header -- and the place of the partial sums.
+// The instantiations for the whole-grid structs compile to the code without them
+template <class P> constexpr bool is_shard() {
+    return std::is_same<P, SchurCrShardFactorParams>::value || std::is_same<P, SchurCrShardSolveParams>::value;
+}
+
 // the regions of the workspace
 struct CrWs {
     int64_t* status;
@@ -33,7 +40,7 @@ __device__ __forceinline__ CrWs cr_ws(double* ws, int64_t N, int m) {
 
 // ASSEMBLE: one thread per entry of D_k and E_k (grid-stride), the header, the status words; everything else is zeroed.  The entries
 // are those of the chunked factor's assemble launch with one chunk
-__global__ void __launch_bounds__(256) schur_cr_assemble_kernel(const SchurCrFactorParams fp) {
+template <class FP> __global__ void __launch_bounds__(256) schur_cr_assemble_kernel(const FP fp) {
     const int64_t m = fp.m, mm = m * m, nd = fp.N * mm, total = 2 * nd;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
     int64_t* head = (int64_t*)fp.ws;
@@ -43,6 +50,7 @@ __global__ void __launch_bounds__(256) schur_cr_assemble_kernel(const SchurCrFac
         head[2] = m;
         head[3] = fp.n_levels;
         for (int j = 4; j < kSchurPart; ++j) head[j] = 0;
+        if constexpr (is_shard<FP>()) head[4] = fp.first;
     }
     for (int64_t e = tid; e < kSchurFixed - kSchurPart; e += stride) fp.ws[kSchurPart + e] = 0.0;
     for (int64_t e = tid; e < fp.N; e += stride) head[kSchurFixed + e] = -1;
@@ -82,7 +90,7 @@ __device__ __forceinline__ void fill_nan(double* g, int mm, int lane) {
 }
 
 // ELIMINATE at level h = 2^l (h = 0: the root, block 0 alone, no neighbours): one wave per eliminated block
-template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_eliminate_kernel(const SchurCrFactorParams fp, const int64_t h) {
+template <int MB, class FP> __global__ void __launch_bounds__(kWave) schur_cr_eliminate_kernel(const FP fp, const int64_t h) {
     __shared__ double lds[3 * MB * MB + MB];
     const int lane = threadIdx.x, m = fp.m, mm = m * m;
     double* A = lds;
@@ -154,7 +162,7 @@ template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_eliminate_ke
 }
 
 // UPDATE at level h: one thread per entry of the survivors' D (lower triangle) and of their new couplings
-__global__ void __launch_bounds__(256) schur_cr_update_kernel(const SchurCrFactorParams fp, const int64_t h) {
+template <class FP> __global__ void __launch_bounds__(256) schur_cr_update_kernel(const FP fp, const int64_t h) {
     const int m = fp.m;
     const int64_t mm = (int64_t)m * m, N = fp.N;
     const CrWs w = cr_ws(fp.ws, N, m);
@@ -197,10 +205,12 @@ template <int MB> struct CrLds {
     double L[MB * MB], G[MB * MB], v[MB], dinv[MB];
 };
 
-// uniform: whether this launch stores anything (the header, and in iteration mode the freeze)
-__device__ __forceinline__ bool cr_go(const SchurCrSolveParams& sp) {
+// uniform: whether this launch stores anything (the header -- on a shard the step range too --, and in iteration mode the freeze)
+template <class SP> __device__ __forceinline__ bool cr_go(const SP& sp) {
     const int64_t* head = (const int64_t*)sp.ws;
     if (head[0] != kSchurCrTag || head[1] != sp.N || head[2] != sp.m || head[3] != sp.n_levels) return false;
+    if constexpr (is_shard<SP>())
+        if (head[4] != sp.first) return false;
     return sp.mode != SCHUR_ITER || sp.cur->status == KRYLOV_RUNNING;
 }
 
@@ -243,7 +253,7 @@ template <int MB, bool TR> __device__ __forceinline__ double cr_matvec(CrLds<MB>
 }
 
 // DOWN at level h: one wave per active block
-template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_down_kernel(const SchurCrSolveParams sp, const int64_t h) {
+template <int MB, class SP> __global__ void __launch_bounds__(kWave) schur_cr_down_kernel(const SP sp, const int64_t h) {
     __shared__ CrLds<MB> s;
     if (!cr_go(sp)) return;
     const int lane = threadIdx.x, m = sp.m;
@@ -278,7 +288,7 @@ template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_down_kernel(
 }
 
 // ROOT: x_0 = L_0^-T L_0^-1 rhs_0
-template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_root_kernel(const SchurCrSolveParams sp) {
+template <int MB, class SP> __global__ void __launch_bounds__(kWave) schur_cr_root_kernel(const SP sp) {
     __shared__ CrLds<MB> s;
     if (!cr_go(sp)) return;
     const int lane = threadIdx.x, m = sp.m;
@@ -291,7 +301,7 @@ template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_root_kernel(
 }
 
 // UP at level h: one wave per eliminated block
-template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_up_kernel(const SchurCrSolveParams sp, const int64_t h) {
+template <int MB, class SP> __global__ void __launch_bounds__(kWave) schur_cr_up_kernel(const SP sp, const int64_t h) {
     __shared__ CrLds<MB> s;
     if (!cr_go(sp)) return;
     const int lane = threadIdx.x, m = sp.m;
@@ -311,14 +321,18 @@ template <int MB> __global__ void __launch_bounds__(kWave) schur_cr_up_kernel(co
 }
 
 // the partial sums of r . x over the block rows, one per workgroup
-__global__ void __launch_bounds__(kWave) schur_cr_dot_kernel(const SchurCrSolveParams sp) {
+template <class SP> __global__ void __launch_bounds__(kWave) schur_cr_dot_kernel(const SP sp) {
     if (!cr_go(sp)) return;
     const int lane = threadIdx.x, m = sp.m;
     double acc = 0.0;
     if (lane < m)
         for (int64_t k = blockIdx.x; k < sp.N; k += gridDim.x) acc += sp.r[k * m + lane] * sp.out[k * m + lane];
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
-    if (lane == 0) sp.ws[kSchurPart + blockIdx.x] = acc;
+    if constexpr (is_shard<SP>()) {
+        if (lane == 0) sp.part[blockIdx.x] = acc;
+    } else {
+        if (lane == 0) sp.ws[kSchurPart + blockIdx.x] = acc;
+    }
 }
 
 template <class F> hipError_t for_block_size(int m, F&& f) {
@@ -335,53 +349,65 @@ inline unsigned cr_grid_threads(int64_t entries) { return cr_grid((entries + 255
 
 }  // namespace
 
-hipError_t schur_cr_factor(const SchurCrFactorParams& fp, hipStream_t st) {
+namespace {
+
+template <class FP> hipError_t cr_factor(const FP& fp, hipStream_t st) {
     if (fp.N < 1 || fp.m < 1 || fp.n_levels != schur_cr_levels(fp.N)) return hipErrorInvalidValue;
     const int64_t mm = (int64_t)fp.m * fp.m;
-    hipLaunchKernelGGL(schur_cr_assemble_kernel, dim3(cr_grid_threads(2 * fp.N * mm)), dim3(256), 0, st, fp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_assemble_kernel<FP>), dim3(cr_grid_threads(2 * fp.N * mm)), dim3(256), 0, st, fp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return for_block_size(fp.m, [&](auto mb) {
         constexpr int MB = decltype(mb)::value;
         for (int l = 0; l < fp.n_levels; ++l) {
             const SchurCrLevel lv = schur_cr_level(fp.N, l);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_eliminate_kernel<MB>), dim3(cr_grid(lv.count)), dim3(kWave), 0, st, fp, lv.first);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_eliminate_kernel<MB, FP>), dim3(cr_grid(lv.count)), dim3(kWave), 0, st, fp, lv.first);
             hipError_t le = hipGetLastError();
             if (le != hipSuccess) return le;
             const int64_t survivors = (fp.N + lv.stride - 1) / lv.stride;
-            hipLaunchKernelGGL(schur_cr_update_kernel, dim3(cr_grid_threads(survivors * 2 * mm)), dim3(256), 0, st, fp, lv.first);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_update_kernel<FP>), dim3(cr_grid_threads(survivors * 2 * mm)), dim3(256), 0, st, fp, lv.first);
             le = hipGetLastError();
             if (le != hipSuccess) return le;
         }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_eliminate_kernel<MB>), dim3(1), dim3(kWave), 0, st, fp, (int64_t)0);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_eliminate_kernel<MB, FP>), dim3(1), dim3(kWave), 0, st, fp, (int64_t)0);
         return hipGetLastError();
     });
 }
 
-hipError_t schur_cr_solve(const SchurCrSolveParams& sp, hipStream_t st) {
+template <class SP> hipError_t cr_solve(const SP& sp, hipStream_t st) {
     if (sp.N < 1 || sp.m < 1 || sp.n_levels != schur_cr_levels(sp.N)) return hipErrorInvalidValue;
     const hipError_t e = for_block_size(sp.m, [&](auto mb) {
         constexpr int MB = decltype(mb)::value;
         for (int l = 0; l < sp.n_levels; ++l) {
             const int64_t h = (int64_t)1 << l;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_down_kernel<MB>), dim3(cr_grid((sp.N + h - 1) / h)), dim3(kWave), 0, st, sp, h);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_down_kernel<MB, SP>), dim3(cr_grid((sp.N + h - 1) / h)), dim3(kWave), 0, st, sp, h);
             const hipError_t le = hipGetLastError();
             if (le != hipSuccess) return le;
         }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_root_kernel<MB>), dim3(1), dim3(kWave), 0, st, sp);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_root_kernel<MB, SP>), dim3(1), dim3(kWave), 0, st, sp);
         hipError_t le = hipGetLastError();
         if (le != hipSuccess) return le;
         for (int l = sp.n_levels - 1; l >= 0; --l) {
             const SchurCrLevel lv = schur_cr_level(sp.N, l);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_up_kernel<MB>), dim3(cr_grid(lv.count)), dim3(kWave), 0, st, sp, lv.first);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_up_kernel<MB, SP>), dim3(cr_grid(lv.count)), dim3(kWave), 0, st, sp, lv.first);
             le = hipGetLastError();
             if (le != hipSuccess) return le;
         }
         return hipSuccess;
     });
     if (e != hipSuccess || sp.mode == SCHUR_PLAIN) return e;
-    hipLaunchKernelGGL(schur_cr_dot_kernel, dim3((unsigned)schur_solve_grid(sp.N)), dim3(kWave), 0, st, sp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(schur_cr_dot_kernel<SP>), dim3((unsigned)schur_solve_grid(sp.N)), dim3(kWave), 0, st, sp);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t schur_cr_factor(const SchurCrFactorParams& fp, hipStream_t st) { return cr_factor(fp, st); }
+hipError_t schur_cr_solve(const SchurCrSolveParams& sp, hipStream_t st) { return cr_solve(sp, st); }
+hipError_t schur_cr_factor(const SchurCrShardFactorParams& fp, hipStream_t st) { return cr_factor(fp, st); }
+hipError_t schur_cr_solve(const SchurCrShardSolveParams& sp, hipStream_t st) {
+    if (sp.mode != SCHUR_PLAIN && !sp.part) return hipErrorInvalidValue;
+    return cr_solve(sp, st);
 }
 
 }  // namespace ctd

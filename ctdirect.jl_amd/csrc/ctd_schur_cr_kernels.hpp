@@ -48,6 +48,14 @@
 // the solve writes the scratch (and the partial sums) only.  The solve checks the header against its own N and m and stores
 // nothing when it does not match; in iteration mode every launch stores nothing unless cur->status is KRYLOV_RUNNING.
 // Kernel boundaries are the only synchronisation between workgroups; plain C++ stores only.
+//
+// THE SHARD FORM (ctd_kkt_schur_cr_shard_*).  A rank's T_r -- the principal submatrix of T on its blocks [sb, se) -- is the whole-grid
+// problem of N_r = se - sb blocks seen through offset pointers: the launchers are given rowptr + sb m (its entries stay absolute
+// indices into colind and jvals), sc + sb m, r + sb m and out + sb m, N_r in place of N, and px indexed by global column.  The last
+// local block has no coupling, so T(se, se - 1) is dropped.  The same kernels run, instantiated a second time for argument structs
+// with two more fields (the whole-grid instantiations keep their instructions): `first` = sb goes into word 4 of the header (0 on
+// the whole grid, as that word has always been) and is checked by every launch of the shard's solve like N, m and n_levels; `part`
+// says where the partial sums of r . x go (the whole grid: the workspace's own, [16, 16 + kSchurMaxWg)).
 #pragma once
 #include <cstdint>
 
@@ -68,6 +76,10 @@ struct SchurCrFactorParams {
     const double *jvals, *px, *sc;          // sc may be null
     double* ws;
 };
+// ... of a shard: `first`, the global index of block 0 (the shard's step_begin), goes into word 4 of the header
+struct SchurCrShardFactorParams : SchurCrFactorParams {
+    int64_t first;
+};
 
 // mode: SchurSolveMode of ctd_schur_kernels.hpp
 struct SchurCrSolveParams {
@@ -78,9 +90,17 @@ struct SchurCrSolveParams {
     double* out;
     const KrylovState* cur;
 };
+// ... of a shard: `first` as above, checked against the header; part: where the partial sums of r . x go (modes other than
+// SCHUR_PLAIN)
+struct SchurCrShardSolveParams : SchurCrSolveParams {
+    int64_t first;
+    double* part;
+};
 
 // Launchers (ctd_schur_cr.hip), enqueue-only on `st`
 hipError_t schur_cr_factor(const SchurCrFactorParams& fp, hipStream_t st);
 hipError_t schur_cr_solve(const SchurCrSolveParams& sp, hipStream_t st);       // modes other than SCHUR_PLAIN: the partial sums too
+hipError_t schur_cr_factor(const SchurCrShardFactorParams& fp, hipStream_t st);
+hipError_t schur_cr_solve(const SchurCrShardSolveParams& sp, hipStream_t st);
 
 }  // namespace ctd

@@ -63,4 +63,41 @@ struct SchurCrPlan {
 // The refusals and the pattern check of plan_kkt_schur (one chunk), then the fields above
 int plan_kkt_schur_cr(const Model& m, bool verify, SchurCrPlan& out, std::string& err);
 
+// ---- the shard form of the log-depth exact form (ctd_kkt_schur_cr_shard_*) ------------------------------------------------------------
+// A rank holds the steps [step_begin, step_end): its matrix T_r is the principal submatrix of T on those n_blocks blocks, factored
+// and applied by the recurrences above with the block index taken relative to step_begin and n_blocks in place of N (the coupling
+// T(step_end, step_end - 1) to the next rank's first block is dropped).  first_row = step_begin block_rows.  The tail fields are the
+// grid's.  The read set of the factor, half-open: [jvals_begin, jvals_end) the CSR range of the rank's block rows; [px_begin, px_end)
+// the span of the non-tail columns of those rows (filled when `ranges` is set: a walk of the rank's rows)
+struct SchurCrShardPlan {
+    int64_t N, step_begin, step_end, n_blocks, block_rows, first_row, tail_rows, first_tail_row, tail_cols, first_tail_col, n_levels,
+        factor_launches, solve_launches, workspace, jvals_begin, jvals_end, px_begin, px_end;
+};
+// the step range as a plan takes it: 0 <= step_begin < step_end <= N
+inline bool schur_cr_shard_range_ok(int64_t N, int64_t step_begin, int64_t step_end) {
+    return step_begin >= 0 && step_begin < step_end && step_end <= N;
+}
+// the fields that are functions of the grid's plan and the step range alone (no model): everything but the read set
+inline SchurCrShardPlan schur_cr_shard_cut(const SchurCrPlan& g, int64_t step_begin, int64_t step_end) {
+    SchurCrShardPlan s{};
+    s.N = g.N;
+    s.step_begin = step_begin;
+    s.step_end = step_end;
+    s.n_blocks = step_end - step_begin;
+    s.block_rows = g.block_rows;
+    s.first_row = step_begin * g.block_rows;
+    s.tail_rows = g.tail_rows;
+    s.first_tail_row = g.first_tail_row;
+    s.tail_cols = g.tail_cols;
+    s.first_tail_col = g.first_tail_col;
+    s.n_levels = schur_cr_levels(s.n_blocks);
+    s.factor_launches = schur_cr_factor_launches(s.n_blocks);
+    s.solve_launches = schur_cr_solve_launches(s.n_blocks);
+    s.workspace = schur_cr_workspace(s.n_blocks, g.block_rows);
+    return s;
+}
+// The refusals and the pattern check of plan_kkt_schur_cr, a step range that is not inside the grid (ST_EINVAL), then the fields
+int plan_kkt_schur_cr_shard(const Model& m, int64_t step_begin, int64_t step_end, bool verify, bool ranges, SchurCrShardPlan& out,
+                            std::string& err);
+
 }  // namespace ctd

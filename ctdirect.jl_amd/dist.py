@@ -34,6 +34,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .docp import SchurCrShardPrecond
+
 # Rehearsal knob: run the collectives on a ONE-rank group too (they are no-ops for the data, but every RCCL call of the
 # multi-GPU path -- in-place / padded all-gather, halo all-gather, all-reduce, broadcast -- is issued exactly as on 8 GPUs),
 # so the one-GPU box can exercise the real backend
@@ -183,13 +185,21 @@ class MinresPhases:
 
     def __init__(self, ranks, halo, gather):
         self.ranks, self.halo, self.gather = ranks, halo, gather
+        # a SchurCrShardPrecond per rank: the phase family ctd_kkt_minres_schur_cr_shard_* on workspaces with the larger slots --
+        # the same phases, the same gathers; on every rank or on none
+        self.schur = isinstance(ranks[0].precond, SchurCrShardPrecond)
+        if any(isinstance(r.precond, SchurCrShardPrecond) != self.schur for r in ranks):
+            raise ValueError("precond: a SchurCrShardPrecond on every shard or on none")
 
     def start(self, rtol, max_iter):
         for r in self.ranks:
-            r.docp.kkt_minres_shard_start(r.rhs, r.z, r.w, r.rank, precond=r.precond, rtol=rtol, max_iter=max_iter)
+            if self.schur:
+                r.docp.kkt_minres_schur_shard_start(r.precond, r.rhs, r.z, r.w, r.rank, rtol=rtol, max_iter=max_iter)
+            else:
+                r.docp.kkt_minres_shard_start(r.rhs, r.z, r.w, r.rank, precond=r.precond, rtol=rtol, max_iter=max_iter)
         self.gather("a")
         for r in self.ranks:
-            r.docp.kkt_minres_shard_begin(r.w, r.rank)
+            (r.docp.kkt_minres_schur_shard_begin if self.schur else r.docp.kkt_minres_shard_begin)(r.w, r.rank)
 
     def iterate(self, k):
         """k iterations: per iteration the halo of v, K v (two launches per rank), (A), the gather of slot A, (B), the gather of
@@ -198,17 +208,20 @@ class MinresPhases:
             self.halo()
             for r in self.ranks:
                 r.docp.kktprod_shard(r.x, r.y, r.w.v_x, r.w.v_c, r.sigma, r.sx, r.sc, out=(r.w.kv_x, r.w.kv_c))
-                r.docp.kkt_minres_shard_alfa(r.z, r.w, r.rank)
+                (r.docp.kkt_minres_schur_shard_alfa if self.schur else r.docp.kkt_minres_shard_alfa)(r.z, r.w, r.rank)
             self.gather("a")
             for r in self.ranks:
-                r.docp.kkt_minres_shard_lanczos(r.z, r.w, r.rank)
+                if self.schur:
+                    r.docp.kkt_minres_schur_shard_lanczos(r.precond, r.z, r.w, r.rank)
+                else:
+                    r.docp.kkt_minres_shard_lanczos(r.z, r.w, r.rank)
             self.gather("b")
             for r in self.ranks:
-                r.docp.kkt_minres_shard_update(r.z, r.w, r.rank)
+                (r.docp.kkt_minres_schur_shard_update if self.schur else r.docp.kkt_minres_shard_update)(r.z, r.w, r.rank)
 
     def infos(self):
         """every rank's MinresInfo: the one host read per chunk"""
-        return [r.docp.kkt_minres_shard_info(r.w) for r in self.ranks]
+        return [(r.docp.kkt_minres_schur_shard_info if self.schur else r.docp.kkt_minres_shard_info)(r.w) for r in self.ranks]
 
     def solve(self, rtol, max_iter, check_every, on_chunk=None):
         """start, then chunks of check_every iterations with one read of the state between chunks.  Every rank's state has the
@@ -247,7 +260,9 @@ def minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond
     """The MinresPhases of a solve whose shards are ALL in this process: `handles` are the shard handles of one transcription in
     ascending order of their steps (one whole-grid handle: the single shard), on one GPU and one stream (torch's current one).
     xs: one x per handle (a shard's own entries and the halo it reads valid, or the table of `set_x_shards` set); y, rhs, sx, sc:
-    full-length tensors shared by the shards, or one per shard (a list); precond: None, a pair (px, pc) or one pair per shard.
+    full-length tensors shared by the shards, or one per shard (a list); precond: None, a pair (px, pc), one pair per shard, or one
+    SchurCrShardPrecond per shard (`DOCP.kkt_schur_cr_shard_factor`: the log-depth Schur preconditioner, exact inside a shard and cut
+    at the shard boundaries; the workspaces are then those of `DOCP.kkt_minres_schur_shard_workspace`).
     out / workspaces: one z / one MinresShardWorkspace per shard, allocated when None.  The gathers are device copies of every
     send slot into every shard's gathered area; the halo of the Lanczos vector is copied from the owners' vectors."""
     G = len(handles)
@@ -260,7 +275,8 @@ def minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond
     for k, h in enumerate(handles):
         if h._stream_raw != cur:
             h.set_stream(cur)
-        w = workspaces[k] if workspaces is not None else h.kkt_minres_shard_workspace(G)
+        new_ws = h.kkt_minres_schur_shard_workspace if isinstance(pres[k], SchurCrShardPrecond) else h.kkt_minres_shard_workspace
+        w = workspaces[k] if workspaces is not None else new_ws(G)
         z = out[k] if out is not None else torch.empty(w.layout.n, dtype=torch.float64, device=dev)
         ranks.append(_MinresRank(h, k, w, z, xs[k], ys[k], obj_weight, sxs[k], scs[k], rhss[k], pres[k]))
     if G == 1:
@@ -331,6 +347,7 @@ class ShardedDOCP:
         self._vv = None
         self._f = None
         self._minres_ws = None              # the workspace of `kkt_minres`, kept between solves
+        self._minres_schur_ws = None        # ... and of its solves with a SchurCrShardPrecond (larger slots)
         self._peer = None                   # data_ptr of the x buffer the peer table is ACTIVE for (enable_peer_x), None: off
         self._peer_tables = {}              # x data_ptr -> (the tensor itself, mapped pointers of the other ranks' buffers): the
                                             # tensor is kept alive so the allocator cannot hand its address to another buffer
@@ -837,12 +854,31 @@ class ShardedDOCP:
             pc[r0:r1] += sc[r0:r1]
         return px, pc
 
+    def kkt_schur_cr_precond(self, x, y, obj_weight=1.0, sx=None, sc=None, floor=1e-8, jvals=None, x_halo_valid=False,
+                             y_halo_valid=False):
+        """`DOCP.kkt_schur_cr_precond` of the sharded transcription: the log-depth Schur preconditioner, exact inside this rank's
+        steps and cut at the rank boundaries -- M^-1 = blkdiag(diag(px), T_0, ..., T_{G-1}, diag(pc_tail)), T_r the principal
+        submatrix of T = Jt diag(1 / px) Jt' + Sc on rank r's blocks; each of the G - 1 cuts drops one coupling block.  Built from
+        this rank's own Jacobian values on a CSR handle (`jvals`: full-length, this rank's rows valid; None: evaluated here),
+        `kkt_diag_precond` and ONE halo exchange of px (`exchange_product_halo`: the next rank's first node); the factor needs no
+        collective.  Returns the SchurCrShardPrecond for `kkt_minres(precond=P)`.  Inputs as `kkt_diag_precond`."""
+        d = self.docp
+        px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc, floor, x_halo_valid, y_halo_valid)
+        self.exchange_product_halo(px)
+        if jvals is None:
+            jvals = torch.empty(d.nnzj, dtype=torch.float64, device=x.device)
+            c = torch.empty(d.dim_NLP_constraints, dtype=torch.float64, device=x.device)
+            self.cons_jac(x, c, jvals, stitch=False)
+        return d.kkt_schur_cr_shard_factor(jvals, px, pc, sc)
+
     def kkt_minres(self, x, y, rhs, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10, max_iter=None, check_every=16,
                    out=None, x_halo_valid=False, y_halo_valid=False):
         """`DOCP.kkt_minres` of the sharded transcription: preconditioned MINRES on K z = rhs with K the operator of `kktprod`,
         device-resident, every rank working on its own entries of the Krylov vectors (`ctd_kkt_minres_shard_*`).  Every tensor
         is full-length with this rank's own entries valid (x, rhs, px: + the nv tail; sx: the nv tail on the last rank only; y, sx,
-        sc may be None).  precond: None, a pair (px, pc), or "diag": the pair of `kkt_diag_precond`.  Returns (z, MinresInfo): z
+        sc may be None).  precond: None, a pair (px, pc), or "diag": the pair of `kkt_diag_precond`; a SchurCrShardPrecond P of
+        `kkt_schur_cr_precond`, or "schur_cr": that of `kkt_schur_cr_precond(x, y, obj_weight, sx, sc)` (the phases
+        `ctd_kkt_minres_schur_cr_shard_*`: the same three gathers on larger slots, no collective added).  Returns (z, MinresInfo): z
         full-length, this rank's own entries and the nv tail valid (`out`: z).
         The halos of x and y are exchanged once before the loop (`x_halo_valid`, `y_halo_valid`: as in `kktprod`).  Per iteration:
         the halo of the Lanczos vector (`exchange_kkt_halo`), the two launches of `kktprod_shard`, three vector launches and two
@@ -860,13 +896,19 @@ class ShardedDOCP:
         if y is not None and not y_halo_valid:
             self.exchange_product_rows(y)
         if isinstance(precond, str):
-            if precond != "diag":
-                raise ValueError(f'precond is None, a pair (px, pc) or "diag", not {precond!r}')
-            precond = self.kkt_diag_precond(x, y, obj_weight, sx, sc, x_halo_valid=True, y_halo_valid=True)
+            if precond not in ("diag", "schur_cr"):
+                raise ValueError(f'precond is None, a pair (px, pc), a SchurCrShardPrecond, "diag" or "schur_cr", not {precond!r}')
+            build = self.kkt_diag_precond if precond == "diag" else self.kkt_schur_cr_precond
+            precond = build(x, y, obj_weight, sx, sc, x_halo_valid=True, y_halo_valid=True)
         collective = self.world > 1 or _FORCE
-        w = self._minres_ws
-        if w is None or w.ws.device != x.device:
-            w = self._minres_ws = d.kkt_minres_shard_workspace(self.world)
+        if isinstance(precond, SchurCrShardPrecond):
+            w = self._minres_schur_ws
+            if w is None or w.ws.device != x.device:
+                w = self._minres_schur_ws = d.kkt_minres_schur_shard_workspace(self.world)
+        else:
+            w = self._minres_ws
+            if w is None or w.ws.device != x.device:
+                w = self._minres_ws = d.kkt_minres_shard_workspace(self.world)
         z = torch.empty(n, dtype=torch.float64, device=x.device) if out is None else out
 
         def gather(which):

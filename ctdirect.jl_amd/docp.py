@@ -114,6 +114,9 @@ MinresInfo = namedtuple("MinresInfo", "status iterations phibar Anorm ynorm beta
 SchurPrecond = namedtuple("SchurPrecond", "px pc ws layout")
 # ... and its log-depth exact form of DOCP.kkt_schur_cr_precond (layout: ctd_schur_cr_layout)
 SchurCrPrecond = namedtuple("SchurCrPrecond", "px pc ws layout")
+# ... and the shard form of that, of DOCP.kkt_schur_cr_shard_factor: the factor of the handle's own steps (layout:
+# ctd_schur_cr_shard_layout); px, pc full-length, valid where the shard reads them
+SchurCrShardPrecond = namedtuple("SchurCrShardPrecond", "px pc ws layout")
 MinresShardWorkspace = namedtuple("MinresShardWorkspace", "ws layout n_ranks v_x v_c kv_x kv_c send_a send_b gathered_a gathered_b")
 
 
@@ -272,6 +275,7 @@ class DOCP:
         if st != _lib.CTD_OK:
             _raise(st, L.ctd_last_error(None).decode())
         self._h = h
+        self._schur_cr_shard_layout = None      # kkt_schur_cr_shard_layout's answer, kept: the handle's steps never change
         self.device = int(device)
         self._load_static()
         if d.pattern_mode == 0 and self.dropped_nonzeros() > 0:
@@ -771,6 +775,59 @@ class DOCP:
         self._ck(_lib.lib().ctd_kkt_schur_cr_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
         return bad.value
 
+    # ---- the shard form of the log-depth Schur preconditioner (ctd_kkt_schur_cr_shard_*) ---------------------------------------------
+    def kkt_schur_cr_shard_layout(self):
+        """`ctd_kkt_schur_cr_shard_layout`: the handle's steps [step_begin, step_end) as the n_blocks blocks of T_r -- the principal
+        submatrix of T of `kkt_schur_cr_precond` on those blocks --, first_row, n_levels = ceil(log2 n_blocks), the launch counts,
+        the workspace in doubles, and the read set of the factor: jvals on [jvals_begin, jvals_end), px on [px_begin, px_end).  The
+        tail fields are the grid's.  Every handle is accepted (a whole-grid handle is the single shard); works on host-only
+        handles."""
+        if self._schur_cr_shard_layout is None:     # (the read set is a walk of the rank's rows on the host: once per handle,
+            lay = _lib.ctd_schur_cr_shard_layout(struct_size=C.sizeof(_lib.ctd_schur_cr_shard_layout))      # whose steps never change)
+            self._ck(_lib.lib().ctd_kkt_schur_cr_shard_layout(self._h, C.byref(lay)))
+            self._schur_cr_shard_layout = lay
+        return _lib.ctd_schur_cr_shard_layout.from_buffer_copy(self._schur_cr_shard_layout)      # (a copy: the caller's to keep)
+
+    def kkt_schur_cr_shard_factor(self, jvals, px, pc, sc, ws=None):
+        """`ctd_kkt_schur_cr_shard_factor_dev_async` (enqueue-only): the factor of T_r from jvals, 1 / px and sc (None: zero), read on
+        the ranges the layout names, into ws (layout.workspace doubles, allocated when None).  All buffers are full-length with
+        global indexing.  Returns the SchurCrShardPrecond (px, pc, ws, layout) for `kkt_schur_cr_shard_solve`, `_info` and the
+        sharded solves (`dist.kkt_minres_shards`, `ShardedDOCP.kkt_minres`)."""
+        self._tensors_only("kkt_schur_cr_shard_factor", jvals=jvals, px=px, pc=pc, sc=sc, ws=ws)
+        lay = self.kkt_schur_cr_shard_layout()
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        if ws is None:
+            import torch
+            ws = torch.empty(lay.workspace, dtype=torch.float64, device=px.device)
+        self._dev_ptr(pc, ncon, "pc")           # (not the factor's, but the solve's that will carry it: checked before anything is enqueued)
+        self._ck(_lib.lib().ctd_kkt_schur_cr_shard_factor_dev_async(
+            self._h, self._dev_ptr(jvals, self.nnzj, "jvals"), self._dev_ptr(px, nvar, "px"), self._dev_ptr(sc, ncon, "sc"),
+            self._dev_ptr(ws, lay.workspace, "ws")))
+        return SchurCrShardPrecond(px, pc, ws, lay)
+
+    def kkt_schur_cr_shard_solve(self, P, r, out=None, sync=True):
+        """`ctd_kkt_schur_cr_shard_solve_dev_async`: out = T_r^-1 r on the handle's block rows [first_row, first_row + n_blocks
+        block_rows); nothing else of out is written (zero in a tensor allocated here).  r, out: ncon entries, out must not be r."""
+        self._tensors_only("kkt_schur_cr_shard_solve", r=r, out=out, ws=P.ws)
+        ncon = self.dim_NLP_constraints
+        if out is None:
+            import torch
+            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+        self._ck(_lib.lib().ctd_kkt_schur_cr_shard_solve_dev_async(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"),
+                                                                  self._dev_ptr(r, ncon, "r"), self._dev_ptr(out, ncon, "out")))
+        if sync:
+            self.sync()
+        return out
+
+    def kkt_schur_cr_shard_info(self, P):
+        """`ctd_kkt_schur_cr_shard_info`: waits for the handle's stream; -1 when every pivot of the factor was positive, otherwise
+        the smallest GLOBAL block (time step) of the handle's range with a pivot that was not positive or not finite."""
+        self._tensors_only("kkt_schur_cr_shard_info", ws=P.ws)
+        bad = C.c_int64(0)
+        self._ck(_lib.lib().ctd_kkt_schur_cr_shard_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
+        return bad.value
+
     # ---- device-resident preconditioned MINRES solve of K z = rhs (ctd_kkt_minres*) ---------------------------------------------
     def _kkt_system(self, fn, vecs, obj_weight, host_ok):
         """The ctd_kkt_system of a solve and the pointers of its other vectors.  vecs: (name, array, layout, required) rows, x
@@ -921,8 +978,10 @@ class DOCP:
         named views of it -- v_x, v_c (the Lanczos vector the operator is applied to), kv_x, kv_c (where `kktprod_shard` puts K v),
         send_a, send_b (this rank's slots) and gathered_a, gathered_b (n_ranks slots each, rank-major: what the all-gathers
         fill; with one rank they are the send slots)."""
+        return self._shard_workspace(self.kkt_minres_shard_layout(n_ranks), n_ranks, ws)
+
+    def _shard_workspace(self, lay, n_ranks, ws):
         import torch
-        lay = self.kkt_minres_shard_layout(n_ranks)
         if ws is None:
             ws = torch.zeros(lay.workspace, dtype=torch.float64, device=torch.device("cuda", self.device))
         self._dev_ptr(ws, lay.workspace, "ws")
@@ -975,6 +1034,58 @@ class DOCP:
         """`ctd_kkt_minres_shard_info`: waits for the handle's stream and returns the MinresInfo in the workspace's state."""
         info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
         self._ck(_lib.lib().ctd_kkt_minres_shard_info(self._h, self._shard_ws_ptr(w), w.n_ranks, C.byref(info)))
+        return self._minres_info(info)
+
+    # ---- ... with the shard form of the log-depth Schur preconditioner (ctd_kkt_minres_schur_cr_shard_*): the same phases on
+    # larger slots; P is the SchurCrShardPrecond of this handle ------------------------------------------------------------------
+    def kkt_minres_schur_shard_layout(self, n_ranks):
+        """`ctd_kkt_minres_schur_cr_shard_layout`: `kkt_minres_shard_layout` with slots of CTD_KKT_MINRES_SCHUR_SHARD_SLOT doubles."""
+        lay = _lib.ctd_minres_shard_layout(struct_size=C.sizeof(_lib.ctd_minres_shard_layout))
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_layout(self._h, int(n_ranks), C.byref(lay)))
+        return lay
+
+    def kkt_minres_schur_shard_workspace(self, n_ranks, ws=None):
+        """`kkt_minres_shard_workspace` for the solve with a SchurCrShardPrecond: the same views, cut with the larger slots."""
+        return self._shard_workspace(self.kkt_minres_schur_shard_layout(n_ranks), n_ranks, ws)
+
+    def _schur_ws_ptr(self, P):
+        return self._dev_ptr(P.ws, P.layout.workspace, "schur_ws")
+
+    def kkt_minres_schur_shard_start(self, P, rhs, z, w, rank, rtol=1e-10, max_iter=None):
+        """`ctd_kkt_minres_schur_cr_shard_start_dev_async`: the start of `kkt_minres_shard_start` with M of P; the partial sums of
+        beta1^2 -- the solve's behind the init kernel's -- go into w.send_a."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        for nm, a in (("rhs", rhs), ("z", z)):
+            if a is None:
+                raise ValueError(f"{nm} is required")
+        sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=1.0)
+        sys.px, sys.pc = self._dev_ptr(P.px, nvar, "px").value, self._dev_ptr(P.pc, ncon, "pc").value
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_start_dev_async(
+            self._h, C.byref(sys), self._schur_ws_ptr(P), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"),
+            self._shard_ws_ptr(w), w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+
+    def kkt_minres_schur_shard_begin(self, w, rank):
+        """`ctd_kkt_minres_schur_cr_shard_begin_dev_async`"""
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_begin_dev_async(self._h, self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+
+    def kkt_minres_schur_shard_alfa(self, z, w, rank):
+        """`ctd_kkt_minres_schur_cr_shard_alfa_dev_async`: phase (A)"""
+        self._shard_phase(_lib.lib().ctd_kkt_minres_schur_cr_shard_alfa_dev_async, z, w, rank)
+
+    def kkt_minres_schur_shard_lanczos(self, P, z, w, rank):
+        """`ctd_kkt_minres_schur_cr_shard_lanczos_dev_async`: phase (B), the solve with P's factor on the handle's block rows, and
+        its partial sums into w.send_b"""
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(
+            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+
+    def kkt_minres_schur_shard_update(self, z, w, rank):
+        """`ctd_kkt_minres_schur_cr_shard_update_dev_async`: phase (C)"""
+        self._shard_phase(_lib.lib().ctd_kkt_minres_schur_cr_shard_update_dev_async, z, w, rank)
+
+    def kkt_minres_schur_shard_info(self, w):
+        """`ctd_kkt_minres_schur_cr_shard_info`"""
+        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_info(self._h, self._shard_ws_ptr(w), w.n_ranks, C.byref(info)))
         return self._minres_info(info)
 
     def grad_shard(self, x, g, sync=False):

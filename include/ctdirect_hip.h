@@ -633,7 +633,7 @@ int32_t ctd_kkt_minres_shard_info(ctd_handle* h, const double* ws_dev, int32_t n
  * LAYOUT (ctd_kkt_schur_layout; works on host-only handles): derived from the handle's layout, and checked on the handle's own
  * Jacobian pattern: two rows that share a non-tail column lie in the same or in adjacent blocks (tail rows exempt), otherwise
  * CTD_EPATTERN with the row in the message.  Refused: block_rows > 64 (CTD_EINVAL), chunk_steps < 1 (CTD_EINVAL), shard handles
- * (CTD_EINVAL: there is no shard form yet), handles whose value_order is not CTD_ORDER_CSR (CTD_EINVAL).
+ * (CTD_EINVAL: the shard form is ctd_kkt_schur_cr_shard_* below), handles whose value_order is not CTD_ORDER_CSR (CTD_EINVAL).
  * WORKSPACE, caller-owned: CTD_KKT_SCHUR_WORKSPACE(N, m) doubles of device memory: 512 fixed (a header, the partial sums of the
  * solve inside MINRES), N words of per-chunk status, N m^2 for the diagonal blocks D_k -> L_k, N m^2 for the couplings E_k -> F_k.
  * Checks in this order: NULL handle -> CTD_EINVAL; struct sizes -> CTD_EINVAL; host-only handle -> CTD_ENODEVICE (not the layout);
@@ -727,6 +727,78 @@ int32_t ctd_kkt_minres_schur_cr_start_dev_async(ctd_handle* h, const ctd_kkt_sys
                                                 const double* rhs_dev, double* z_dev, double rtol);
 int32_t ctd_kkt_minres_schur_cr_dev(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
                                     double* z_dev, double rtol, int64_t max_iter, int64_t check_every, ctd_minres_info* info);
+
+/* ---- the shard form of the log-depth exact Schur preconditioner ------------------------------------------------------------------
+ * Rank r of G holds the steps [sb, se), N_r = se - sb blocks.  With T of the sections above, T_r is the principal submatrix of T on
+ * the blocks [sb, se) and
+ *     M^-1 = blkdiag(diag(px), T_0, ..., T_{G-1}, diag(pc_tail)):
+ * exact inside a rank (block cyclic reduction over the rank's own blocks, schur_cr_levels(N_r) = ceil(log2 N_r) levels, factor
+ * 2 n_levels + 2 launches, solve 2 n_levels + 1), cut at the rank boundaries: each of the G - 1 cuts drops one coupling block
+ * T(se, se - 1) of the matrix.  It is the chunked matrix of ctd_kkt_schur_* with the ranks' step ranges -- of any lengths -- as
+ * chunks.  No collective is needed: a rank's factor and solve touch its own blocks only.  The kernels are those of the section
+ * above, given the rank's blocks through offset pointers (csrc/ctd_schur_cr_kernels.hpp): every sum is in their order, and a
+ * whole-grid handle -- the single shard -- leaves the bits of ctd_kkt_schur_cr_factor_dev_async in the factor's part of the
+ * workspace (header, status words, blocks) and the bits of ctd_kkt_schur_cr_solve_dev_async in out.
+ * Every handle is accepted.  Buffers are full-length with global indexing (jvals: nnzj, px: nvar, sc / r / out: ncon entries).
+ * LAYOUT (works on host-only handles): N the grid's steps; n_blocks = N_r; first_row = sb block_rows; tail_rows, first_tail_row,
+ * tail_cols: the grid's (the tail rows are the last rank's in the MINRES solve, none of this family touches them); workspace =
+ * CTD_KKT_SCHUR_CR_WORKSPACE(n_blocks, block_rows).  THE READ SET OF THE FACTOR, half-open ranges derived from the handle's own
+ * pattern: jvals on [jvals_begin, jvals_end), the CSR range of the rank's block rows (inside ctd_shard_info's range; on the last
+ * rank without the tail rows behind it); px on [px_begin, px_end), the span of the non-tail columns of those rows: the rank's own
+ * variables and the first node of block se -- the entries ctd_jsq_rows_shard_dev_async reads of its weight --; sc on the rows
+ * [first_row, first_row + n_blocks block_rows).  Anything else of the three buffers may hold anything.
+ * Refusals: value_order not CTD_ORDER_CSR, block_rows > 64 (CTD_EINVAL), the pattern (CTD_EPATTERN), in the order of the sections
+ * above; null pointers, an output equal to an input -> CTD_EINVAL.  ctd_last_error begins with the entry point that was called.
+ * A workspace factored for another step range, another N_r or m, or by the chunked family is recognised on the device by the
+ * solve (the header: tag, N_r, m, n_levels, sb) and nothing is stored; the info call returns CTD_EINVAL for it. */
+/* struct_size = sizeof(ctd_schur_cr_shard_layout), set by the caller */
+typedef struct ctd_schur_cr_shard_layout {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t N, step_begin, step_end, n_blocks, block_rows;
+    int64_t first_row, tail_rows, first_tail_row, tail_cols;
+    int64_t n_levels, factor_launches, solve_launches;
+    int64_t workspace;          /* doubles */
+    int64_t jvals_begin, jvals_end, px_begin, px_end;
+} ctd_schur_cr_shard_layout;
+int32_t ctd_kkt_schur_cr_shard_layout(ctd_handle* h, ctd_schur_cr_shard_layout* out);
+/* Factor of T_r, enqueue-only, factor_launches launches; reads the read set above, writes the whole workspace.  The pattern upload
+ * is shared with the other factors: the first factor of any kind on a handle is refused while the stream is capturing. */
+int32_t ctd_kkt_schur_cr_shard_factor_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev,
+                                                double* ws_dev);
+/* out = T_r^-1 r on the rank's block rows [first_row, first_row + n_blocks block_rows): reads r there, writes out there and nothing
+ * else of out (not the tail rows, not another rank's rows); solve_launches launches; out must not be r */
+int32_t ctd_kkt_schur_cr_shard_solve_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev);
+/* waits for the handle's stream; *first_bad_block = -1, or the smallest GLOBAL block index in [sb, se) with a recorded pivot */
+int32_t ctd_kkt_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block);
+/* The shard form of the MINRES solve (ctd_kkt_minres_shard_* above: the same phases, the same three all-gathers by the caller, the
+ * same checks) with M of this section.  sys->px and sys->pc are required (px: the one the factor was built from; pc is read on the
+ * tail rows).  Both send slots grow to CTD_KKT_MINRES_SCHUR_SHARD_SLOT doubles: the slot above, then room for the solve's at most
+ * 256 partial sums of r2 . y over the rank's block rows, padded with +0.0, and their count; the workspace is cut by
+ * ctd_kkt_minres_schur_cr_shard_layout (the struct of ctd_kkt_minres_shard_layout; slot = CTD_KKT_MINRES_SCHUR_SHARD_SLOT).  No
+ * fourth gather: the partial sums travel in the slots.  start and lanczos take the factor's workspace (the handle keeps no state of
+ * the solve): behind their own launch -- which leaves y and its term of the inner product open on the rank's block rows -- they
+ * enqueue the solve_launches launches of the solve and one launch that writes min(N_r, 256) partial sums into the send slot
+ * (workgroup g: the local blocks g, g + G_r, ... in that order); in lanczos every one of them reads the status (B) read and stores
+ * nothing unless it is running.  begin, alfa, update: one launch each.  beta1^2 and beta^2 are one running sum from 0.0: the terms
+ * of the diagonal form in their order (ranks ascending, workgroups ascending), then the ranks ascending again, each rank's solve
+ * partial sums in ascending workgroup order; with one rank that is the order of ctd_kkt_minres_schur_cr_dev, whose bits a single
+ * shard of the whole grid gives.  A failed pivot on one rank is NaN in its partial sums, which reaches beta^2 on every rank: all
+ * ranks end with "breakdown" after the same chunk.  Further checks: px / pc / schur_ws null or misaligned, schur_ws overlapping z
+ * or the workspace -> CTD_EINVAL. */
+#define CTD_KKT_MINRES_SCHUR_SHARD_SLOT (CTD_KKT_MINRES_SHARD_SLOT + 256 + 16)
+#define CTD_KKT_MINRES_SCHUR_SHARD_WORKSPACE(n, n_ranks) \
+    (8 * (int64_t)(n) + (2 + 2 * (int64_t)(n_ranks)) * CTD_KKT_MINRES_SCHUR_SHARD_SLOT + 96)
+int32_t ctd_kkt_minres_schur_cr_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out);
+int32_t ctd_kkt_minres_schur_cr_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev,
+                                                      const double* rhs_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
+                                                      int32_t rank, double rtol, int64_t max_iter);
+int32_t ctd_kkt_minres_schur_cr_shard_begin_dev_async(ctd_handle* h, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_shard_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev,
+                                                        int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_shard_update_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info);
 
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of

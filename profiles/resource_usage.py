@@ -223,24 +223,35 @@ def krylov_table():
     ks = remarks("ctd_krylov", "", KRYLOV_KERNELS)
     names = [n for n in mangled("ctd_krylov") if re.search("|".join(KRYLOV_KERNELS), n)]
     assert len(names) == len(ks)
-    for k, n in zip(ks, names):         # the SCHUR = true instantiation of a kernel (its only template argument)
-        if re.search(r"ILb1EE", n):
+    for k, n in zip(ks, names):         # the SCHUR = true instantiation of a kernel (its only template argument); of a shard kernel:
+        if re.search(r"ILb1EE", n) or "KrylovSchurShardParams" in n:      # the one for the Schur form's argument struct
             k["kernel"] += "<SCHUR>"
     assert sorted({k["kernel"].replace("<SCHUR>", "") for k in ks}) == sorted(KRYLOV_KERNELS), ks
     for stem, kernels in (("ctd_schur", SCHUR_KERNELS), ("ctd_schur_cr", SCHUR_CR_KERNELS)):
         sch = remarks(stem, "", kernels)
         for k, n in zip(sch, [n for n in mangled(stem) if re.search("|".join(kernels), n)]):
-            mb = re.search(r"ILi(\d+)EE", n)
+            mb = re.search(r"ILi(\d+)E", n)
             k["kernel"] += f"<{mb.group(1)}>" if mb else ""
+            if "SchurCrShard" in n:      # the instantiation for a shard's argument struct (csrc/ctd_schur_cr_kernels.hpp)
+                k["kernel"] += " shard"
         ks += sch
     path = os.path.join(ROOT, "profiles", "kkt_minres_resources.md")
     lines = ["# Resources of the MINRES vector kernels (csrc/ctd_krylov.hip)\n\n",
              "From the compiler's remarks for gfx950 (`python profiles/resource_usage.py --krylov`, no GPU needed).  The kernels do not\n"
              "depend on the OCP: one instantiation each, two (`<SCHUR>`: with the block-tridiagonal Schur preconditioner) of the four whose\n"
-             "code differs with it; below them the kernels of that preconditioner (csrc/ctd_schur.hip), the factor and the solve per\n"
-             "largest block size, and those of its log-depth exact form (csrc/ctd_schur_cr.hip).  The script fails if any of them uses\n"
+             "code differs with it (of the shard form: the four instantiated for the Schur form's argument struct, csrc/\n"
+             "ctd_krylov_shard_kernels.hpp); below them the kernels of that preconditioner (csrc/ctd_schur.hip), the factor and the solve per\n"
+             "largest block size, and those of its log-depth exact form (csrc/ctd_schur_cr.hip; `shard`: the instantiation for a\n"
+             "shard's argument struct).  The script fails if any of them uses\n"
              "scratch.\n\n",
              "| kernel | VGPR + AGPR | scratch B/lane | waves/SIMD |\n", "|---|---|---|---|\n"]
+    # a kernel keeps the row it has in the file; new ones follow in the compiler's order (instantiating a kernel a second time
+    # reorders the compiler's remarks, not the table)
+    have = []
+    if os.path.exists(path):
+        with open(path) as f:
+            have = [l.split("|")[1].strip() for l in f if l.startswith("| ") and not l.startswith("| kernel")]
+    ks = [k for _, k in sorted(enumerate(ks), key=lambda ik: (have.index(ik[1]["kernel"]) if ik[1]["kernel"] in have else len(have), ik[0]))]
     for k in ks:
         assert k["scratch"] == 0, k
         lines.append(f"| {k['kernel']} | {k['vgpr']} + {k['agpr']} | {k['scratch']} | {k['waves']} |\n")
