@@ -85,6 +85,29 @@ class ctd_schur_cr_shard_layout(C.Structure):
         "factor_launches", "solve_launches", "workspace", "jvals_begin", "jvals_end", "px_begin", "px_end")]
 
 
+# the joined form (ctd_kkt_schur_cr_joint_layout): separator, interior, launch counts, record slots, workspace offsets, read set
+class ctd_schur_cr_joint_layout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(nm, C.c_int64) for nm in (
+        "N", "n_ranks", "rank", "step_begin", "step_end", "separator", "int_begin", "n_int", "block_rows", "first_row", "tail_rows",
+        "first_tail_row", "tail_cols", "n_levels", "n_sep", "factor_local_launches", "factor_join_launches", "solve_local_launches",
+        "solve_join_launches", "factor_slot", "solve_slot", "off_es", "off_eb", "off_ds", "off_wl", "off_wr", "off_scratch", "off_reduced",
+        "off_rs", "off_xs", "off_sigma", "workspace", "jvals_begin", "jvals_end", "jvals_halo_begin", "jvals_halo_end", "px_begin",
+        "px_end")]
+
+
+# CTD_KKT_MINRES_SCHUR_JOINT_SLOT: the slot of the sharded solve that carries the joined form
+KKT_MINRES_SCHUR_JOINT_SLOT = KKT_MINRES_SHARD_SLOT + 256 + 16 + 3 * 64 + 16
+
+# CTD_KKT_SCHUR_CR_JOINT_MAX_RANKS, CTD_KKT_SCHUR_CR_JOINT_SOLVE_SLOT
+KKT_SCHUR_CR_JOINT_MAX_RANKS = 256
+KKT_SCHUR_CR_JOINT_SOLVE_SLOT = 16 + 3 * 64
+
+
+def kkt_schur_cr_joint_factor_slot(m):
+    """CTD_KKT_SCHUR_CR_JOINT_FACTOR_SLOT(m)"""
+    return 16 + 4 * m * m
+
+
 # CTD_KKT_MINRES_SCHUR_SHARD_SLOT: the slot of the sharded solve that carries it
 KKT_MINRES_SCHUR_SHARD_SLOT = KKT_MINRES_SHARD_SLOT + 256 + 16
 
@@ -215,6 +238,21 @@ SYMBOLS = {
     "ctd_kkt_minres_schur_cr_shard_lanczos_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
     "ctd_kkt_minres_schur_cr_shard_update_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
     "ctd_kkt_minres_schur_cr_shard_info": (C.c_int32, [_vp, _vp, C.c_int32, C.POINTER(ctd_minres_info)]),
+    # the joined form of the log-depth Schur preconditioner: local phases and joins around the caller's all-gathers
+    "ctd_kkt_schur_cr_joint_layout": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.POINTER(ctd_schur_cr_joint_layout)]),
+    "ctd_kkt_schur_cr_joint_factor_local_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_schur_cr_joint_factor_join_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_schur_cr_joint_solve_local_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_schur_cr_joint_solve_join_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_schur_cr_joint_info": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _ip]),
+    "ctd_kkt_minres_schur_cr_joint_layout": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.POINTER(ctd_minres_shard_layout)]),
+    "ctd_kkt_minres_schur_cr_joint_start_dev_async": (C.c_int32, [_vp, C.POINTER(ctd_kkt_system), _vp, _vp, _vp, _vp, C.c_int32, C.c_int32,
+                                                                  C.c_double, C.c_int64]),
+    "ctd_kkt_minres_schur_cr_joint_begin_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_joint_alfa_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_joint_lanczos_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_joint_update_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32]),
+    "ctd_kkt_minres_schur_cr_joint_info": (C.c_int32, [_vp, _vp, C.c_int32, C.POINTER(ctd_minres_info)]),
     "ctd_jprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_jtprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "ctd_hprod_shard_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_double, _vp, _vp]),

@@ -29,6 +29,7 @@
 #include "ctd_diag_kernels.hpp"
 #include "ctd_krylov_kernels.hpp"
 #include "ctd_krylov_shard_kernels.hpp"
+#include "ctd_schur_cr_joint_kernels.hpp"
 #include "ctd_schur_cr_kernels.hpp"
 #include "ctd_schur_kernels.hpp"
 #include "ctd_jit.hpp"
@@ -2400,6 +2401,404 @@ int32_t ctd_kkt_minres_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, 
     KrylovState s;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks, kKrylovSchurSlot).pend, sizeof(s),
+                         hipMemcpyDeviceToHost));
+    info->status = s.status;
+    info->iterations = s.itn;
+    info->phibar = s.phibar;
+    info->Anorm = s.Anorm;
+    info->ynorm = s.ynorm;
+    info->beta1 = s.beta1;
+    return CTD_OK;
+}
+
+// ---- the joined form of the log-depth Schur preconditioner (plan: ctd_schur_plan.hpp; kernels: ctd_schur_cr_joint_kernels.hpp) ---------
+static_assert(kSchurJointMaxRanks == CTD_KKT_SCHUR_CR_JOINT_MAX_RANKS, "the largest n_ranks of the header");
+static_assert(kSchurJointSolveSlot == CTD_KKT_SCHUR_CR_JOINT_SOLVE_SLOT, "the solve record of the header");
+static_assert(schur_cr_joint_factor_slot(9) == CTD_KKT_SCHUR_CR_JOINT_FACTOR_SLOT(9), "the factor record of the header");
+
+// every handle is accepted; the plan's own refusals (CSR order, block_rows, the pattern -- walked once per handle --, the split)
+static int32_t schur_crj_plan(ctd_handle* h, const char* fn, int32_t n_ranks, int32_t rank, bool ranges, SchurCrJointPlan& pl) {
+    std::string err;
+    const int st = plan_kkt_schur_cr_joint(h->model, n_ranks, rank, h->step_begin, h->step_end, !h->schur_verified, ranges, pl, err);
+    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
+    h->schur_verified = true;
+    return CTD_OK;
+}
+static SchurCrJointId schur_crj_id(const SchurCrJointPlan& pl) {
+    return SchurCrJointId{pl.step_begin, pl.step_end, (int32_t)pl.n_ranks, (int32_t)pl.rank};
+}
+// the arguments of the family's own kernels; the pattern must have been uploaded for the factor (the solves do not read it)
+static SchurCrJointParams schur_crj_params(const ctd_handle* h, const SchurCrJointPlan& pl, double* ws) {
+    SchurCrJointParams p{};
+    p.N = pl.N;
+    p.n_int = pl.n_int;
+    p.v_off = pl.first_tail_col;
+    p.int_begin = pl.int_begin;
+    p.id = schur_crj_id(pl);
+    p.m = (int32_t)pl.block_rows;
+    p.n_levels = (int32_t)pl.n_levels;
+    p.mode = SCHUR_PLAIN;
+    p.rowptr = h->d_schur_rowptr.p;
+    p.colind = h->d_schur_colind.p;
+    p.ws = ws;
+    p.off_es = pl.off_es; p.off_eb = pl.off_eb; p.off_ds = pl.off_ds; p.off_wl = pl.off_wl; p.off_wr = pl.off_wr;
+    p.off_scratch = pl.off_scratch; p.off_reduced = pl.off_reduced; p.off_rs = pl.off_rs; p.off_xs = pl.off_xs; p.off_sigma = pl.off_sigma;
+    p.workspace = pl.workspace;
+    return p;
+}
+// the interior as the whole-grid problem of n_int blocks: the solve's arguments
+static SchurCrJointSolveParams schur_crj_solve_params(const SchurCrJointPlan& pl, int32_t mode, double* ws, const double* r, double* out,
+                                                      const KrylovState* cur, double* part) {
+    SchurCrJointSolveParams sp{};
+    const int64_t row0 = pl.int_begin * pl.block_rows;
+    static_cast<SchurCrSolveParams&>(sp) =
+        SchurCrSolveParams{pl.n_int, (int32_t)pl.block_rows, mode, (int32_t)pl.n_levels, 0, ws, r + row0, out + row0, cur};
+    sp.first = pl.int_begin;
+    sp.part = part;
+    sp.id = schur_crj_id(pl);
+    return sp;
+}
+// [p, p + n) against the workspace
+static int32_t schur_crj_disjoint(ctd_handle* h, const char* fn, const char* name, const double* p, int64_t n, const double* ws,
+                                  const SchurCrJointPlan& pl) {
+    if (mrs_overlap(p, n, ws, pl.workspace)) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " overlaps the workspace");
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_joint_layout(ctd_handle* h, int32_t n_ranks, int32_t rank, ctd_schur_cr_joint_layout* out) {
+    const char* fn = "ctd_kkt_schur_cr_joint_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_schur_cr_joint_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_cr_joint_layout) = " +
+                                       std::to_string(sizeof(ctd_schur_cr_joint_layout)));
+    SchurCrJointPlan pl;
+    if (const int32_t st = schur_crj_plan(h, fn, n_ranks, rank, true, pl)) return st;
+    out->reserved = 0;
+    out->N = pl.N; out->n_ranks = pl.n_ranks; out->rank = pl.rank;
+    out->step_begin = pl.step_begin; out->step_end = pl.step_end;
+    out->separator = pl.separator; out->int_begin = pl.int_begin; out->n_int = pl.n_int;
+    out->block_rows = pl.block_rows; out->first_row = pl.first_row;
+    out->tail_rows = pl.tail_rows; out->first_tail_row = pl.first_tail_row; out->tail_cols = pl.tail_cols;
+    out->n_levels = pl.n_levels; out->n_sep = pl.n_sep;
+    out->factor_local_launches = pl.factor_local_launches; out->factor_join_launches = pl.factor_join_launches;
+    out->solve_local_launches = pl.solve_local_launches; out->solve_join_launches = pl.solve_join_launches;
+    out->factor_slot = pl.factor_slot; out->solve_slot = pl.solve_slot;
+    out->off_es = pl.off_es; out->off_eb = pl.off_eb; out->off_ds = pl.off_ds; out->off_wl = pl.off_wl; out->off_wr = pl.off_wr;
+    out->off_scratch = pl.off_scratch; out->off_reduced = pl.off_reduced; out->off_rs = pl.off_rs; out->off_xs = pl.off_xs;
+    out->off_sigma = pl.off_sigma;
+    out->workspace = pl.workspace;
+    out->jvals_begin = pl.jvals_begin; out->jvals_end = pl.jvals_end;
+    out->jvals_halo_begin = pl.jvals_halo_begin; out->jvals_halo_end = pl.jvals_halo_end;
+    out->px_begin = pl.px_begin; out->px_end = pl.px_end;
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_schur_cr_joint_factor_local_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev,
+                                                      double* ws_dev, double* send_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_schur_cr_joint_factor_local_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    int32_t st;
+    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if ((st = mrs_check_ptr(h, fn, "jvals", jvals_dev)) || (st = mrs_check_ptr(h, fn, "px", px_dev)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev)))
+        return st;
+    if (sc_dev && (st = mrs_check_ptr(h, fn, "sc", sc_dev))) return st;
+    if (n_ranks > 1 && (st = mrs_check_ptr(h, fn, "send", send_dev))) return st;
+    const Layout& L = h->model.L;
+    if ((st = schur_crj_disjoint(h, fn, "jvals", jvals_dev, h->model.nnzj, ws_dev, pl)) || (st = schur_crj_disjoint(h, fn, "px", px_dev, L.nvar, ws_dev, pl)) ||
+        (st = schur_crj_disjoint(h, fn, "sc", sc_dev, L.ncon, ws_dev, pl)) ||
+        (n_ranks > 1 && (st = schur_crj_disjoint(h, fn, "send", send_dev, pl.factor_slot, ws_dev, pl))))
+        return st;
+    if (n_ranks > 1 && (mrs_overlap(send_dev, pl.factor_slot, jvals_dev, h->model.nnzj) || mrs_overlap(send_dev, pl.factor_slot, px_dev, L.nvar) ||
+                        mrs_overlap(send_dev, pl.factor_slot, sc_dev, L.ncon)))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (ws and send) must not overlap an input buffer");
+    if ((st = schur_upload_pattern(h, fn))) return st;
+    SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
+    p.jvals = jvals_dev;
+    p.px = px_dev;
+    p.sc = sc_dev;
+    p.send = send_dev;
+    const int64_t row0 = pl.int_begin * pl.block_rows;
+    SchurCrJointFactorParams fp{};
+    static_cast<SchurCrFactorParams&>(fp) =
+        SchurCrFactorParams{pl.n_int, pl.first_tail_col, (int32_t)pl.block_rows, (int32_t)pl.n_levels, h->d_schur_rowptr.p + row0,
+                            h->d_schur_colind.p, jvals_dev, px_dev, sc_dev ? sc_dev + row0 : nullptr, ws_dev};
+    fp.first = pl.int_begin;
+    fp.id = p.id;
+    hipError_t e = n_ranks > 1 ? schur_cr_joint_interface(p, h->stream) : hipSuccess;      // (one rank: no interface, nothing behind the interior's part is read)
+    if (e == hipSuccess) e = schur_cr_factor(fp, h->stream);
+    if (e == hipSuccess && n_ranks > 1) e = schur_cr_joint_spikes(p, h->stream);
+    return mrs_launched(h, fn, e);
+}
+
+int32_t ctd_kkt_schur_cr_joint_factor_join_dev_async(ctd_handle* h, double* ws_dev, const double* gathered_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_schur_cr_joint_factor_join_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    int32_t st;
+    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    if (n_ranks == 1) return CTD_OK;
+    if ((st = mrs_check_ptr(h, fn, "gathered", gathered_dev))) return st;
+    if ((st = schur_crj_disjoint(h, fn, "gathered", gathered_dev, n_ranks * pl.factor_slot, ws_dev, pl))) return st;
+    SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
+    p.gathered = gathered_dev;
+    p.slot = pl.factor_slot;
+    return mrs_launched(h, fn, schur_cr_joint_factor_join(p, h->stream));
+}
+
+int32_t ctd_kkt_schur_cr_joint_solve_local_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev, double* send_dev,
+                                                     int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_schur_cr_joint_solve_local_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    int32_t st;
+    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev)) || (st = mrs_check_ptr(h, fn, "r", r_dev)) || (st = mrs_check_ptr(h, fn, "out", out_dev)))
+        return st;
+    if (n_ranks > 1 && (st = mrs_check_ptr(h, fn, "send", send_dev))) return st;
+    const int64_t ncon = h->model.L.ncon;
+    if (mrs_overlap(out_dev, ncon, r_dev, ncon)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not overlap r");
+    if ((st = schur_crj_disjoint(h, fn, "r", r_dev, ncon, ws_dev, pl)) || (st = schur_crj_disjoint(h, fn, "out", out_dev, ncon, ws_dev, pl)))
+        return st;
+    if (n_ranks > 1 && (mrs_overlap(send_dev, pl.solve_slot, r_dev, ncon) || mrs_overlap(send_dev, pl.solve_slot, out_dev, ncon) ||
+                        mrs_overlap(send_dev, pl.solve_slot, ws_dev, pl.workspace)))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": send must not overlap r, out or the workspace");
+    hipError_t e = schur_cr_solve(schur_crj_solve_params(pl, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr), h->stream);
+    if (e == hipSuccess && n_ranks > 1) {
+        SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
+        p.r = r_dev;
+        p.out = out_dev;
+        p.send = send_dev;
+        e = schur_cr_joint_solve_record(p, h->stream);
+    }
+    return mrs_launched(h, fn, e);
+}
+
+int32_t ctd_kkt_schur_cr_joint_solve_join_dev_async(ctd_handle* h, double* ws_dev, const double* gathered_dev, double* out_dev, int32_t n_ranks,
+                                                    int32_t rank) {
+    const char* fn = "ctd_kkt_schur_cr_joint_solve_join_dev_async";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    int32_t st;
+    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev)) || (st = mrs_check_ptr(h, fn, "out", out_dev))) return st;
+    if (n_ranks == 1) return CTD_OK;
+    if ((st = mrs_check_ptr(h, fn, "gathered", gathered_dev))) return st;
+    const int64_t ncon = h->model.L.ncon, glen = n_ranks * pl.solve_slot;
+    if ((st = schur_crj_disjoint(h, fn, "gathered", gathered_dev, glen, ws_dev, pl)) || (st = schur_crj_disjoint(h, fn, "out", out_dev, ncon, ws_dev, pl)))
+        return st;
+    if (mrs_overlap(gathered_dev, glen, out_dev, ncon)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not overlap gathered");
+    SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
+    p.gathered = gathered_dev;
+    p.slot = pl.solve_slot;
+    p.out = out_dev;
+    return mrs_launched(h, fn, schur_cr_joint_solve_join(p, h->stream));
+}
+
+int32_t ctd_kkt_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, int32_t rank, int64_t* first_bad_block) {
+    const char* fn = "ctd_kkt_schur_cr_joint_info";
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    if (const int32_t st = schur_crj_plan(h, fn, n_ranks, rank, false, pl)) return st;
+    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int64_t head[9];
+    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
+    if (head[0] != kSchurCrJointTag || head[1] != pl.n_int || head[2] != pl.block_rows || head[3] != pl.n_levels || head[4] != pl.int_begin ||
+        head[5] != pl.step_begin || head[6] != pl.step_end || head[7] != pl.n_ranks || head[8] != pl.rank)
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle's steps as rank " + std::to_string(rank) + " of " +
+                                       std::to_string(n_ranks) + " (ctd_kkt_schur_cr_joint_factor_local_dev_async)");
+    std::vector<int64_t> status((size_t)pl.n_int), red((size_t)pl.n_sep);
+    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(red.data(), ws_dev + pl.off_reduced, sizeof(int64_t) * red.size(), hipMemcpyDeviceToHost));
+    int64_t bad = -1;
+    for (int64_t k = 0; k < pl.n_int && bad < 0; ++k)
+        if (status[(size_t)k] >= 0) bad = pl.int_begin + k;
+    for (int64_t k = 0; k < pl.n_ranks - 1; ++k)
+        if (red[(size_t)k] >= 0 && (bad < 0 || red[(size_t)k] < bad)) bad = red[(size_t)k];
+    *first_bad_block = bad;
+    return CTD_OK;
+}
+
+// The phases of ctd_kkt_minres_schur_cr_shard_* with M of the joined form: slots of kKrylovSchurJointSlot doubles
+static_assert(kKrylovSchurJointSlot == CTD_KKT_MINRES_SCHUR_JOINT_SLOT, "the slot length of the header");
+static_assert(kKrylovSchurJointSlot - kSlotJoint == kSchurJointSolveSlot, "the solve record fits behind the Schur form's slot");
+static_assert(CTD_KKT_MINRES_SCHUR_JOINT_WORKSPACE(10, 3) == kKrylovVectors * 10 + 8 * kKrylovSchurJointSlot + 96, "the workspace of the header");
+
+static KrylovSchurJointParams mrsj_params(const ctd_handle* h, const SchurCrJointPlan& sc, double* ws, double* z, const double* schur_ws) {
+    const KrylovShardPlan pl = mrs_plan(h);
+    const KrylovOwn own{pl.var_lo, pl.var_hi - pl.var_lo, pl.tail_lo, pl.tail_hi - pl.tail_lo, pl.row_lo, pl.last, (int32_t)sc.n_ranks};
+    KrylovSchurJointParams sp{};
+    static_cast<KrylovShardParams&>(sp) = krylov_shard_params(ws, pl.n, pl.n_own, own, z, kKrylovSchurJointSlot);
+    sp.s_lo = h->model.L.nvar + sc.first_row;
+    sp.s_hi = h->model.L.nvar + sc.step_end * sc.block_rows;
+    sp.s_nwg = schur_solve_grid(sc.n_int);
+    sp.sigma = schur_ws ? schur_ws + sc.off_sigma : nullptr;
+    return sp;
+}
+// the prologue of every phase: rank, plan, pointers, disjoint ranges (z and the factor's workspace may be absent)
+static int32_t mrsj_phase(ctd_handle* h, const char* fn, const double* schur_ws, bool with_schur, const double* z_dev, bool with_z,
+                          const double* ws_dev, int32_t n_ranks, int32_t rank, SchurCrJointPlan& pl) {
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
+    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if (with_z && (st = mrs_check_ptr(h, fn, "z", z_dev))) return st;
+    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    if (with_schur && (st = mrs_check_ptr(h, fn, "schur_ws", schur_ws))) return st;
+    const int64_t n = h->model.L.nvar + h->model.L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurJointSlot);
+    if (with_z && mrs_overlap(z_dev, n, ws_dev, wlen)) return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
+    if (with_schur && (mrs_overlap(schur_ws, pl.workspace, ws_dev, wlen) || (with_z && mrs_overlap(schur_ws, pl.workspace, z_dev, n))))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": schur_ws must not overlap z or the workspace");
+    return CTD_OK;
+}
+// behind start's and (B)'s launch: the interior's solve with its partial sums into the send slot, then the solve record behind them
+static hipError_t mrsj_local(const ctd_handle* h, const SchurCrJointPlan& pl, const KrylovSchurJointParams& sp, int32_t mode, double* schur_ws,
+                             double* send) {
+    const int64_t nvar = h->model.L.nvar;
+    hipError_t e = schur_cr_solve(schur_crj_solve_params(pl, mode, schur_ws, sp.r2 + nvar, sp.y + nvar, sp.cur, send + kSlotSchur), h->stream);
+    if (e != hipSuccess || pl.n_ranks == 1) return e;
+    SchurCrJointParams p = schur_crj_params(h, pl, schur_ws);
+    p.mode = mode;
+    p.cur = sp.cur;
+    p.r = sp.r2 + nvar;
+    p.out = sp.y + nvar;
+    p.send = send + kSlotJoint;
+    return schur_cr_joint_solve_record(p, h->stream);
+}
+// ahead of begin's and (C)'s launch: the reduced solve from the gathered records (sigma), the correction of y on the rank's block rows
+static hipError_t mrsj_join(const ctd_handle* h, const SchurCrJointPlan& pl, const KrylovSchurJointParams& sp, int32_t mode, double* schur_ws,
+                            const double* gathered) {
+    if (pl.n_ranks == 1) return hipSuccess;
+    SchurCrJointParams p = schur_crj_params(h, pl, schur_ws);
+    p.mode = mode;
+    p.cur = sp.cur;
+    p.out = sp.y + h->model.L.nvar;
+    p.gathered = gathered + kSlotJoint;
+    p.slot = kKrylovSchurJointSlot;
+    return schur_cr_joint_solve_join(p, h->stream);
+}
+
+int32_t ctd_kkt_minres_schur_cr_joint_layout(ctd_handle* h, int32_t n_ranks, int32_t rank, ctd_minres_shard_layout* out) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_layout";
+    if (!h) return CTD_EINVAL;
+    if (!out || out->struct_size != sizeof(ctd_minres_shard_layout))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_minres_shard_layout) = " +
+                                       std::to_string(sizeof(ctd_minres_shard_layout)));
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
+    SchurCrJointPlan sp;
+    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, sp))) return st;
+    const KrylovShardPlan pl = mrs_plan(h);
+    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks, kKrylovSchurJointSlot);
+    out->reserved = 0;
+    out->n = pl.n; out->n_ranks = n_ranks;
+    out->var_begin = pl.var_lo; out->var_end = pl.var_hi;
+    out->tail_begin = pl.tail_lo; out->tail_end = pl.tail_hi;
+    out->row_begin = pl.row_lo; out->row_end = pl.row_hi;
+    out->n_own = pl.n_own; out->n_dot = pl.n_dot; out->nwg = pl.nwg; out->chunk = pl.chunk;
+    out->slot = kKrylovSchurJointSlot;
+    out->off_v = l.v; out->off_kv = l.kv;
+    out->off_send_a = l.send_a; out->off_send_b = l.send_b;
+    out->off_gathered_a = l.gathered_a; out->off_gathered_b = l.gathered_b;
+    out->off_state = l.pend;
+    out->workspace = krylov_shard_workspace(pl.n, n_ranks, kKrylovSchurJointSlot);
+    return CTD_OK;
+}
+
+int32_t ctd_kkt_minres_schur_cr_joint_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
+                                                      double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank, double rtol,
+                                                      int64_t max_iter) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_start_dev_async";
+    int32_t st;
+    if (!mr_structs_ok(h, fn, sys, false, nullptr, &st)) return st;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true)) || (st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if ((st = mrs_check_ptr(h, fn, "rhs", rhs_dev)) || (st = mrs_check_ptr(h, fn, "px", sys->px)) || (st = mrs_check_ptr(h, fn, "pc", sys->pc))) return st;
+    if ((st = mrsj_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl))) return st;
+    {   // the inputs as ranges against the output ranges
+        const Layout& L = h->model.L;
+        const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurJointSlot);
+        const std::pair<const double*, int64_t> ins[] = {{rhs_dev, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
+        for (const auto& in : ins)
+            if (mrs_overlap(in.first, in.second, z_dev, n) || mrs_overlap(in.first, in.second, ws_dev, wlen) ||
+                mrs_overlap(in.first, in.second, schur_ws_dev, pl.workspace))
+                return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (z, ws and schur_ws) must not overlap an input buffer");
+    }
+    if (!(rtol >= 0.0)) return fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
+    if (max_iter < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": max_iter = " + std::to_string(max_iter) + ", must be at least 1");
+    const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, z_dev, schur_ws_dev);
+    hipError_t e = krylov_schur_joint_start(sp, rhs_dev, sys->px, sys->pc, h->model.L.nvar, rtol, max_iter, h->stream);
+    if (e == hipSuccess) e = mrsj_local(h, pl, sp, SCHUR_START, schur_ws_dev, sp.send_a);
+    return mrs_launched(h, fn, e);
+}
+int32_t ctd_kkt_minres_schur_cr_joint_begin_dev_async(ctd_handle* h, double* schur_ws_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_begin_dev_async";
+    if (!h) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    if (const int32_t st = mrsj_phase(h, fn, schur_ws_dev, true, nullptr, false, ws_dev, n_ranks, rank, pl)) return st;
+    const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, nullptr, schur_ws_dev);
+    hipError_t e = mrsj_join(h, pl, sp, SCHUR_START, schur_ws_dev, sp.gathered_a);
+    if (e == hipSuccess) e = krylov_schur_joint_begin(sp, h->stream);
+    return mrs_launched(h, fn, e);
+}
+int32_t ctd_kkt_minres_schur_cr_joint_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_alfa_dev_async";
+    if (!h) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    if (const int32_t st = mrsj_phase(h, fn, nullptr, false, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    return mrs_launched(h, fn, krylov_shard_alfa(mrsj_params(h, pl, ws_dev, z_dev, nullptr), h->stream));
+}
+int32_t ctd_kkt_minres_schur_cr_joint_lanczos_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
+                                                        int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_lanczos_dev_async";
+    if (!h) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    if (const int32_t st = mrsj_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, z_dev, schur_ws_dev);
+    hipError_t e = krylov_schur_joint_lanczos(sp, h->stream);
+    if (e == hipSuccess) e = mrsj_local(h, pl, sp, SCHUR_ITER, schur_ws_dev, sp.send_b);
+    return mrs_launched(h, fn, e);
+}
+int32_t ctd_kkt_minres_schur_cr_joint_update_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
+                                                       int32_t rank) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_update_dev_async";
+    if (!h) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    SchurCrJointPlan pl;
+    if (const int32_t st = mrsj_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, z_dev, schur_ws_dev);
+    hipError_t e = mrsj_join(h, pl, sp, SCHUR_ITER, schur_ws_dev, sp.gathered_b);
+    if (e == hipSuccess) e = krylov_schur_joint_update(sp, h->stream);
+    return mrs_launched(h, fn, e);
+}
+int32_t ctd_kkt_minres_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info) {
+    const char* fn = "ctd_kkt_minres_schur_cr_joint_info";
+    if (!h) return CTD_EINVAL;
+    if (!info || info->struct_size != sizeof(ctd_minres_info))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
+                                       std::to_string(sizeof(ctd_minres_info)));
+    const OnDevice on(h, fn);
+    if (on.st) return on.st;
+    int32_t st;
+    if ((st = mrs_check_rank(h, fn, n_ranks, 0, false)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    KrylovState s;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks, kKrylovSchurJointSlot).pend, sizeof(s),
                          hipMemcpyDeviceToHost));
     info->status = s.status;
     info->iterations = s.itn;

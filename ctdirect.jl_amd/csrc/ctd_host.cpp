@@ -1365,6 +1365,43 @@ int plan_kkt_schur_cr_shard(const Model& mo, int64_t step_begin, int64_t step_en
     return ST_OK;
 }
 
+// ... and of the joined form: the separator, the interior and the offsets; the read set is the shard form's and the halo behind it
+int plan_kkt_schur_cr_joint(const Model& mo, int64_t n_ranks, int64_t rank, int64_t step_begin, int64_t step_end, bool verify, bool ranges,
+                            SchurCrJointPlan& out, std::string& err) {
+    SchurCrShardPlan sh;
+    if (const int st = plan_kkt_schur_cr_shard(mo, step_begin, step_end, verify, ranges, sh, err)) return st;
+    if (!schur_cr_joint_range_ok(sh.N, n_ranks, rank, step_begin, step_end)) {
+        const std::string steps = "the steps [" + std::to_string(step_begin) + ", " + std::to_string(step_end) + ") of " + std::to_string(sh.N);
+        if (n_ranks < 1 || n_ranks > kSchurJointMaxRanks)
+            err = "n_ranks = " + std::to_string(n_ranks) + " is outside [1, " + std::to_string(kSchurJointMaxRanks) + "]";
+        else if (rank < 0 || rank >= n_ranks)
+            err = "rank = " + std::to_string(rank) + " is outside [0, n_ranks = " + std::to_string(n_ranks) + ")";
+        else if (rank > 0 && step_begin > 0 && step_end - step_begin < 2 && (rank == n_ranks - 1) == (step_end == sh.N))
+            err = steps + " hold the separator of rank " + std::to_string(rank) + " and no interior block: a rank >= 1 needs at least 2 steps";
+        else
+            err = steps + " cannot be block rank = " + std::to_string(rank) + " of n_ranks = " + std::to_string(n_ranks) +
+                  " ascending blocks of the grid";
+        return ST_EINVAL;
+    }
+    SchurCrPlan g{};
+    g.N = sh.N;
+    g.block_rows = sh.block_rows;
+    g.tail_rows = sh.tail_rows;
+    g.first_tail_row = sh.first_tail_row;
+    g.tail_cols = sh.tail_cols;
+    g.first_tail_col = sh.first_tail_col;
+    out = schur_cr_joint_cut(g, n_ranks, rank, step_begin, step_end);
+    if (!ranges) return ST_OK;
+    out.jvals_begin = sh.jvals_begin;
+    out.jvals_end = sh.jvals_end;
+    out.px_begin = sh.px_begin;
+    out.px_end = sh.px_end;
+    const int64_t h0 = step_end * sh.block_rows, h1 = h0 + sh.block_rows;
+    out.jvals_halo_begin = out.jvals_halo_end = sh.jvals_end;
+    if (step_end < sh.N) out.jvals_halo_end = h1 < mo.L.ncon ? mo.row_start(h1) : mo.nnzj;
+    return ST_OK;
+}
+
 int build_model(const HostDesc& d, Model& mo, std::string& err) {
     mo.problem = d.problem;
     mo.pattern_mode = d.pattern_mode;

@@ -283,8 +283,9 @@ __device__ __forceinline__ int slot_count(const double* slot) {
 // P (here and in the kernels below): the kernels' arguments, KrylovShardParams or, for the Schur form (ctd_krylov_shard_kernels.hpp),
 // KrylovSchurShardParams -- slots of kKrylovSchurSlot doubles, y and its term of the inner product left to the solve's launches on the
 // rows [s_lo, s_hi).  The instantiations for KrylovShardParams compile to the code without it
-template <class P> constexpr bool is_schur() { return std::is_same<P, KrylovSchurShardParams>::value; }
-template <class P> constexpr int slot_len() { return is_schur<P>() ? kKrylovSchurSlot : kKrylovSlot; }
+template <class P> constexpr bool is_joint() { return std::is_same<P, KrylovSchurJointParams>::value; }      // (the joined form)
+template <class P> constexpr bool is_schur() { return std::is_same<P, KrylovSchurShardParams>::value || is_joint<P>(); }
+template <class P> constexpr int slot_len() { return is_joint<P>() ? kKrylovSchurJointSlot : (is_schur<P>() ? kKrylovSchurSlot : kKrylovSlot); }
 // one running sum from 0.0: ranks ascending, within a rank the workgroups ascending; entry j of rows `stride` doubles apart; SLOT:
 // the doubles of a slot
 template <int SLOT> __device__ __forceinline__ double gathered_sum(const double* g, int n_ranks, int stride, int j) {
@@ -298,9 +299,9 @@ template <int SLOT> __device__ __forceinline__ double gathered_sum(const double*
     return s;
 }
 // the Schur form: the solves' partial sums of r2 . y added to the running sum s, ranks ascending, within a rank ascending
-__device__ __forceinline__ double gathered_schur_sum(double s, const double* g, int n_ranks) {
+template <int SLOT> __device__ __forceinline__ double gathered_schur_sum(double s, const double* g, int n_ranks) {
     for (int r = 0; r < n_ranks; ++r) {
-        const double* slot = g + (int64_t)r * kKrylovSchurSlot;
+        const double* slot = g + (int64_t)r * SLOT;
         const double c = slot[kSlotSchurCount];
         const int cnt = c >= 0.0 && c <= (double)kSlotSchurMax ? (int)c : 0;
 #pragma unroll 8
@@ -332,7 +333,7 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_init_kernel(const P
             sp.send_b[e] = c;
         }
         if constexpr (is_schur<P>()) {                  // (the solve's launches write their s_nwg partial sums behind this one)
-            for (int e = kSlotSchur + threadIdx.x; e < kKrylovSchurSlot; e += kKrylovBlock) {
+            for (int e = kSlotSchur + threadIdx.x; e < slot_len<P>(); e += kKrylovBlock) {
                 const double c = e == kSlotSchurCount ? (double)sp.s_nwg : 0.0;
                 sp.send_a[e] = c;
                 sp.send_b[e] = c;
@@ -377,7 +378,9 @@ template <class P>
 __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_first_kernel(const P sp) {
     const P& kp = sp;
     double b2 = gathered_sum<slot_len<P>()>(sp.gathered_a, sp.own.n_ranks, 1, 0);
-    if constexpr (is_schur<P>()) b2 = gathered_schur_sum(b2, sp.gathered_a, sp.own.n_ranks);
+    if constexpr (is_schur<P>()) b2 = gathered_schur_sum<slot_len<P>()>(b2, sp.gathered_a, sp.own.n_ranks);
+    if constexpr (is_joint<P>())
+        if (sp.own.n_ranks > 1) b2 += *sp.sigma;
     KrylovState t{};
     t.cs = -1.0;
     t.rtol = sp.meta->rtol;
@@ -507,7 +510,9 @@ __global__ void __launch_bounds__(kKrylovBlock) krylov_shard_update_kernel(const
             uu += q[3];
         }
     }
-    if constexpr (is_schur<P>()) b2 = gathered_schur_sum(b2, sp.gathered_b, sp.own.n_ranks);
+    if constexpr (is_schur<P>()) b2 = gathered_schur_sum<slot_len<P>()>(b2, sp.gathered_b, sp.own.n_ranks);
+    if constexpr (is_joint<P>())
+        if (sp.own.n_ranks > 1) b2 += *sp.sigma;
     const double alfa = *kp.alfa;
     KrylovState t = s;
     if (bad_beta2(b2)) {
@@ -603,6 +608,25 @@ hipError_t krylov_schur_shard_lanczos(const KrylovSchurShardParams& sp, hipStrea
 }
 hipError_t krylov_schur_shard_update(const KrylovSchurShardParams& sp, hipStream_t st) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_update_kernel<KrylovSchurShardParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    return hipGetLastError();
+}
+
+hipError_t krylov_schur_joint_start(const KrylovSchurJointParams& sp, const double* rhs, const double* px, const double* pc, int64_t nvar,
+                                    double rtol, int64_t max_iter, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_init_kernel<KrylovSchurJointParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp,
+                       rhs, px, pc, nvar, rtol, max_iter);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_joint_begin(const KrylovSchurJointParams& sp, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_first_kernel<KrylovSchurJointParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_joint_lanczos(const KrylovSchurJointParams& sp, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_lanczos_kernel<KrylovSchurJointParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
+    return hipGetLastError();
+}
+hipError_t krylov_schur_joint_update(const KrylovSchurJointParams& sp, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(krylov_shard_update_kernel<KrylovSchurJointParams>), dim3((unsigned)sp.nwg), dim3(kKrylovBlock), 0, st, sp);
     return hipGetLastError();
 }
 

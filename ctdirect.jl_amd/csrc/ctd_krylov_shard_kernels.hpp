@@ -62,6 +62,11 @@ constexpr int kSlotSchurMax = 256;                               // = kSchurMaxW
 constexpr int kSlotSchurCount = kSlotSchur + kSlotSchurMax;      // 2336
 constexpr int kKrylovSchurSlot = kSlotSchurCount + 16;           // 2352 = CTD_KKT_MINRES_SCHUR_SHARD_SLOT
 
+// the joined form's slot (ctd_kkt_minres_schur_cr_joint_*): the slot above, then the rank's solve record of
+// ctd_schur_cr_joint_kernels.hpp (kSchurJointSolveSlot = 16 + 3 * 64 doubles)
+constexpr int kSlotJoint = kKrylovSchurSlot;                     // 2352
+constexpr int kKrylovSchurJointSlot = kKrylovSchurSlot + 16 + 3 * 64;      // 2560 = CTD_KKT_MINRES_SCHUR_JOINT_SLOT
+
 // what start records for begin and for (B): the handle keeps no per-solve state
 struct KrylovShardMeta { double rtol; int64_t max_iter; int32_t precond, pad; };
 
@@ -159,5 +164,23 @@ hipError_t krylov_schur_shard_start(const KrylovSchurShardParams& sp, const doub
 hipError_t krylov_schur_shard_begin(const KrylovSchurShardParams& sp, hipStream_t st);
 hipError_t krylov_schur_shard_lanczos(const KrylovSchurShardParams& sp, hipStream_t st);
 hipError_t krylov_schur_shard_update(const KrylovSchurShardParams& sp, hipStream_t st);
+
+// THE JOINED FORM (ctd_kkt_minres_schur_cr_joint_*): M = blkdiag(diag(1 / px), T^-1, diag(1 / pc_tail)) with T^-1 applied by
+// ctd_kkt_schur_cr_joint_* (ctd_schur_cr_joint_kernels.hpp).  The Schur form above on slots of kKrylovSchurJointSlot doubles: [s_lo,
+// s_hi) are the rank's block rows, the separator's included; behind start's and (B)'s launch the caller enqueues the interior's
+// solve, whose last launch writes the partial sums of r_I . g_r where the shard form's solve writes its own, and the record kernel,
+// which writes the solve record at [kSlotJoint, kKrylovSchurJointSlot) of the same send slot: no gather is added.  begin and (C) are
+// preceded, in the same phase, by the two join launches (the reduced solve from the gathered records, which leaves sigma = x_s . rs~
+// at `sigma`; the correction of y on the rank's block rows).  ORDER OF beta1^2 AND beta^2: the running sum of the Schur form above --
+// the own terms, ranks ascending; the partial sums of r_I . g_r, ranks ascending --, then + sigma, once, when n_ranks > 1.  With
+// one rank there is no separator and sigma is not read: the order and the bits of the Schur form above.
+struct KrylovSchurJointParams : KrylovSchurShardParams {
+    const double* sigma;
+};
+hipError_t krylov_schur_joint_start(const KrylovSchurJointParams& sp, const double* rhs, const double* px, const double* pc, int64_t nvar,
+                                    double rtol, int64_t max_iter, hipStream_t st);
+hipError_t krylov_schur_joint_begin(const KrylovSchurJointParams& sp, hipStream_t st);
+hipError_t krylov_schur_joint_lanczos(const KrylovSchurJointParams& sp, hipStream_t st);
+hipError_t krylov_schur_joint_update(const KrylovSchurJointParams& sp, hipStream_t st);
 
 }  // namespace ctd

@@ -100,4 +100,82 @@ inline SchurCrShardPlan schur_cr_shard_cut(const SchurCrPlan& g, int64_t step_be
 int plan_kkt_schur_cr_shard(const Model& m, int64_t step_begin, int64_t step_end, bool verify, bool ranges, SchurCrShardPlan& out,
                             std::string& err);
 
+// ---- the joined form (ctd_kkt_schur_cr_joint_*): the shard form with the couplings across the ranks restored ---------------------------
+// Rank r of n_ranks holds the steps [step_begin, step_end).  Every rank but rank 0 gives up its first block as a separator; its
+// interior, the blocks [int_begin, step_end) with int_begin = step_begin + (rank > 0), is factored exactly by the recurrences above
+// (n_int blocks through offset pointers, as the shard form does), and the n_ranks - 1 separators are joined by a reduced block
+// tridiagonal system that every rank factors redundantly (kernels, records and orders: ctd_schur_cr_joint_kernels.hpp).
+constexpr int kSchurJointMaxRanks = 256;    // accepted n_ranks: the reduced sweep over n_ranks - 1 blocks is sequential, one wave
+constexpr int64_t kSchurJointHead = 16;     // doubles of a record before its blocks / vectors
+constexpr int64_t schur_cr_joint_factor_slot(int64_t m) { return kSchurJointHead + 4 * m * m; }       // (sb, se, m, rank; D_s, Cll, Crl, Crr)
+constexpr int64_t kSchurJointSolveSlot = kSchurJointHead + 3 * kSchurMaxBlock;                     // (rank; r_s, qu, qd: 64 apart)
+
+// Offsets in doubles into the workspace.  [0, off_es): the workspace of the log-depth form for the interior (with this family's tag
+// in word 0 of the header and, behind the words of the shard form, step_begin, step_end, n_ranks and rank in the words 5 .. 8); then
+// E[s] = T(int_begin, s), E[b] = T(step_end, step_end - 1) and D_s (m^2 each, zero where the rank has none); the spikes Wl and Wr
+// (n_int m^2 each, block k row-major m x m); the scratch of the multi-column solve (2 m columns of n_int m running right-hand sides,
+// then as many of y); the reduced factor (n_sep status words, n_sep blocks L_k, n_sep blocks F_k; n_sep = max(n_ranks - 1, 1)); rs~
+// and x_s (n_sep m each); sigma (16, the first is used)
+struct SchurCrJointPlan {
+    int64_t N, n_ranks, rank, step_begin, step_end, separator, int_begin, n_int, block_rows, first_row, tail_rows, first_tail_row, tail_cols,
+        first_tail_col, n_levels, n_sep, factor_local_launches, factor_join_launches, solve_local_launches, solve_join_launches, factor_slot,
+        solve_slot, off_es, off_eb, off_ds, off_wl, off_wr, off_scratch, off_reduced, off_rs, off_xs, off_sigma, workspace, jvals_begin,
+        jvals_end, jvals_halo_begin, jvals_halo_end, px_begin, px_end;
+};
+// what the step range and the rank must satisfy: inside the grid, able to be block `rank` of n_ranks ascending blocks, and at least
+// one interior block behind the separator
+inline bool schur_cr_joint_range_ok(int64_t N, int64_t n_ranks, int64_t rank, int64_t sb, int64_t se) {
+    if (!schur_cr_shard_range_ok(N, sb, se) || n_ranks < 1 || n_ranks > kSchurJointMaxRanks || rank < 0 || rank >= n_ranks) return false;
+    if ((rank == 0) != (sb == 0) || (rank == n_ranks - 1) != (se == N)) return false;
+    return rank == 0 || se - sb >= 2;
+}
+// the fields that are functions of the grid's plan, the step range and the rank alone (no model): everything but the read set
+inline SchurCrJointPlan schur_cr_joint_cut(const SchurCrPlan& g, int64_t n_ranks, int64_t rank, int64_t sb, int64_t se) {
+    SchurCrJointPlan s{};
+    const int64_t m = g.block_rows, mm = m * m;
+    s.N = g.N;
+    s.n_ranks = n_ranks;
+    s.rank = rank;
+    s.step_begin = sb;
+    s.step_end = se;
+    s.separator = rank > 0 ? sb : -1;
+    s.int_begin = sb + (rank > 0 ? 1 : 0);
+    s.n_int = se - s.int_begin;
+    s.block_rows = m;
+    s.first_row = sb * m;
+    s.tail_rows = g.tail_rows;
+    s.first_tail_row = g.first_tail_row;
+    s.tail_cols = g.tail_cols;
+    s.first_tail_col = g.first_tail_col;
+    s.n_levels = schur_cr_levels(s.n_int);
+    s.n_sep = n_ranks > 1 ? n_ranks - 1 : 1;
+    // local factor: the interior's factor; with more than one rank the interface assemble, the multi-column solve, the contributions
+    s.factor_local_launches = schur_cr_factor_launches(s.n_int) + (n_ranks > 1 ? schur_cr_solve_launches(s.n_int) + 2 : 0);
+    s.factor_join_launches = n_ranks > 1 ? 1 : 0;       // the reduced matrix from the records and its block Cholesky, one wave
+    s.solve_local_launches = schur_cr_solve_launches(s.n_int) + (n_ranks > 1 ? 1 : 0);        // ... and the record
+    s.solve_join_launches = n_ranks > 1 ? 2 : 0;        // rs~, the reduced sweeps and sigma, one wave; the correction
+    s.factor_slot = schur_cr_joint_factor_slot(m);
+    s.solve_slot = kSchurJointSolveSlot;
+    s.off_es = schur_cr_workspace(s.n_int, m);
+    s.off_eb = s.off_es + mm;
+    s.off_ds = s.off_eb + mm;
+    s.off_wl = s.off_ds + mm;
+    s.off_wr = s.off_wl + s.n_int * mm;
+    s.off_scratch = s.off_wr + s.n_int * mm;
+    s.off_reduced = s.off_scratch + 4 * s.n_int * mm;
+    s.off_rs = s.off_reduced + s.n_sep + 2 * s.n_sep * mm;
+    s.off_xs = s.off_rs + s.n_sep * m;
+    s.off_sigma = s.off_xs + s.n_sep * m;
+    s.workspace = s.off_sigma + 16;
+    return s;
+}
+// The refusals and the pattern check of plan_kkt_schur_cr, then schur_cr_joint_range_ok (ST_EINVAL, with the reason), then the
+// fields.  ranges: the read set of the factor.  jvals on [jvals_begin, jvals_end), the CSR range of the rank's own block rows (the
+// separator's included), and on the halo [jvals_halo_begin, jvals_halo_end), the CSR range of the rows of block step_end, which
+// E[b] reads (empty on the last rank; it lies right behind the rank's own range).  px on [px_begin, px_end), the span of the non-tail
+// columns of the rank's own rows: E[b] adds over the columns that a row of block step_end shares with a row of block step_end - 1,
+// which lie inside that span
+int plan_kkt_schur_cr_joint(const Model& m, int64_t n_ranks, int64_t rank, int64_t step_begin, int64_t step_end, bool verify, bool ranges,
+                            SchurCrJointPlan& out, std::string& err);
+
 }  // namespace ctd

@@ -31,10 +31,14 @@ to that stream): nothing here synchronises with the host.
 """
 import os
 
+import ctypes as C
+
+import numpy as np
 import torch
 import torch.distributed as dist
 
-from .docp import SchurCrShardPrecond
+from . import _lib
+from .docp import SchurCrJointPrecond, SchurCrShardPrecond
 
 # Rehearsal knob: run the collectives on a ONE-rank group too (they are no-ops for the data, but every RCCL call of the
 # multi-GPU path -- in-place / padded all-gather, halo all-gather, all-reduce, broadcast -- is issued exactly as on 8 GPUs),
@@ -190,16 +194,26 @@ class MinresPhases:
         self.schur = isinstance(ranks[0].precond, SchurCrShardPrecond)
         if any(isinstance(r.precond, SchurCrShardPrecond) != self.schur for r in ranks):
             raise ValueError("precond: a SchurCrShardPrecond on every shard or on none")
+        # ... or a SchurCrJointPrecond per rank (factored AND joined): the family ctd_kkt_minres_schur_cr_joint_*, whose slots also carry
+        # the solve records; begin and (C) take the factor's workspace
+        self.joint = isinstance(ranks[0].precond, SchurCrJointPrecond)
+        if any(isinstance(r.precond, SchurCrJointPrecond) != self.joint for r in ranks):
+            raise ValueError("precond: a SchurCrJointPrecond on every shard or on none")
 
     def start(self, rtol, max_iter):
         for r in self.ranks:
-            if self.schur:
+            if self.joint:
+                r.docp.kkt_minres_schur_joint_start(r.precond, r.rhs, r.z, r.w, r.rank, rtol=rtol, max_iter=max_iter)
+            elif self.schur:
                 r.docp.kkt_minres_schur_shard_start(r.precond, r.rhs, r.z, r.w, r.rank, rtol=rtol, max_iter=max_iter)
             else:
                 r.docp.kkt_minres_shard_start(r.rhs, r.z, r.w, r.rank, precond=r.precond, rtol=rtol, max_iter=max_iter)
         self.gather("a")
         for r in self.ranks:
-            (r.docp.kkt_minres_schur_shard_begin if self.schur else r.docp.kkt_minres_shard_begin)(r.w, r.rank)
+            if self.joint:
+                r.docp.kkt_minres_schur_joint_begin(r.precond, r.w, r.rank)
+            else:
+                (r.docp.kkt_minres_schur_shard_begin if self.schur else r.docp.kkt_minres_shard_begin)(r.w, r.rank)
 
     def iterate(self, k):
         """k iterations: per iteration the halo of v, K v (two launches per rank), (A), the gather of slot A, (B), the gather of
@@ -208,19 +222,27 @@ class MinresPhases:
             self.halo()
             for r in self.ranks:
                 r.docp.kktprod_shard(r.x, r.y, r.w.v_x, r.w.v_c, r.sigma, r.sx, r.sc, out=(r.w.kv_x, r.w.kv_c))
-                (r.docp.kkt_minres_schur_shard_alfa if self.schur else r.docp.kkt_minres_shard_alfa)(r.z, r.w, r.rank)
+                alfa = r.docp.kkt_minres_schur_joint_alfa if self.joint else (r.docp.kkt_minres_schur_shard_alfa if self.schur else r.docp.kkt_minres_shard_alfa)
+                alfa(r.z, r.w, r.rank)
             self.gather("a")
             for r in self.ranks:
-                if self.schur:
+                if self.joint:
+                    r.docp.kkt_minres_schur_joint_lanczos(r.precond, r.z, r.w, r.rank)
+                elif self.schur:
                     r.docp.kkt_minres_schur_shard_lanczos(r.precond, r.z, r.w, r.rank)
                 else:
                     r.docp.kkt_minres_shard_lanczos(r.z, r.w, r.rank)
             self.gather("b")
             for r in self.ranks:
-                (r.docp.kkt_minres_schur_shard_update if self.schur else r.docp.kkt_minres_shard_update)(r.z, r.w, r.rank)
+                if self.joint:
+                    r.docp.kkt_minres_schur_joint_update(r.precond, r.z, r.w, r.rank)
+                else:
+                    (r.docp.kkt_minres_schur_shard_update if self.schur else r.docp.kkt_minres_shard_update)(r.z, r.w, r.rank)
 
     def infos(self):
         """every rank's MinresInfo: the one host read per chunk"""
+        if self.joint:
+            return [r.docp.kkt_minres_schur_joint_info(r.w) for r in self.ranks]
         return [(r.docp.kkt_minres_schur_shard_info if self.schur else r.docp.kkt_minres_shard_info)(r.w) for r in self.ranks]
 
     def solve(self, rtol, max_iter, check_every, on_chunk=None):
@@ -262,7 +284,9 @@ def minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond
     xs: one x per handle (a shard's own entries and the halo it reads valid, or the table of `set_x_shards` set); y, rhs, sx, sc:
     full-length tensors shared by the shards, or one per shard (a list); precond: None, a pair (px, pc), one pair per shard, or one
     SchurCrShardPrecond per shard (`DOCP.kkt_schur_cr_shard_factor`: the log-depth Schur preconditioner, exact inside a shard and cut
-    at the shard boundaries; the workspaces are then those of `DOCP.kkt_minres_schur_shard_workspace`).
+    at the shard boundaries; the workspaces are then those of `DOCP.kkt_minres_schur_shard_workspace`), or one SchurCrJointPrecond per
+    shard (`kkt_schur_cr_joint_shards`, which also does the factor-time gather as device copies: the couplings across the shards
+    restored; workspaces of `DOCP.kkt_minres_schur_joint_workspace`).
     out / workspaces: one z / one MinresShardWorkspace per shard, allocated when None.  The gathers are device copies of every
     send slot into every shard's gathered area; the halo of the Lanczos vector is copied from the owners' vectors."""
     G = len(handles)
@@ -275,7 +299,10 @@ def minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond
     for k, h in enumerate(handles):
         if h._stream_raw != cur:
             h.set_stream(cur)
-        new_ws = h.kkt_minres_schur_shard_workspace if isinstance(pres[k], SchurCrShardPrecond) else h.kkt_minres_shard_workspace
+        if isinstance(pres[k], SchurCrJointPrecond):
+            new_ws = lambda G, h=h, k=k: h.kkt_minres_schur_joint_workspace(G, k)      # noqa: E731
+        else:
+            new_ws = h.kkt_minres_schur_shard_workspace if isinstance(pres[k], SchurCrShardPrecond) else h.kkt_minres_shard_workspace
         w = workspaces[k] if workspaces is not None else new_ws(G)
         z = out[k] if out is not None else torch.empty(w.layout.n, dtype=torch.float64, device=dev)
         ranks.append(_MinresRank(h, k, w, z, xs[k], ys[k], obj_weight, sxs[k], scs[k], rhss[k], pres[k]))
@@ -318,6 +345,47 @@ def kkt_minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, pre
     return [r.z for r in ph.ranks], infos
 
 
+def kkt_schur_cr_joint_shards(handles, jvals, px, pc, sc):
+    """The joined form of the log-depth Schur preconditioner (ctd_kkt_schur_cr_joint_*) over shard handles that are ALL in this
+    process, in ascending order of their steps, on one GPU and one stream (torch's current one): every rank's local factor, the
+    all-gather of the factor records as device copies, every rank's join.  jvals, px, pc, sc: full-length tensors shared by the
+    shards, or one per shard (a list); a shard's jvals must be valid on its own range and on the halo its layout names.  Returns one
+    SchurCrJointPrecond per shard, for `kkt_schur_cr_joint_apply_shards`."""
+    G = len(handles)
+    per = lambda a: list(a) if isinstance(a, (list, tuple)) else [a] * G      # noqa: E731
+    jv, pxs, pcs, scs = per(jvals), per(px), per(pc), per(sc)
+    cur = torch.cuda.current_stream(pxs[0].device).cuda_stream
+    for h in handles:
+        if h._stream_raw != cur:
+            h.set_stream(cur)
+    Ps = [h.kkt_schur_cr_joint_factor_local(jv[k], pxs[k], pcs[k], scs[k], G, k) for k, h in enumerate(handles)]
+    if G == 1:
+        return Ps
+    gathered = torch.cat([P.send for P in Ps])
+    for h, P in zip(handles, Ps):
+        h.kkt_schur_cr_joint_factor_join(P, gathered)
+    return Ps
+
+
+def kkt_schur_cr_joint_apply_shards(handles, Ps, r, out=None):
+    """out = T^-1 r on the block rows with the factors of `kkt_schur_cr_joint_shards`: every rank's local solve, the all-gather of the
+    solve records as device copies, every rank's join.  r: ncon entries, shared by the shards or one per shard (a rank reads its own
+    block rows); out: one tensor of ncon entries -- every rank writes its own block rows of it, the tail rows are left untouched -- or
+    one per shard; zeros when None.  Enqueue-only but for the allocation; returns out."""
+    G = len(handles)
+    rs = list(r) if isinstance(r, (list, tuple)) else [r] * G
+    if out is None:
+        out = torch.zeros_like(rs[0])
+    outs = list(out) if isinstance(out, (list, tuple)) else [out] * G
+    for k, (h, P) in enumerate(zip(handles, Ps)):
+        h.kkt_schur_cr_joint_solve_local(P, rs[k], outs[k])
+    if G > 1:
+        gathered = torch.cat([P.xsend for P in Ps])
+        for k, (h, P) in enumerate(zip(handles, Ps)):
+            h.kkt_schur_cr_joint_solve_join(P, gathered, outs[k], sync=False)
+    return out
+
+
 class ShardedDOCP:
     """One rank's view of a grid-sharded transcription.  `make_docp(steps=(begin, end))` builds the engine handle
     (ctdirect DOCP) for the rank's block of steps."""
@@ -348,6 +416,7 @@ class ShardedDOCP:
         self._f = None
         self._minres_ws = None              # the workspace of `kkt_minres`, kept between solves
         self._minres_schur_ws = None        # ... and of its solves with a SchurCrShardPrecond (larger slots)
+        self._minres_joint_ws = None        # ... with a SchurCrJointPrecond (larger again)
         self._peer = None                   # data_ptr of the x buffer the peer table is ACTIVE for (enable_peer_x), None: off
         self._peer_tables = {}              # x data_ptr -> (the tensor itself, mapped pointers of the other ranks' buffers): the
                                             # tensor is kept alive so the allocator cannot hand its address to another buffer
@@ -871,6 +940,53 @@ class ShardedDOCP:
             self.cons_jac(x, c, jvals, stitch=False)
         return d.kkt_schur_cr_shard_factor(jvals, px, pc, sc)
 
+    def exchange_jvals_block_halo(self, jvals):
+        """The joined form of the Schur preconditioner: fills, inside this rank's full-length Jacobian values (CSR order), the values
+        of the rows of block `step_end` -- the next rank's first block, which E[b] = T(step_end, step_end - 1) reads
+        (`ctd_kkt_schur_cr_joint_layout`: [jvals_halo_begin, jvals_halo_end)) -- with ONE all-gather, shaped like
+        `exchange_product_halo`: every rank sends the values of the rows of its own first block, padded to the longest block of
+        the grid so that all ranks send alike."""
+        def build():
+            d = self.docp
+            rowptr = np.empty(d.dim_NLP_constraints + 1, dtype=np.int64)
+            colind = np.empty(d.nnzj, dtype=np.int64)
+            d._ck(_lib.lib().ctd_jac_csr(d._h, rowptr.ctypes.data_as(C.POINTER(C.c_int64)), colind.ctypes.data_as(C.POINTER(C.c_int64))))
+            m = int(d.kkt_schur_cr_shard_layout().block_rows)
+            (b, e), r, G, N, ar = self.steps, self.rank, self.world, self.N, torch.arange
+            L = int(max(rowptr[(k + 1) * m] - rowptr[k * m] for k in range(N)))
+            pack = [torch.clamp(int(rowptr[b * m]) + ar(L), max=d.nnzj - 1)]        # (the padding repeats the last value: never read)
+            dst, src = [], []
+            if r + 1 < G:
+                Lh = int(rowptr[(e + 1) * m] - rowptr[e * m])
+                dst, src = [int(rowptr[e * m]) + ar(Lh)], [(r + 1) * L + ar(Lh)]
+            return pack, dst, src
+        return self._exchange(jvals, "jvals_block", build)
+
+    def kkt_schur_cr_joint_precond(self, x, y, obj_weight=1.0, sx=None, sc=None, floor=1e-8, jvals=None, x_halo_valid=False,
+                                   y_halo_valid=False):
+        """`kkt_schur_cr_precond` with the couplings across the ranks restored (`ctd_kkt_schur_cr_joint_*`): T^-1 itself on the block
+        rows.  Every rank but the first gives up its first block as a separator (it needs at least two steps).  Built like
+        `kkt_schur_cr_precond`, with TWO more collectives, at factor time only: one small halo exchange of the Jacobian values
+        (`exchange_jvals_block_halo`) and one all-gather of the factor records, after which every rank factors the same reduced
+        system.  Returns the SchurCrJointPrecond for `kkt_minres(precond=P)`.  Inputs as `kkt_diag_precond`."""
+        d = self.docp
+        px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc, floor, x_halo_valid, y_halo_valid)
+        self.exchange_product_halo(px)
+        if jvals is None:
+            jvals = torch.empty(d.nnzj, dtype=torch.float64, device=x.device)
+            c = torch.empty(d.dim_NLP_constraints, dtype=torch.float64, device=x.device)
+            self.cons_jac(x, c, jvals, stitch=False)
+        self.exchange_jvals_block_halo(jvals)
+        cur = torch.cuda.current_stream(x.device).cuda_stream
+        if d._stream_raw != cur:
+            d.set_stream(cur)
+        P = d.kkt_schur_cr_joint_factor_local(jvals, px, pc, sc, self.world, self.rank)
+        if self.world > 1:
+            gathered = torch.empty(self.world * P.layout.factor_slot, dtype=torch.float64, device=x.device)
+            _all_gather_into(gathered, P.send, self.group)
+            d.kkt_schur_cr_joint_factor_join(P, gathered)
+        return P
+
     def kkt_minres(self, x, y, rhs, obj_weight=1.0, sx=None, sc=None, precond=None, rtol=1e-10, max_iter=None, check_every=16,
                    out=None, x_halo_valid=False, y_halo_valid=False):
         """`DOCP.kkt_minres` of the sharded transcription: preconditioned MINRES on K z = rhs with K the operator of `kktprod`,
@@ -878,7 +994,9 @@ class ShardedDOCP:
         is full-length with this rank's own entries valid (x, rhs, px: + the nv tail; sx: the nv tail on the last rank only; y, sx,
         sc may be None).  precond: None, a pair (px, pc), or "diag": the pair of `kkt_diag_precond`; a SchurCrShardPrecond P of
         `kkt_schur_cr_precond`, or "schur_cr": that of `kkt_schur_cr_precond(x, y, obj_weight, sx, sc)` (the phases
-        `ctd_kkt_minres_schur_cr_shard_*`: the same three gathers on larger slots, no collective added).  Returns (z, MinresInfo): z
+        `ctd_kkt_minres_schur_cr_shard_*`: the same three gathers on larger slots, no collective added); a SchurCrJointPrecond P of
+        `kkt_schur_cr_joint_precond`, or "schur_cr_joint": the same with the couplings across the ranks restored (the phases
+        `ctd_kkt_minres_schur_cr_joint_*`: the same three gathers on slots that also carry the solve records).  Returns (z, MinresInfo): z
         full-length, this rank's own entries and the nv tail valid (`out`: z).
         The halos of x and y are exchanged once before the loop (`x_halo_valid`, `y_halo_valid`: as in `kktprod`).  Per iteration:
         the halo of the Lanczos vector (`exchange_kkt_halo`), the two launches of `kktprod_shard`, three vector launches and two
@@ -896,12 +1014,19 @@ class ShardedDOCP:
         if y is not None and not y_halo_valid:
             self.exchange_product_rows(y)
         if isinstance(precond, str):
-            if precond not in ("diag", "schur_cr"):
-                raise ValueError(f'precond is None, a pair (px, pc), a SchurCrShardPrecond, "diag" or "schur_cr", not {precond!r}')
-            build = self.kkt_diag_precond if precond == "diag" else self.kkt_schur_cr_precond
+            if precond not in ("diag", "schur_cr", "schur_cr_joint"):
+                raise ValueError('precond is None, a pair (px, pc), a SchurCrShardPrecond, a SchurCrJointPrecond, "diag", "schur_cr" or '
+                                 f'"schur_cr_joint", not {precond!r}')
+            build = {"diag": self.kkt_diag_precond, "schur_cr": self.kkt_schur_cr_precond, "schur_cr_joint": self.kkt_schur_cr_joint_precond}[precond]
             precond = build(x, y, obj_weight, sx, sc, x_halo_valid=True, y_halo_valid=True)
         collective = self.world > 1 or _FORCE
-        if isinstance(precond, SchurCrShardPrecond):
+        if isinstance(precond, SchurCrJointPrecond):      # (slots that also carry the solve records: a workspace of its own)
+            if (precond.layout.n_ranks, precond.layout.rank) != (self.world, self.rank):
+                raise ValueError(f"precond was factored as rank {precond.layout.rank} of {precond.layout.n_ranks}, this is rank {self.rank} of {self.world}")
+            w = self._minres_joint_ws
+            if w is None or w.ws.device != x.device:
+                w = self._minres_joint_ws = d.kkt_minres_schur_joint_workspace(self.world, self.rank)
+        elif isinstance(precond, SchurCrShardPrecond):
             w = self._minres_schur_ws
             if w is None or w.ws.device != x.device:
                 w = self._minres_schur_ws = d.kkt_minres_schur_shard_workspace(self.world)

@@ -117,6 +117,9 @@ SchurCrPrecond = namedtuple("SchurCrPrecond", "px pc ws layout")
 # ... and the shard form of that, of DOCP.kkt_schur_cr_shard_factor: the factor of the handle's own steps (layout:
 # ctd_schur_cr_shard_layout); px, pc full-length, valid where the shard reads them
 SchurCrShardPrecond = namedtuple("SchurCrShardPrecond", "px pc ws layout")
+# ... and the joined form of that, of DOCP.kkt_schur_cr_joint_factor_local: the rank's local factor and, after the join, the reduced
+# factor (layout: ctd_schur_cr_joint_layout); send, xsend: the rank's factor record and solve record
+SchurCrJointPrecond = namedtuple("SchurCrJointPrecond", "px pc ws layout send xsend")
 MinresShardWorkspace = namedtuple("MinresShardWorkspace", "ws layout n_ranks v_x v_c kv_x kv_c send_a send_b gathered_a gathered_b")
 
 
@@ -828,6 +831,83 @@ class DOCP:
         self._ck(_lib.lib().ctd_kkt_schur_cr_shard_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
         return bad.value
 
+    # ---- the joined form of the log-depth Schur preconditioner (ctd_kkt_schur_cr_joint_*): the couplings across the ranks restored ----
+    def kkt_schur_cr_joint_layout(self, n_ranks, rank):
+        """`ctd_kkt_schur_cr_joint_layout`: the handle's steps as rank `rank` of n_ranks -- the separator (its first block; -1 on rank 0),
+        the interior [int_begin, step_end) of n_int blocks, the launch counts of the four phases, the record slots, the offsets into
+        the workspace (doubles) and the read set of the factor: that of the shard form and the halo of jvals, [jvals_halo_begin,
+        jvals_halo_end).  Works on host-only handles."""
+        lay = _lib.ctd_schur_cr_joint_layout(struct_size=C.sizeof(_lib.ctd_schur_cr_joint_layout))
+        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_layout(self._h, int(n_ranks), int(rank), C.byref(lay)))
+        return lay
+
+    def kkt_schur_cr_joint_factor_local(self, jvals, px, pc, sc, n_ranks, rank, ws=None, send=None, xsend=None):
+        """`ctd_kkt_schur_cr_joint_factor_local_dev_async`: the interface blocks, the factor of the interior, the spikes and the
+        factor record, written into send (layout.factor_slot doubles).  The caller gathers the records of all ranks in rank order
+        and hands them to `kkt_schur_cr_joint_factor_join`.  Returns the SchurCrJointPrecond (px, pc, ws, layout, send, xsend);
+        xsend (layout.solve_slot doubles) is where `kkt_schur_cr_joint_solve_local` puts the solve record.  ws, send and xsend are
+        allocated when None; with all three given (send and xsend may stay None with one rank, which has no record) the call
+        allocates nothing and waits for nothing: enqueue-only, like the C entry point."""
+        self._tensors_only("kkt_schur_cr_joint_factor_local", jvals=jvals, px=px, pc=pc, sc=sc, ws=ws, send=send, xsend=xsend)
+        lay = self.kkt_schur_cr_joint_layout(n_ranks, rank)
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        fresh = ws is None or (lay.n_ranks > 1 and (send is None or xsend is None))
+        if fresh:
+            import torch
+            if ws is None:
+                ws = torch.empty(lay.workspace, dtype=torch.float64, device=px.device)
+            if lay.n_ranks > 1:
+                send = torch.zeros(lay.factor_slot, dtype=torch.float64, device=px.device) if send is None else send
+                xsend = torch.zeros(lay.solve_slot, dtype=torch.float64, device=px.device) if xsend is None else xsend
+            torch.cuda.current_stream(px.device).synchronize()       # (the zeros are there before the handle's stream writes)
+        self._dev_ptr(pc, ncon, "pc")
+        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_factor_local_dev_async(
+            self._h, self._dev_ptr(jvals, self.nnzj, "jvals"), self._dev_ptr(px, nvar, "px"), self._dev_ptr(sc, ncon, "sc"),
+            self._dev_ptr(ws, lay.workspace, "ws"), self._dev_ptr(send, lay.factor_slot, "send"), int(n_ranks), int(rank)))
+        return SchurCrJointPrecond(px, pc, ws, lay, send, xsend)
+
+    def kkt_schur_cr_joint_factor_join(self, P, gathered):
+        """`ctd_kkt_schur_cr_joint_factor_join_dev_async`: the reduced matrix from the n_ranks gathered records (rank order,
+        layout.factor_slot doubles apart) and its factor, into P's workspace.  Nothing is launched with one rank (gathered may be None)."""
+        self._tensors_only("kkt_schur_cr_joint_factor_join", ws=P.ws, gathered=gathered)
+        lay = P.layout
+        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_factor_join_dev_async(
+            self._h, self._dev_ptr(P.ws, lay.workspace, "ws"), self._dev_ptr(gathered, lay.n_ranks * lay.factor_slot, "gathered"),
+            lay.n_ranks, lay.rank))
+
+    def kkt_schur_cr_joint_solve_local(self, P, r, out, send=None):
+        """`ctd_kkt_schur_cr_joint_solve_local_dev_async`: out = A^-1 r on the rank's interior rows and the solve record into send
+        (P.xsend when None; layout.solve_slot doubles).  r, out: ncon entries, out must not be r.  Returns send."""
+        self._tensors_only("kkt_schur_cr_joint_solve_local", r=r, out=out, ws=P.ws, send=send)
+        lay, ncon = P.layout, self.dim_NLP_constraints
+        send = P.xsend if send is None else send
+        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_solve_local_dev_async(
+            self._h, self._dev_ptr(P.ws, lay.workspace, "ws"), self._dev_ptr(r, ncon, "r"), self._dev_ptr(out, ncon, "out"),
+            self._dev_ptr(send, lay.solve_slot, "send"), lay.n_ranks, lay.rank))
+        return send
+
+    def kkt_schur_cr_joint_solve_join(self, P, gathered, out, sync=True):
+        """`ctd_kkt_schur_cr_joint_solve_join_dev_async`: the reduced solve from the n_ranks gathered solve records, then out = T^-1 r
+        on the rank's block rows (the separator's rows and the correction of the interior rows `kkt_schur_cr_joint_solve_local`
+        left in out).  Nothing else of out is written; nothing is launched with one rank."""
+        self._tensors_only("kkt_schur_cr_joint_solve_join", out=out, ws=P.ws, gathered=gathered)
+        lay = P.layout
+        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_solve_join_dev_async(
+            self._h, self._dev_ptr(P.ws, lay.workspace, "ws"), self._dev_ptr(gathered, lay.n_ranks * lay.solve_slot, "gathered"),
+            self._dev_ptr(out, self.dim_NLP_constraints, "out"), lay.n_ranks, lay.rank))
+        if sync:
+            self.sync()
+        return out
+
+    def kkt_schur_cr_joint_info(self, P):
+        """`ctd_kkt_schur_cr_joint_info`: waits for the handle's stream; -1 when every pivot was positive, otherwise the smallest GLOBAL
+        block with a recorded pivot among the rank's interior and the separators of the reduced factor."""
+        self._tensors_only("kkt_schur_cr_joint_info", ws=P.ws)
+        bad = C.c_int64(0)
+        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), P.layout.n_ranks, P.layout.rank,
+                                                        C.byref(bad)))
+        return bad.value
+
     # ---- device-resident preconditioned MINRES solve of K z = rhs (ctd_kkt_minres*) ---------------------------------------------
     def _kkt_system(self, fn, vecs, obj_weight, host_ok):
         """The ctd_kkt_system of a solve and the pointers of its other vectors.  vecs: (name, array, layout, required) rows, x
@@ -991,7 +1071,12 @@ class DOCP:
                                     cut(lay.off_kv + nvar, n - nvar), cut(lay.off_send_a, slot), cut(lay.off_send_b, slot),
                                     cut(lay.off_gathered_a, G * slot), cut(lay.off_gathered_b, G * slot))
 
-    def _shard_ws_ptr(self, w):
+    def _shard_ws_ptr(self, w, slot):
+        """the workspace's pointer, for the phase family whose slots have `slot` doubles: the C side lays the pointer out with its
+        own slot length and cannot know the tensor's, so a workspace cut for another family never reaches a kernel"""
+        if w.layout.slot != slot:
+            raise ValueError(f"the workspace was cut with slots of {w.layout.slot} doubles, this phase family needs {slot}: take it from "
+                             "the family's own kkt_minres_*_workspace")
         return self._dev_ptr(w.ws, w.layout.workspace, "ws")
 
     def kkt_minres_shard_start(self, rhs, z, w, rank, precond=None, rtol=1e-10, max_iter=None):
@@ -1008,15 +1093,18 @@ class DOCP:
         if px is not None:
             sys.px, sys.pc = self._dev_ptr(px, nvar, "px").value, self._dev_ptr(pc, ncon, "pc").value
         self._ck(_lib.lib().ctd_kkt_minres_shard_start_dev_async(
-            self._h, C.byref(sys), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"), self._shard_ws_ptr(w),
+            self._h, C.byref(sys), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SHARD_SLOT),
             w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
 
     def kkt_minres_shard_begin(self, w, rank):
         """`ctd_kkt_minres_shard_begin_dev_async`: beta1 from w.gathered_a, the first Lanczos vector, the state."""
-        self._ck(_lib.lib().ctd_kkt_minres_shard_begin_dev_async(self._h, self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+        self._ck(_lib.lib().ctd_kkt_minres_shard_begin_dev_async(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SHARD_SLOT), w.n_ranks, int(rank)))
 
     def _shard_phase(self, fn, z, w, rank):
-        self._ck(fn(self._h, self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+        name = fn.__name__          # (the phase family is in the entry point's name)
+        slot = _lib.KKT_MINRES_SCHUR_JOINT_SLOT if "schur_cr_joint" in name else (
+            _lib.KKT_MINRES_SCHUR_SHARD_SLOT if "schur_cr_shard" in name else _lib.KKT_MINRES_SHARD_SLOT)
+        self._ck(fn(self._h, self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, slot), w.n_ranks, int(rank)))
 
     def kkt_minres_shard_alfa(self, z, w, rank):
         """`ctd_kkt_minres_shard_alfa_dev_async`: phase (A), after `kktprod_shard` wrote K v into (w.kv_x, w.kv_c)."""
@@ -1033,7 +1121,7 @@ class DOCP:
     def kkt_minres_shard_info(self, w):
         """`ctd_kkt_minres_shard_info`: waits for the handle's stream and returns the MinresInfo in the workspace's state."""
         info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
-        self._ck(_lib.lib().ctd_kkt_minres_shard_info(self._h, self._shard_ws_ptr(w), w.n_ranks, C.byref(info)))
+        self._ck(_lib.lib().ctd_kkt_minres_shard_info(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SHARD_SLOT), w.n_ranks, C.byref(info)))
         return self._minres_info(info)
 
     # ---- ... with the shard form of the log-depth Schur preconditioner (ctd_kkt_minres_schur_cr_shard_*): the same phases on
@@ -1062,11 +1150,11 @@ class DOCP:
         sys.px, sys.pc = self._dev_ptr(P.px, nvar, "px").value, self._dev_ptr(P.pc, ncon, "pc").value
         self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_start_dev_async(
             self._h, C.byref(sys), self._schur_ws_ptr(P), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"),
-            self._shard_ws_ptr(w), w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+            self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
 
     def kkt_minres_schur_shard_begin(self, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_begin_dev_async`"""
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_begin_dev_async(self._h, self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_begin_dev_async(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, int(rank)))
 
     def kkt_minres_schur_shard_alfa(self, z, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_alfa_dev_async`: phase (A)"""
@@ -1076,7 +1164,7 @@ class DOCP:
         """`ctd_kkt_minres_schur_cr_shard_lanczos_dev_async`: phase (B), the solve with P's factor on the handle's block rows, and
         its partial sums into w.send_b"""
         self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(
-            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w), w.n_ranks, int(rank)))
+            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, int(rank)))
 
     def kkt_minres_schur_shard_update(self, z, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_update_dev_async`: phase (C)"""
@@ -1085,7 +1173,57 @@ class DOCP:
     def kkt_minres_schur_shard_info(self, w):
         """`ctd_kkt_minres_schur_cr_shard_info`"""
         info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_info(self._h, self._shard_ws_ptr(w), w.n_ranks, C.byref(info)))
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_info(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, C.byref(info)))
+        return self._minres_info(info)
+
+    # ---- ... with the joined form (ctd_kkt_minres_schur_cr_joint_*): the same phases on slots that also carry the solve records; P is
+    # the SchurCrJointPrecond of this handle, joined (kkt_schur_cr_joint_factor_join) ---------------------------------------------
+    def kkt_minres_schur_joint_layout(self, n_ranks, rank):
+        """`ctd_kkt_minres_schur_cr_joint_layout`: `kkt_minres_shard_layout` with slots of CTD_KKT_MINRES_SCHUR_JOINT_SLOT doubles."""
+        lay = _lib.ctd_minres_shard_layout(struct_size=C.sizeof(_lib.ctd_minres_shard_layout))
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_layout(self._h, int(n_ranks), int(rank), C.byref(lay)))
+        return lay
+
+    def kkt_minres_schur_joint_workspace(self, n_ranks, rank, ws=None):
+        """`kkt_minres_shard_workspace` for the solve with a SchurCrJointPrecond: the same views, cut with the larger slots."""
+        return self._shard_workspace(self.kkt_minres_schur_joint_layout(n_ranks, rank), n_ranks, ws)
+
+    def kkt_minres_schur_joint_start(self, P, rhs, z, w, rank, rtol=1e-10, max_iter=None):
+        """`ctd_kkt_minres_schur_cr_joint_start_dev_async`: the start with M of P; the partial sums of beta1^2 and the rank's solve
+        record go into w.send_a."""
+        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
+        for nm, a in (("rhs", rhs), ("z", z)):
+            if a is None:
+                raise ValueError(f"{nm} is required")
+        sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=1.0)
+        sys.px, sys.pc = self._dev_ptr(P.px, nvar, "px").value, self._dev_ptr(P.pc, ncon, "pc").value
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_start_dev_async(
+            self._h, C.byref(sys), self._schur_ws_ptr(P), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"),
+            self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+
+    def kkt_minres_schur_joint_begin(self, P, w, rank):
+        """`ctd_kkt_minres_schur_cr_joint_begin_dev_async`: the two join launches, then beta1 and the first Lanczos vector"""
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_begin_dev_async(self._h, self._schur_ws_ptr(P), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank)))
+
+    def kkt_minres_schur_joint_alfa(self, z, w, rank):
+        """`ctd_kkt_minres_schur_cr_joint_alfa_dev_async`: phase (A)"""
+        self._shard_phase(_lib.lib().ctd_kkt_minres_schur_cr_joint_alfa_dev_async, z, w, rank)
+
+    def kkt_minres_schur_joint_lanczos(self, P, z, w, rank):
+        """`ctd_kkt_minres_schur_cr_joint_lanczos_dev_async`: phase (B), the interior's solve, its partial sums and the solve record
+        into w.send_b"""
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_lanczos_dev_async(
+            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank)))
+
+    def kkt_minres_schur_joint_update(self, P, z, w, rank):
+        """`ctd_kkt_minres_schur_cr_joint_update_dev_async`: the two join launches, then phase (C)"""
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_update_dev_async(
+            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank)))
+
+    def kkt_minres_schur_joint_info(self, w):
+        """`ctd_kkt_minres_schur_cr_joint_info`"""
+        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_info(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, C.byref(info)))
         return self._minres_info(info)
 
     def grad_shard(self, x, g, sync=False):

@@ -800,6 +800,104 @@ int32_t ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(ctd_handle* h, double* s
 int32_t ctd_kkt_minres_schur_cr_shard_update_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
 int32_t ctd_kkt_minres_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info);
 
+/* ---- the joined form of the log-depth exact Schur preconditioner: the couplings across the ranks restored ----------------------------
+ * The shard form above is exact inside a rank and drops the G - 1 coupling blocks T(se, se - 1) at the rank boundaries.  This family
+ * applies T^-1 itself on the N blocks, on any ascending split of the steps over G ranks, by separator elimination: every rank but
+ * rank 0 gives up its first block s = sb as a separator; its interior I = [sb + (rank > 0), se) -- at least one block: se - sb >= 2 for
+ * rank >= 1 -- is factored exactly by the block cyclic reduction of the sections above (the same kernels through offset pointers); the
+ * G - 1 separators are joined by a reduced block tridiagonal system of G - 1 blocks of m rows, the Schur complement of T on the
+ * separators, which every rank assembles from the gathered records and factors redundantly (one wave, a sequential block Cholesky
+ * sweep: n_ranks <= CTD_KKT_SCHUR_CR_JOINT_MAX_RANKS).  SPD throughout.  Two collectives by the caller: ONE ALL-GATHER of the factor
+ * records at factor time (CTD_KKT_SCHUR_CR_JOINT_FACTOR_SLOT(m) doubles per rank) and ONE ALL-GATHER of the solve records per
+ * application (CTD_KKT_SCHUR_CR_JOINT_SOLVE_SLOT doubles per rank); gathered buffers hold the n_ranks records in rank order, one slot
+ * apart.  Identical gathered records give identical bits of the reduced factor, x_s and sigma on every rank.
+ *   factor_local   the interface blocks D_s, E[s] = T(s + 1, s), E[b] = T(se, se - 1) by the assemble expression of the sections above;
+ *                  the factor of the interior; the spikes Wl = A^-1 (e_a E[s]) and Wr = A^-1 (e_b E[b]') -- all (up to) 2 m columns
+ *                  through ONE chain of 2 n_levels + 1 launches, the column as the second grid dimension, each column with the bits of
+ *                  a single solve --; the contributions Cll, Crl, Crr and the record (sb, se, m, rank; D_s, Cll, Crl, Crr) into send_dev.
+ *   factor_join    S(r, r) = (D_s^(r) - Crr^(r-1)) - Cll^(r), S(r + 1, r) = -Crl^(r) and its block Cholesky sweep: one launch.  Records
+ *                  that are not an ascending cover of [0, N) make the reduced factor NaN.
+ *   solve_local    g = A^-1 r on the interior rows of out (2 n_levels + 1 launches), then the record (r_s, qu = E[s]' g_a, qd = E[b] g_b).
+ *   solve_join     rs~_r = (r_s^(r) - qd^(r-1)) - qu^(r); x_s = S^-1 rs~ (one wave; it also leaves sigma = x_s . rs~ in the workspace at
+ *                  off_sigma: r' T^-1 r = sum_r r_I . g_r + sigma); then out_s = x_s on the rank's separator and out = (g - Wl x_s,r) -
+ *                  Wr x_s,r+1 on its interior: two launches.  out then holds T^-1 r on the rank's block rows, nothing else is written.
+ * With one rank there is no separator, no record and no join launch (send_dev and gathered_dev may be NULL, the joins do nothing):
+ * the bits of ctd_kkt_schur_cr_shard_* on the same handle.  The recurrences and the order of every sum:
+ * csrc/ctd_schur_cr_joint_kernels.hpp.  Enqueue-only on the handle's stream, plain stores, no atomics, strict rounding.
+ * LAYOUT (works on host-only handles): the separator (-1 on rank 0), the interior, the launch counts, the slots and the offsets (in
+ * doubles) into the workspace of `workspace` doubles.  THE READ SET OF THE FACTOR: that of the shard form on [sb, se) and, of jvals,
+ * the halo [jvals_halo_begin, jvals_halo_end) -- the CSR range of the rows of block se, the next rank's first, right behind the
+ * rank's own range; empty on the last rank -- which the caller fills.  px needs nothing more: E[b] adds over the columns that block
+ * se shares with block se - 1, inside [px_begin, px_end).
+ * Refusals as in the section above, then: n_ranks outside [1, 256], rank outside [0, n_ranks), steps that cannot be block `rank` of
+ * n_ranks ascending blocks, a rank >= 1 of one step -> CTD_EINVAL; null or misaligned pointers, an output that overlaps an input ->
+ * CTD_EINVAL.  The workspace carries a tag of its own and the rank's identity (interior, steps, n_ranks, rank) in its header: a
+ * workspace of the sections above given to this family, or the reverse, or one factored for another split, is recognised on the
+ * device and nothing is stored; the info call returns CTD_EINVAL for it. */
+#define CTD_KKT_SCHUR_CR_JOINT_MAX_RANKS 256
+#define CTD_KKT_SCHUR_CR_JOINT_FACTOR_SLOT(m) (16 + 4 * (int64_t)(m) * (m))
+#define CTD_KKT_SCHUR_CR_JOINT_SOLVE_SLOT (16 + 3 * 64)
+/* struct_size = sizeof(ctd_schur_cr_joint_layout), set by the caller */
+typedef struct ctd_schur_cr_joint_layout {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t N, n_ranks, rank, step_begin, step_end, separator, int_begin, n_int, block_rows;
+    int64_t first_row, tail_rows, first_tail_row, tail_cols;
+    int64_t n_levels, n_sep;
+    int64_t factor_local_launches, factor_join_launches, solve_local_launches, solve_join_launches;
+    int64_t factor_slot, solve_slot;      /* doubles */
+    int64_t off_es, off_eb, off_ds, off_wl, off_wr, off_scratch, off_reduced, off_rs, off_xs, off_sigma;
+    int64_t workspace;                    /* doubles */
+    int64_t jvals_begin, jvals_end, jvals_halo_begin, jvals_halo_end, px_begin, px_end;
+} ctd_schur_cr_joint_layout;
+int32_t ctd_kkt_schur_cr_joint_layout(ctd_handle* h, int32_t n_ranks, int32_t rank, ctd_schur_cr_joint_layout* out);
+/* writes the whole workspace and the factor record (factor_slot doubles) into send_dev; with one rank only the interior's part of the
+ * workspace, [0, off_es), and no record (factor_local_launches counts exactly what is launched).  The pattern upload is
+ * shared with the other factors: the first factor of any kind on a handle is refused while the stream is capturing */
+int32_t ctd_kkt_schur_cr_joint_factor_local_dev_async(ctd_handle* h, const double* jvals_dev, const double* px_dev, const double* sc_dev,
+                                                      double* ws_dev, double* send_dev, int32_t n_ranks, int32_t rank);
+/* gathered_dev: n_ranks records, factor_slot doubles apart; writes the reduced factor in the workspace */
+int32_t ctd_kkt_schur_cr_joint_factor_join_dev_async(ctd_handle* h, double* ws_dev, const double* gathered_dev, int32_t n_ranks,
+                                                     int32_t rank);
+/* r, out: ncon entries; reads r on the rank's block rows, writes out on its interior rows and the solve record (solve_slot doubles)
+ * into send_dev; out must not be r */
+int32_t ctd_kkt_schur_cr_joint_solve_local_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev, double* send_dev,
+                                                     int32_t n_ranks, int32_t rank);
+/* gathered_dev: n_ranks records, solve_slot doubles apart; out: the one solve_local wrote */
+int32_t ctd_kkt_schur_cr_joint_solve_join_dev_async(ctd_handle* h, double* ws_dev, const double* gathered_dev, double* out_dev,
+                                                    int32_t n_ranks, int32_t rank);
+/* waits for the handle's stream; *first_bad_block = -1, or the smallest GLOBAL block index with a recorded pivot among the rank's
+ * interior and the separators (a reduced factor made NaN by records that do not cover the grid reports block 0) */
+int32_t ctd_kkt_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, int32_t rank, int64_t* first_bad_block);
+/* The shard form of the MINRES solve (ctd_kkt_minres_schur_cr_shard_* above: the same phases, the same THREE all-gathers by the caller,
+ * the same checks) with M of this section, T^-1 on the block rows.  No fourth gather: both send slots grow to
+ * CTD_KKT_MINRES_SCHUR_JOINT_SLOT doubles -- the slot of the shard form, whose solve partial sums are now those of r_I . g_r over the
+ * rank's interior, then the rank's solve record (CTD_KKT_SCHUR_CR_JOINT_SOLVE_SLOT doubles).  start and lanczos enqueue, behind their own
+ * launch, the interior's solve, its partial sums and the record kernel (solve_local_launches + 1 launches); begin and update START
+ * with the two join launches (the reduced solve from the gathered records, the correction of y on the rank's own block rows), then
+ * their kernel adds sigma = x_s . rs~ -- read from the factor's workspace -- after all gathered partial sums:
+ *     beta^2 = [the terms of the diagonal form, ranks ascending] + [the partial sums of r_I . g_r, ranks ascending] + sigma,
+ * one running sum from 0.0 (r' T^-1 r split by the block elimination: both parts are non-negative).  v = y / beta in (C) sees the
+ * corrected y.  Identical gathered slots give identical sigma, states and decisions on every rank; a failed pivot anywhere reaches
+ * every rank's beta^2 as NaN through the records: all ranks end with "breakdown" after the same chunk.  In lanczos and update every
+ * added launch reads the status (B) read and stores nothing unless it is running.  With one rank no join launch is enqueued and
+ * sigma is not read: the bits of ctd_kkt_minres_schur_cr_shard_* on the same handle, hence of ctd_kkt_minres_schur_cr_dev.  begin
+ * and update take the factor's workspace (the handle keeps no state of the solve).  Capturable after one warm call. */
+#define CTD_KKT_MINRES_SCHUR_JOINT_SLOT (CTD_KKT_MINRES_SCHUR_SHARD_SLOT + 3 * 64 + 16)
+#define CTD_KKT_MINRES_SCHUR_JOINT_WORKSPACE(n, n_ranks) \
+    (8 * (int64_t)(n) + (2 + 2 * (int64_t)(n_ranks)) * CTD_KKT_MINRES_SCHUR_JOINT_SLOT + 96)
+int32_t ctd_kkt_minres_schur_cr_joint_layout(ctd_handle* h, int32_t n_ranks, int32_t rank, ctd_minres_shard_layout* out);
+int32_t ctd_kkt_minres_schur_cr_joint_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev,
+                                                      const double* rhs_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
+                                                      int32_t rank, double rtol, int64_t max_iter);
+int32_t ctd_kkt_minres_schur_cr_joint_begin_dev_async(ctd_handle* h, double* schur_ws_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_joint_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_joint_lanczos_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev,
+                                                        int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_joint_update_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev,
+                                                       int32_t n_ranks, int32_t rank);
+int32_t ctd_kkt_minres_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info);
+
 /* ---- matrix-free products on a shard of the grid ------------------------------------------------------------------------
  * The products above for a handle restricted to the steps [sb, se) = [step_begin, step_end) of its ctd_desc (handles of
  * ctd_sharded_handle included), modelled on ctd_grad_shard_dev_async: enqueue-only on the handle's stream, capturable after one

@@ -208,7 +208,11 @@ KRYLOV_KERNELS = ("krylov_init_kernel", "krylov_first_kernel", "krylov_alfa_kern
 SCHUR_KERNELS = ("schur_assemble_kernel", "schur_factor_kernel", "schur_solve_kernel")
 # the log-depth exact form (csrc/ctd_schur_cr.hip)
 SCHUR_CR_KERNELS = ("schur_cr_assemble_kernel", "schur_cr_eliminate_kernel", "schur_cr_update_kernel", "schur_cr_down_kernel",
-                    "schur_cr_root_kernel", "schur_cr_up_kernel", "schur_cr_dot_kernel")
+                    "schur_cr_root_kernel", "schur_cr_up_kernel", "schur_cr_dot_kernel",
+                    # the joined form (csrc/ctd_schur_cr_joint_kernels.hpp; its translation unit is csrc/ctd_schur_cr_joint.hip)
+                    "schur_cr_joint_interface_kernel", "schur_cr_joint_down_kernel", "schur_cr_joint_root_kernel", "schur_cr_joint_up_kernel",
+                    "schur_cr_joint_contrib_kernel", "schur_cr_joint_reduce_kernel", "schur_cr_joint_record_kernel",
+                    "schur_cr_joint_reduced_solve_kernel", "schur_cr_joint_correct_kernel")
 
 
 def mangled(stem):
@@ -226,14 +230,18 @@ def krylov_table():
     for k, n in zip(ks, names):         # the SCHUR = true instantiation of a kernel (its only template argument); of a shard kernel:
         if re.search(r"ILb1EE", n) or "KrylovSchurShardParams" in n:      # the one for the Schur form's argument struct
             k["kernel"] += "<SCHUR>"
-    assert sorted({k["kernel"].replace("<SCHUR>", "") for k in ks}) == sorted(KRYLOV_KERNELS), ks
-    for stem, kernels in (("ctd_schur", SCHUR_KERNELS), ("ctd_schur_cr", SCHUR_CR_KERNELS)):
+        if "KrylovSchurJointParams" in n:       # ... for the joined form's
+            k["kernel"] += "<JOINT>"
+    assert sorted({k["kernel"].replace("<SCHUR>", "").replace("<JOINT>", "") for k in ks}) == sorted(KRYLOV_KERNELS), ks
+    for stem, kernels in (("ctd_schur", SCHUR_KERNELS), ("ctd_schur_cr", SCHUR_CR_KERNELS), ("ctd_schur_cr_joint", SCHUR_CR_KERNELS)):
         sch = remarks(stem, "", kernels)
         for k, n in zip(sch, [n for n in mangled(stem) if re.search("|".join(kernels), n)]):
             mb = re.search(r"ILi(\d+)E", n)
             k["kernel"] += f"<{mb.group(1)}>" if mb else ""
             if "SchurCrShard" in n:      # the instantiation for a shard's argument struct (csrc/ctd_schur_cr_kernels.hpp)
                 k["kernel"] += " shard"
+            if "SchurCrJoint" in n and "schur_cr_joint_" not in n:      # ... for the joined form's (csrc/ctd_schur_cr_joint_kernels.hpp)
+                k["kernel"] += " joint"
         ks += sch
     path = os.path.join(ROOT, "profiles", "kkt_minres_resources.md")
     lines = ["# Resources of the MINRES vector kernels (csrc/ctd_krylov.hip)\n\n",
@@ -242,7 +250,7 @@ def krylov_table():
              "code differs with it (of the shard form: the four instantiated for the Schur form's argument struct, csrc/\n"
              "ctd_krylov_shard_kernels.hpp); below them the kernels of that preconditioner (csrc/ctd_schur.hip), the factor and the solve per\n"
              "largest block size, and those of its log-depth exact form (csrc/ctd_schur_cr.hip; `shard`: the instantiation for a\n"
-             "shard's argument struct).  The script fails if any of them uses\n"
+             "shard's argument struct; `joint`: for the joined form's, followed by that form's own kernels).  The script fails if any of them uses\n"
              "scratch.\n\n",
              "| kernel | VGPR + AGPR | scratch B/lane | waves/SIMD |\n", "|---|---|---|---|\n"]
     # a kernel keeps the row it has in the file; new ones follow in the compiler's order (instantiating a kernel a second time
