@@ -170,6 +170,30 @@ static int32_t fail(ctd_handle* h, int32_t code, const std::string& msg) {
             return fail(h, CTD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
+// The end of every enqueue: a launch that failed is CTD_EHIP, named by the entry point that was called (fn null: no name)
+static int32_t launched(ctd_handle* h, const char* fn, hipError_t e) {
+    if (e == hipSuccess) return CTD_OK;
+    return fail(h, CTD_EHIP, (fn ? std::string(fn) + ": " : std::string()) + "kernel launch: " + hipGetErrorString(e));
+}
+
+// A struct of the caller's (`arg`: sys, info, layout): null, or laid out by another version of the header -- its struct_size is
+// not sizeof(T) -- is CTD_EINVAL, set as the handle's error; false then
+template <class T> static bool struct_ok(ctd_handle* h, const char* fn, const char* arg, const char* type, const T* p) {
+    if (p && p->struct_size == sizeof(T)) return true;
+    fail(h, CTD_EINVAL, std::string(fn) + ": " + arg + " is null or its struct_size is not sizeof(" + type + ") = " + std::to_string(sizeof(T)));
+    return false;
+}
+#define STRUCT_OK(h, fn, arg, T, p) struct_ok<T>(h, fn, arg, #T, p)
+
+// A device pointer the caller must give: null or not aligned to a double is CTD_EINVAL, by name
+static int32_t check_ptr(ctd_handle* h, const char* fn, const char* name, const void* p) {
+    if (!p) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (" + name + " is required)");
+    if ((uintptr_t)p % sizeof(double)) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " is not aligned to 8 bytes");
+    return CTD_OK;
+}
+// [a, a + na) and [b, b + nb) share an entry (null: no range)
+static bool ranges_overlap(const double* a, int64_t na, const double* b, int64_t nb) { return a && b && a < b + nb && b < a + na; }
+
 // Every entry point that touches the device runs on the handle's device and leaves the caller's current device as it found
 // it (a process driving several GPUs keeps its own notion of "current"); hipGetDevice is a thread-local read, and the
 // hipSetDevice pair is only paid when the two differ.
@@ -462,9 +486,7 @@ struct MfCall {
     MfForm form;
     const char* fn() const { return op.name[form]; }
     bool shard() const { return form == MF_SHARD; }
-    int32_t launched(ctd_handle* h, hipError_t e) const {
-        return e == hipSuccess ? CTD_OK : fail(h, CTD_EHIP, std::string(fn()) + ": kernel launch: " + hipGetErrorString(e));
-    }
+    int32_t launched(ctd_handle* h, hipError_t e) const { return ::launched(h, fn(), e); }
 };
 
 // The directions a lane of a unit pass takes together: D<P>::JC of a registry problem, the same rule for a run-time OCP
@@ -1031,8 +1053,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
             using P = typename decltype(tag)::type;
             e = launch_cons_jac_batch<P>(kp, x_dev, bl, h->plan.grid, h->plan.block, h->plan.lds_bytes, h->stream, bt->n);
         });
-        if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-        return CTD_OK;
+        return launched(h, nullptr, e);
     }
     if (h->rt) {
         void* args[] = {&kp, &x_dev};
@@ -1042,8 +1063,7 @@ static int32_t enqueue_cons_jac(ctd_handle* h, const double* x_dev, double* c_de
         using P = typename decltype(tag)::type;
         e = launch_cons_jac<P>(kp, x_dev, h->plan.grid, h->plan.block, h->plan.lds_bytes, h->stream, te0, te1, h->plan.lean_ok);
     });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, nullptr, e);
 }
 
 int32_t ctd_cons_jac_dev_async(ctd_handle* h, const double* x_dev, double* c_dev, double* vals_dev) {
@@ -1137,8 +1157,7 @@ static int32_t enqueue_obj(ctd_handle* h, const double* x_dev, double* f_dev, co
         using P = typename decltype(tag)::type;
         e = launch_obj<P>(op, x_dev, lagrange ? blocks : 0, 256, h->stream, nb);
     });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, nullptr, e);
 }
 
 static int fill_obj_params(ctd_handle* h, double* f_dev, ObjParams& op) {
@@ -1254,8 +1273,7 @@ static int32_t enqueue_grad(ctd_handle* h, const double* x_dev, double* g_dev, G
         using P = typename decltype(tag)::type;
         e = launch_grad<P>(gp, x_dev, lagrange ? blocks : 0, h->stream, nb);
     });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, nullptr, e);
 }
 
 int32_t ctd_grad(ctd_handle* h, const double* x, double* g) {
@@ -1514,14 +1532,7 @@ static constexpr MfOp kMrStart = CTD_MR_OP("ctd_kkt_minres_start_dev_async", "sy
 // (*st = the status to return when the result is false)
 static bool mr_structs_ok(ctd_handle* h, const char* fn, const ctd_kkt_system* sys, bool with_info, const ctd_minres_info* info, int32_t* st) {
     *st = CTD_EINVAL;
-    if (!h) return false;
-    if (!sys || sys->struct_size != sizeof(ctd_kkt_system))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": sys is null or its struct_size is not sizeof(ctd_kkt_system) = " +
-                                       std::to_string(sizeof(ctd_kkt_system))), false;
-    if (with_info && (!info || info->struct_size != sizeof(ctd_minres_info)))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
-                                       std::to_string(sizeof(ctd_minres_info))), false;
-    return true;
+    return h && STRUCT_OK(h, fn, "sys", ctd_kkt_system, sys) && (!with_info || STRUCT_OK(h, fn, "info", ctd_minres_info, info));
 }
 // ... after it (OnDevice): whole-grid handle, the pointers (mf_check), the preconditioner pair
 static int32_t mr_check(const OnDevice& on, ctd_handle* h, const MfCall& c, const ctd_kkt_system* sys, const double* rhs, const double* z,
@@ -1538,11 +1549,12 @@ static int32_t mr_check(const OnDevice& on, ctd_handle* h, const MfCall& c, cons
         return fail(h, CTD_EINVAL, std::string(c.fn()) + ": px and pc are given both (M = diag(1 / px, 1 / pc)) or neither (no preconditioner)");
     return CTD_OK;
 }
-static int32_t mr_check_count(ctd_handle* h, const MfCall& c, const char* name, int64_t v) {
-    return v >= 1 ? CTD_OK : fail(h, CTD_EINVAL, std::string(c.fn()) + ": " + name + " = " + std::to_string(v) + ", must be at least 1");
+// (these two: the whole-grid solves and the start of every phase family on a shard)
+static int32_t mr_check_count(ctd_handle* h, const char* fn, const char* name, int64_t v) {
+    return v >= 1 ? CTD_OK : fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " = " + std::to_string(v) + ", must be at least 1");
 }
-static int32_t mr_check_rtol(ctd_handle* h, const MfCall& c, double rtol) {
-    return rtol >= 0.0 ? CTD_OK : fail(h, CTD_EINVAL, std::string(c.fn()) + ": rtol must not be negative (or NaN)");
+static int32_t mr_check_rtol(ctd_handle* h, const char* fn, double rtol) {
+    return rtol >= 0.0 ? CTD_OK : fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
 }
 
 static KrylovParams mr_params(const ctd_handle* h) {
@@ -1608,10 +1620,11 @@ static int32_t mr_enqueue_iters(ctd_handle* h, const MfCall& c, const ctd_kkt_sy
     return CTD_OK;
 }
 
-static int32_t mr_read_info(ctd_handle* h, ctd_minres_info* info) {
+// the state of a solve (state_dev: a KrylovState on the device) as the caller's info; waits for the handle's stream
+static int32_t mr_read_info(ctd_handle* h, const void* state_dev, ctd_minres_info* info) {
     KrylovState s;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(&s, mr_params(h).pend, sizeof(s), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(&s, state_dev, sizeof(s), hipMemcpyDeviceToHost));
     info->status = s.status;
     info->iterations = s.itn;
     info->phibar = s.phibar;
@@ -1627,10 +1640,10 @@ static int32_t mr_drive(ctd_handle* h, const MfCall& c, const ctd_kkt_system& sy
     if (const int32_t st = mr_enqueue_start(h, c, sys, rhs_dev, z_dev, rtol, max_iter, schur_ws, schur_cr)) return st;
     for (int64_t done = 0; done < max_iter; done += check_every) {
         if (const int32_t st = mr_enqueue_iters(h, c, sys, check_every)) return st;
-        if (const int32_t st = mr_read_info(h, info)) return st;
+        if (const int32_t st = mr_read_info(h, mr_params(h).pend, info)) return st;
         if (info->status != CTD_MINRES_RUNNING) return CTD_OK;
     }
-    return mr_read_info(h, info);
+    return mr_read_info(h, mr_params(h).pend, info);
 }
 
 int32_t ctd_kkt_minres_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev, double rtol) {
@@ -1639,7 +1652,7 @@ int32_t ctd_kkt_minres_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys,
     if (!mr_structs_ok(h, c.fn(), sys, false, nullptr, &st)) return st;
     const OnDevice on(h, c.fn());
     if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
-    if ((st = mr_check_rtol(h, c, rtol))) return st;
+    if ((st = mr_check_rtol(h, c.fn(), rtol))) return st;
     return mr_enqueue_start(h, c, *sys, rhs_dev, z_dev, rtol, INT64_MAX);
 }
 
@@ -1649,7 +1662,7 @@ int32_t ctd_kkt_minres_iters_dev_async(ctd_handle* h, const ctd_kkt_system* sys,
     if (!mr_structs_ok(h, c.fn(), sys, false, nullptr, &st)) return st;
     const OnDevice on(h, c.fn());
     if ((st = mr_check(on, h, c, sys, nullptr, z_dev, false))) return st;
-    if ((st = mr_check_count(h, c, "k", k))) return st;
+    if ((st = mr_check_count(h, c.fn(), "k", k))) return st;
     if (!h->mr_z) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": no solve has been started on this handle (ctd_kkt_minres_start_dev_async)");
     if (z_dev != h->mr_z) return fail(h, CTD_EINVAL, std::string(c.fn()) + ": z is not the iterate of the solve started last");
     return mr_enqueue_iters(h, c, *sys, k);
@@ -1657,14 +1670,11 @@ int32_t ctd_kkt_minres_iters_dev_async(ctd_handle* h, const ctd_kkt_system* sys,
 
 int32_t ctd_kkt_minres_info(ctd_handle* h, ctd_minres_info* info) {
     const char* fn = "ctd_kkt_minres_info";
-    if (!h) return CTD_EINVAL;
-    if (!info || info->struct_size != sizeof(ctd_minres_info))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
-                                       std::to_string(sizeof(ctd_minres_info)));
+    if (!h || !STRUCT_OK(h, fn, "info", ctd_minres_info, info)) return CTD_EINVAL;
     const OnDevice on(h, fn);
     if (on.st) return on.st;
     if (!h->mr_z) return fail(h, CTD_EINVAL, std::string(fn) + ": no solve has been started on this handle (ctd_kkt_minres_start_dev_async)");
-    return mr_read_info(h, info);
+    return mr_read_info(h, mr_params(h).pend, info);
 }
 
 int32_t ctd_kkt_minres_dev(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev, double rtol, int64_t max_iter,
@@ -1674,8 +1684,8 @@ int32_t ctd_kkt_minres_dev(ctd_handle* h, const ctd_kkt_system* sys, const doubl
     if (!mr_structs_ok(h, c.fn(), sys, true, info, &st)) return st;
     const OnDevice on(h, c.fn());
     if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
-    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
-        (st = mr_check_count(h, c, "check_every", check_every)))
+    if ((st = mr_check_rtol(h, c.fn(), rtol)) || (st = mr_check_count(h, c.fn(), "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c.fn(), "check_every", check_every)))
         return st;
     return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info);
 }
@@ -1687,8 +1697,8 @@ int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* r
     if (!mr_structs_ok(h, c.fn(), sys, true, info, &st)) return st;
     const OnDevice on(h, c.fn());
     if ((st = mr_check(on, h, c, sys, rhs, z, true))) return st;
-    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
-        (st = mr_check_count(h, c, "check_every", check_every)))
+    if ((st = mr_check_rtol(h, c.fn(), rtol)) || (st = mr_check_count(h, c.fn(), "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c.fn(), "check_every", check_every)))
         return st;
     // x, y, sx, sc where ctd_kktprod stages them; (px, pc), rhs and z in buffers of the solve's own
     const Layout& L = h->model.L;
@@ -1717,6 +1727,52 @@ int32_t ctd_kkt_minres(ctd_handle* h, const ctd_kkt_system* sys, const double* r
 static_assert(kSchurFixed == CTD_KKT_SCHUR_FIXED, "the fixed part of the workspace of the header");
 static constexpr int32_t kPlanStatus[] = {CTD_OK, CTD_EINVAL, CTD_EGRID, CTD_ESCHEME, CTD_EPATTERN, CTD_EPROBLEM};
 
+// What the four Schur families share around their own plans, kernels and workspaces.  The end of a family's plan: its status `st`
+// (ctd_schur_plan.hpp) as the C status with its text behind the entry point's name; a plan that passed has walked the pattern
+static int32_t schur_planned(ctd_handle* h, const char* fn, int st, const std::string& err) {
+    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
+    h->schur_verified = true;
+    return CTD_OK;
+}
+// the arguments of a factor (sc may be null: zero) ...
+static int32_t schur_check_factor_args(ctd_handle* h, const char* fn, const double* jvals, const double* px, const double* sc, const double* ws) {
+    if (!jvals || !px || !ws) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
+    if (ws == jvals || ws == px || ws == sc) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    return CTD_OK;
+}
+// ... and of a solve; ws_written: the solve uses a scratch region of the workspace (the log-depth forms), so r must not be it either
+static int32_t schur_check_solve_args(ctd_handle* h, const char* fn, const double* ws, const double* r, const double* out, bool ws_written) {
+    if (!ws || !r || !out) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
+    if (out == r || out == ws || (ws_written && r == ws))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) " + (ws_written ? "and the workspace " : "") + "must not be an input buffer");
+    return CTD_OK;
+}
+// The status words of a factor, for the families' info calls (ws, first_bad_block: their arguments): waits for the handle's
+// stream, reads the header of the workspace and compares its first words with `expect` (the tag and the fields the factor wrote
+// for this handle); then `status` gets the n words behind the fixed part -- one per block, -1: every pivot was positive --, or as
+// many as header word count_word says (>= 0: the chunked form's count of chunks, at most n).  It stays empty when the header is
+// another's: the caller words the refusal.  schur_first_set: the first word that is set (-1: none)
+static int32_t schur_read_status(ctd_handle* h, const char* fn, const double* ws_dev, const int64_t* first_bad_block,
+                                 std::initializer_list<int64_t> expect, int count_word, int64_t n, std::vector<int64_t>& status) {
+    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
+    int64_t head[9];
+    static_assert(sizeof(head) <= sizeof(double) * kSchurFixed, "the header lies in the fixed part of every family's workspace");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
+    status.clear();
+    if (!std::equal(expect.begin(), expect.end(), head)) return CTD_OK;
+    if (count_word >= 0) n = head[count_word] <= n ? head[count_word] : 0;
+    if (n < 1) return CTD_OK;
+    status.resize((size_t)n);
+    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
+    return CTD_OK;
+}
+static int64_t schur_first_set(const std::vector<int64_t>& status) {
+    for (size_t k = 0; k < status.size(); ++k)
+        if (status[k] >= 0) return (int64_t)k;
+    return -1;
+}
+
 // The checks every entry point of the family shares once the handle (and its device) are known: whole grid, then the plan's own
 // (CSR order, block_rows, chunk_steps, the pattern -- walked once per handle)
 static int32_t schur_plan(ctd_handle* h, const char* fn, int64_t chunk_steps, SchurPlan& pl) {
@@ -1724,18 +1780,12 @@ static int32_t schur_plan(ctd_handle* h, const char* fn, int64_t chunk_steps, Sc
         return fail(h, CTD_EINVAL, std::string(fn) + ": this call needs a handle of the whole grid; a shard of the grid (step_begin / "
                                    "step_end, ctd_set_x_shards) is refused: the Schur preconditioner has no shard form yet");
     std::string err;
-    const int st = plan_kkt_schur(h->model, chunk_steps, !h->schur_verified, pl, err);
-    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
-    h->schur_verified = true;
-    return CTD_OK;
+    return schur_planned(h, fn, plan_kkt_schur(h->model, chunk_steps, !h->schur_verified, pl, err), err);
 }
 
 int32_t ctd_kkt_schur_layout(ctd_handle* h, int64_t chunk_steps, ctd_schur_layout* out) {
     const char* fn = "ctd_kkt_schur_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_schur_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_layout) = " +
-                                       std::to_string(sizeof(ctd_schur_layout)));
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_schur_layout, out)) return CTD_EINVAL;
     SchurPlan pl;
     if (const int32_t st = schur_plan(h, fn, chunk_steps, pl)) return st;
     out->reserved = 0;
@@ -1780,15 +1830,11 @@ int32_t ctd_kkt_schur_factor_dev_async(ctd_handle* h, const double* jvals_dev, c
     if (on.st) return on.st;
     SchurPlan pl;
     if (const int32_t st = schur_plan(h, fn, chunk_steps, pl)) return st;
-    if (!jvals_dev || !px_dev || !ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
-    if (ws_dev == jvals_dev || ws_dev == px_dev || ws_dev == sc_dev)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    if (const int32_t st = schur_check_factor_args(h, fn, jvals_dev, px_dev, sc_dev, ws_dev)) return st;
     if (const int32_t st = schur_upload_pattern(h, fn)) return st;
     const SchurFactorParams fp{pl.N, pl.first_tail_col, pl.chunk_steps, pl.n_chunks, (int32_t)pl.block_rows, 0,
                                h->d_schur_rowptr.p, h->d_schur_colind.p, jvals_dev, px_dev, sc_dev, ws_dev};
-    const hipError_t e = schur_factor(fp, h->stream);
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, fn, schur_factor(fp, h->stream));
 }
 
 int32_t ctd_kkt_schur_solve_dev_async(ctd_handle* h, const double* ws_dev, const double* r_dev, double* out_dev) {
@@ -1797,12 +1843,9 @@ int32_t ctd_kkt_schur_solve_dev_async(ctd_handle* h, const double* ws_dev, const
     if (on.st) return on.st;
     SchurPlan pl;
     if (const int32_t st = schur_plan(h, fn, 1, pl)) return st;
-    if (!ws_dev || !r_dev || !out_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
-    if (out_dev == r_dev || out_dev == ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not be an input buffer");
+    if (const int32_t st = schur_check_solve_args(h, fn, ws_dev, r_dev, out_dev, false)) return st;
     const SchurSolveParams sp{pl.N, (int32_t)pl.block_rows, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr};
-    const hipError_t e = schur_solve(sp, h->stream);
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, fn, schur_solve(sp, h->stream));
 }
 
 int32_t ctd_kkt_schur_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block) {
@@ -1811,14 +1854,10 @@ int32_t ctd_kkt_schur_info(ctd_handle* h, const double* ws_dev, int64_t* first_b
     if (on.st) return on.st;
     SchurPlan pl;
     if (const int32_t st = schur_plan(h, fn, 1, pl)) return st;
-    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    int64_t head[5];
-    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
-    if (head[0] != kSchurTag || head[1] != pl.N || head[2] != pl.block_rows || head[4] < 1 || head[4] > pl.N)
+    std::vector<int64_t> status;       // one word per chunk (the factor's count: header word 4), each the chunk's first bad block
+    if (const int32_t st = schur_read_status(h, fn, ws_dev, first_bad_block, {kSchurTag, pl.N, pl.block_rows}, 4, pl.N, status)) return st;
+    if (status.empty())
         return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle (ctd_kkt_schur_factor_dev_async)");
-    std::vector<int64_t> status((size_t)head[4]);
-    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
     *first_bad_block = -1;
     for (int64_t b : status)
         if (b >= 0 && (*first_bad_block < 0 || b < *first_bad_block)) *first_bad_block = b;
@@ -1849,7 +1888,7 @@ int32_t ctd_kkt_minres_schur_start_dev_async(ctd_handle* h, const ctd_kkt_system
     if ((st = schur_plan(h, c.fn(), 1, pl))) return st;             // (whole grid, CSR order, the block size)
     if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
     if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
-    if ((st = mr_check_rtol(h, c, rtol))) return st;
+    if ((st = mr_check_rtol(h, c.fn(), rtol))) return st;
     return mr_enqueue_start(h, c, *sys, rhs_dev, z_dev, rtol, INT64_MAX, schur_ws_dev);
 }
 
@@ -1864,8 +1903,8 @@ int32_t ctd_kkt_minres_schur_dev(ctd_handle* h, const ctd_kkt_system* sys, doubl
     if ((st = schur_plan(h, c.fn(), 1, pl))) return st;             // (whole grid, CSR order, the block size)
     if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
     if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
-    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
-        (st = mr_check_count(h, c, "check_every", check_every)))
+    if ((st = mr_check_rtol(h, c.fn(), rtol)) || (st = mr_check_count(h, c.fn(), "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c.fn(), "check_every", check_every)))
         return st;
     return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info, schur_ws_dev);
 }
@@ -1878,18 +1917,12 @@ static int32_t schur_cr_plan(ctd_handle* h, const char* fn, SchurCrPlan& pl) {
                                    "step_end, ctd_set_x_shards) is refused: this entry point has no shard form (the shard form of the "
                                    "log-depth preconditioner is ctd_kkt_schur_cr_shard_*)");
     std::string err;
-    const int st = plan_kkt_schur_cr(h->model, !h->schur_verified, pl, err);
-    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
-    h->schur_verified = true;
-    return CTD_OK;
+    return schur_planned(h, fn, plan_kkt_schur_cr(h->model, !h->schur_verified, pl, err), err);
 }
 
 int32_t ctd_kkt_schur_cr_layout(ctd_handle* h, ctd_schur_cr_layout* out) {
     const char* fn = "ctd_kkt_schur_cr_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_schur_cr_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_cr_layout) = " +
-                                       std::to_string(sizeof(ctd_schur_cr_layout)));
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_schur_cr_layout, out)) return CTD_EINVAL;
     SchurCrPlan pl;
     if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
     static_assert(CTD_KKT_SCHUR_CR_WORKSPACE(7, 9) == kSchurFixed + 7 + 3 * 7 * 81 + 2 * 7 * 9, "the workspace of the header");
@@ -1912,15 +1945,11 @@ int32_t ctd_kkt_schur_cr_factor_dev_async(ctd_handle* h, const double* jvals_dev
     if (on.st) return on.st;
     SchurCrPlan pl;
     if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
-    if (!jvals_dev || !px_dev || !ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
-    if (ws_dev == jvals_dev || ws_dev == px_dev || ws_dev == sc_dev)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    if (const int32_t st = schur_check_factor_args(h, fn, jvals_dev, px_dev, sc_dev, ws_dev)) return st;
     if (const int32_t st = schur_upload_pattern(h, fn)) return st;
     const SchurCrFactorParams fp{pl.N, pl.first_tail_col, (int32_t)pl.block_rows, (int32_t)pl.n_levels,
                                  h->d_schur_rowptr.p, h->d_schur_colind.p, jvals_dev, px_dev, sc_dev, ws_dev};
-    const hipError_t e = schur_cr_factor(fp, h->stream);
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, fn, schur_cr_factor(fp, h->stream));
 }
 
 int32_t ctd_kkt_schur_cr_solve_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev) {
@@ -1929,13 +1958,9 @@ int32_t ctd_kkt_schur_cr_solve_dev_async(ctd_handle* h, double* ws_dev, const do
     if (on.st) return on.st;
     SchurCrPlan pl;
     if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
-    if (!ws_dev || !r_dev || !out_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
-    if (out_dev == r_dev || out_dev == ws_dev || r_dev == ws_dev)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) and the workspace must not be an input buffer");
+    if (const int32_t st = schur_check_solve_args(h, fn, ws_dev, r_dev, out_dev, true)) return st;
     const SchurCrSolveParams sp{pl.N, (int32_t)pl.block_rows, SCHUR_PLAIN, (int32_t)pl.n_levels, 0, ws_dev, r_dev, out_dev, nullptr};
-    const hipError_t e = schur_cr_solve(sp, h->stream);
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, fn, schur_cr_solve(sp, h->stream));
 }
 
 int32_t ctd_kkt_schur_cr_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block) {
@@ -1944,20 +1969,13 @@ int32_t ctd_kkt_schur_cr_info(ctd_handle* h, const double* ws_dev, int64_t* firs
     if (on.st) return on.st;
     SchurCrPlan pl;
     if (const int32_t st = schur_cr_plan(h, fn, pl)) return st;
-    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    int64_t head[4];
-    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
-    if (head[0] != kSchurCrTag || head[1] != pl.N || head[2] != pl.block_rows || head[3] != pl.n_levels)
+    std::vector<int64_t> status;       // one word per block
+    if (const int32_t st = schur_read_status(h, fn, ws_dev, first_bad_block, {kSchurCrTag, pl.N, pl.block_rows, pl.n_levels},
+                                             -1, pl.N, status))
+        return st;
+    if (status.empty())
         return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle (ctd_kkt_schur_cr_factor_dev_async)");
-    std::vector<int64_t> status((size_t)pl.N);
-    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
-    *first_bad_block = -1;
-    for (int64_t k = 0; k < pl.N; ++k)
-        if (status[(size_t)k] >= 0) {
-            *first_bad_block = k;
-            break;
-        }
+    *first_bad_block = schur_first_set(status);
     return CTD_OK;
 }
 
@@ -1977,7 +1995,7 @@ int32_t ctd_kkt_minres_schur_cr_start_dev_async(ctd_handle* h, const ctd_kkt_sys
     if ((st = schur_cr_plan(h, c.fn(), pl))) return st;             // (whole grid, CSR order, the block size)
     if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
     if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
-    if ((st = mr_check_rtol(h, c, rtol))) return st;
+    if ((st = mr_check_rtol(h, c.fn(), rtol))) return st;
     return mr_enqueue_start(h, c, *sys, rhs_dev, z_dev, rtol, INT64_MAX, schur_ws_dev, true);
 }
 
@@ -1992,8 +2010,8 @@ int32_t ctd_kkt_minres_schur_cr_dev(ctd_handle* h, const ctd_kkt_system* sys, do
     if ((st = schur_cr_plan(h, c.fn(), pl))) return st;             // (whole grid, CSR order, the block size)
     if ((st = mr_check(on, h, c, sys, rhs_dev, z_dev, true))) return st;
     if ((st = mr_schur_check(h, c, sys, schur_ws_dev, rhs_dev, z_dev))) return st;
-    if ((st = mr_check_rtol(h, c, rtol)) || (st = mr_check_count(h, c, "max_iter", max_iter)) ||
-        (st = mr_check_count(h, c, "check_every", check_every)))
+    if ((st = mr_check_rtol(h, c.fn(), rtol)) || (st = mr_check_count(h, c.fn(), "max_iter", max_iter)) ||
+        (st = mr_check_count(h, c.fn(), "check_every", check_every)))
         return st;
     return mr_drive(h, c, *sys, rhs_dev, z_dev, rtol, max_iter, check_every, info, schur_ws_dev, true);
 }
@@ -2010,7 +2028,7 @@ static void mrs_geom(int64_t n, int32_t* nwg, int64_t* chunk) {
 static KrylovShardPlan mrs_plan(const ctd_handle* h) { return plan_krylov_shard(h->model.L, h->step_begin, h->step_end, mrs_geom); }
 
 // n_ranks, rank and the handle's steps: the steps must be able to be block `rank` of n_ranks ascending blocks of the grid
-static int32_t mrs_check_rank(ctd_handle* h, const char* fn, int32_t n_ranks, int32_t rank, bool with_rank) {
+static int32_t check_ranks(ctd_handle* h, const char* fn, int32_t n_ranks, int32_t rank, bool with_rank) {
     const int64_t N = h->model.L.N, sb = h->step_begin, se = h->step_end;
     if (n_ranks < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": n_ranks = " + std::to_string(n_ranks) + ", must be at least 1");
     if (n_ranks > N)
@@ -2024,51 +2042,93 @@ static int32_t mrs_check_rank(ctd_handle* h, const char* fn, int32_t n_ranks, in
                                        std::to_string(n_ranks) + " ascending blocks of the grid");
     return CTD_OK;
 }
-static int32_t mrs_check_ptr(ctd_handle* h, const char* fn, const char* name, const void* p) {
-    if (!p) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (" + name + " is required)");
-    if ((uintptr_t)p % sizeof(double)) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " is not aligned to 8 bytes");
+
+// What the phase families share (this one, ctd_kkt_minres_schur_cr_shard_* and ctd_kkt_minres_schur_cr_joint_* below); a family is
+// data here: the length of its slots and, where it carries a factor, the length of the factor's workspace.
+// The buffers of one call: the solve's workspace, cut with slots of `slot` doubles; z (n entries) and the factor's workspace where
+// the call takes them (with_z, with_schur; null otherwise), so that a null pointer is refused by name
+struct PhaseBufs {
+    int64_t slot;
+    const double* ws;
+    bool with_z;
+    const double* z;
+    bool with_schur;
+    const double* schur_ws;
+};
+// ... checked, for every phase and for start: the pointers by name (null, alignment), z against the workspace
+// (CTD_KKT_MINRES_SHARD_WORKSPACE doubles for the family's slot), the factor's workspace (schur_len doubles) against both
+static int32_t check_phase_buffers(ctd_handle* h, const char* fn, const PhaseBufs& b, int32_t n_ranks, int64_t schur_len) {
+    int32_t st;
+    if (b.with_z && (st = check_ptr(h, fn, "z", b.z))) return st;
+    if ((st = check_ptr(h, fn, "ws", b.ws))) return st;
+    if (b.with_schur && (st = check_ptr(h, fn, "schur_ws", b.schur_ws))) return st;
+    const int64_t n = h->model.L.nvar + h->model.L.ncon, wlen = krylov_shard_workspace(n, n_ranks, b.slot);
+    if (ranges_overlap(b.z, n, b.ws, wlen)) return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
+    if (ranges_overlap(b.schur_ws, schur_len, b.ws, wlen) || ranges_overlap(b.schur_ws, schur_len, b.z, n))
+        return fail(h, CTD_EINVAL, std::string(fn) + ": schur_ws must not overlap z or the workspace");
     return CTD_OK;
 }
-// [a, a + na) and [b, b + nb) share an entry (null: no range)
-static bool mrs_overlap(const double* a, int64_t na, const double* b, int64_t nb) { return a && b && a < b + nb && b < a + na; }
-// z (n entries) and the workspace (CTD_KKT_MINRES_SHARD_WORKSPACE(n, n_ranks) doubles) as ranges: they must be disjoint
-static int32_t mrs_check_disjoint(ctd_handle* h, const char* fn, const double* z, const double* ws, int32_t n_ranks) {
-    const int64_t n = h->model.L.nvar + h->model.L.ncon;
-    if (mrs_overlap(z, n, ws, krylov_shard_workspace(n, n_ranks)))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
+// The prologue of a phase is, in every family: phase_rank -- the handle and its device (on), n_ranks / rank / the handle's steps --,
+// the family's plan (the one step that is its own; it gives the length of the factor's workspace), check_phase_buffers
+static int32_t phase_rank(const OnDevice& on, ctd_handle* h, const char* fn, int32_t n_ranks, int32_t rank) {
+    return on.st ? on.st : check_ranks(h, fn, n_ranks, rank, true);
+}
+// start's own, behind its pointers and the buffers, in the header's order: the inputs (rhs, px, pc; null: none) as ranges against
+// every output range; (the diagonal form's rule for px / pc, which its start has between the two;) then rtol and max_iter
+static int32_t check_start_inputs(ctd_handle* h, const char* fn, const ctd_kkt_system* sys, const double* rhs, const PhaseBufs& b,
+                                  int32_t n_ranks, int64_t schur_len) {
+    const Layout& L = h->model.L;
+    const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks, b.slot);
+    const std::pair<const double*, int64_t> ins[] = {{rhs, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
+    for (const auto& in : ins)
+        if (ranges_overlap(in.first, in.second, b.z, n) || ranges_overlap(in.first, in.second, b.ws, wlen) ||
+            ranges_overlap(in.first, in.second, b.schur_ws, schur_len))
+            return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (" + (b.with_schur ? "z, ws and schur_ws" : "z and ws") +
+                                           ") must not overlap an input buffer");
     return CTD_OK;
 }
-static KrylovShardParams mrs_params(const ctd_handle* h, double* ws, double* z, int32_t n_ranks) {
+static int32_t check_start_scalars(ctd_handle* h, const char* fn, double rtol, int64_t max_iter) {
+    if (const int32_t st = mr_check_rtol(h, fn, rtol)) return st;
+    return mr_check_count(h, fn, "max_iter", max_iter);
+}
+// the Krylov arguments of a call on the handle's shard: what the rank owns (mrs_plan), the workspace cut with `slot`
+static KrylovShardParams shard_krylov_params(const ctd_handle* h, double* ws, double* z, int32_t n_ranks, int64_t slot) {
     const KrylovShardPlan pl = mrs_plan(h);
     const KrylovOwn own{pl.var_lo, pl.var_hi - pl.var_lo, pl.tail_lo, pl.tail_hi - pl.tail_lo, pl.row_lo, pl.last, n_ranks};
-    return krylov_shard_params(ws, pl.n, pl.n_own, own, z);
+    return krylov_shard_params(ws, pl.n, pl.n_own, own, z, slot);
 }
-static int32_t mrs_launched(ctd_handle* h, const char* fn, hipError_t e) {
-    return e == hipSuccess ? CTD_OK : fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-}
-
-int32_t ctd_kkt_minres_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out) {
-    const char* fn = "ctd_kkt_minres_shard_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_minres_shard_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_minres_shard_layout) = " +
-                                       std::to_string(sizeof(ctd_minres_shard_layout)));
-    if (const int32_t st = mrs_check_rank(h, fn, n_ranks, 0, false)) return st;
+// the layout query behind the family's own checks
+static int32_t fill_shard_layout(const ctd_handle* h, int32_t n_ranks, int64_t slot, ctd_minres_shard_layout* out) {
     const KrylovShardPlan pl = mrs_plan(h);
-    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks);
+    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks, slot);
     out->reserved = 0;
     out->n = pl.n; out->n_ranks = n_ranks;
     out->var_begin = pl.var_lo; out->var_end = pl.var_hi;
     out->tail_begin = pl.tail_lo; out->tail_end = pl.tail_hi;
     out->row_begin = pl.row_lo; out->row_end = pl.row_hi;
     out->n_own = pl.n_own; out->n_dot = pl.n_dot; out->nwg = pl.nwg; out->chunk = pl.chunk;
-    out->slot = kKrylovSlot;
+    out->slot = slot;
     out->off_v = l.v; out->off_kv = l.kv;
     out->off_send_a = l.send_a; out->off_send_b = l.send_b;
     out->off_gathered_a = l.gathered_a; out->off_gathered_b = l.gathered_b;
     out->off_state = l.pend;
-    out->workspace = krylov_shard_workspace(pl.n, n_ranks);
+    out->workspace = krylov_shard_workspace(pl.n, n_ranks, slot);
     return CTD_OK;
+}
+// the info call of a family: the state words of its workspace
+static int32_t shard_info(ctd_handle* h, const char* fn, const double* ws_dev, int32_t n_ranks, int64_t slot, ctd_minres_info* info) {
+    if (!h || !STRUCT_OK(h, fn, "info", ctd_minres_info, info)) return CTD_EINVAL;
+    const OnDevice on(h, fn);
+    int32_t st;
+    if ((st = on.st) || (st = check_ranks(h, fn, n_ranks, 0, false)) || (st = check_ptr(h, fn, "ws", ws_dev))) return st;
+    return mr_read_info(h, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks, slot).pend, info);
+}
+
+int32_t ctd_kkt_minres_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out) {
+    const char* fn = "ctd_kkt_minres_shard_layout";
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_minres_shard_layout, out)) return CTD_EINVAL;
+    if (const int32_t st = check_ranks(h, fn, n_ranks, 0, false)) return st;
+    return fill_shard_layout(h, n_ranks, kKrylovSlot, out);
 }
 
 int32_t ctd_kkt_minres_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, const double* rhs_dev, double* z_dev,
@@ -2077,40 +2137,25 @@ int32_t ctd_kkt_minres_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system
     int32_t st;
     if (!mr_structs_ok(h, fn, sys, false, nullptr, &st)) return st;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
-    if ((st = mrs_check_ptr(h, fn, "rhs", rhs_dev)) || (st = mrs_check_ptr(h, fn, "z", z_dev)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev)))
-        return st;
+    if ((st = phase_rank(on, h, fn, n_ranks, rank)) || (st = check_ptr(h, fn, "rhs", rhs_dev))) return st;
+    if ((sys->px && (st = check_ptr(h, fn, "px", sys->px))) || (sys->pc && (st = check_ptr(h, fn, "pc", sys->pc)))) return st;
+    const PhaseBufs b{kKrylovSlot, ws_dev, true, z_dev, false, nullptr};
+    if ((st = check_phase_buffers(h, fn, b, n_ranks, 0)) || (st = check_start_inputs(h, fn, sys, rhs_dev, b, n_ranks, 0))) return st;
     if (!sys->px != !sys->pc)
         return fail(h, CTD_EINVAL, std::string(fn) + ": px and pc are given both (M = diag(1 / px, 1 / pc)) or neither (no preconditioner)");
-    if (sys->px && ((st = mrs_check_ptr(h, fn, "px", sys->px)) || (st = mrs_check_ptr(h, fn, "pc", sys->pc)))) return st;
-    {   // the inputs as ranges against the two output ranges, then the outputs against each other
-        const Layout& L = h->model.L;
-        const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks);
-        const std::pair<const double*, int64_t> ins[] = {{rhs_dev, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
-        for (const auto& in : ins)
-            if (mrs_overlap(in.first, in.second, z_dev, n) || mrs_overlap(in.first, in.second, ws_dev, wlen))
-                return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (z and ws) must not overlap an input buffer");
-    }
-    if ((st = mrs_check_disjoint(h, fn, z_dev, ws_dev, n_ranks))) return st;
-    if (!(rtol >= 0.0)) return fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
-    if (max_iter < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": max_iter = " + std::to_string(max_iter) + ", must be at least 1");
-    return mrs_launched(h, fn, krylov_shard_start(mrs_params(h, ws_dev, z_dev, n_ranks), rhs_dev, sys->px, sys->pc, h->model.L.nvar, rtol,
-                                                  max_iter, h->stream));
+    if ((st = check_start_scalars(h, fn, rtol, max_iter))) return st;
+    return launched(h, fn, krylov_shard_start(shard_krylov_params(h, ws_dev, z_dev, n_ranks, kKrylovSlot), rhs_dev, sys->px, sys->pc,
+                                              h->model.L.nvar, rtol, max_iter, h->stream));
 }
 
-// the prologue of begin and of the phases: z may be absent (begin)
+// begin and the phases: one launch each; z is absent in begin
 static int32_t mrs_phase(ctd_handle* h, const char* fn, double* z_dev, bool with_z, double* ws_dev, int32_t n_ranks, int32_t rank,
                          hipError_t (*launch)(const KrylovShardParams&, hipStream_t)) {
-    if (!h) return CTD_EINVAL;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
     int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
-    if (with_z && (st = mrs_check_ptr(h, fn, "z", z_dev))) return st;
-    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
-    if (with_z && (st = mrs_check_disjoint(h, fn, z_dev, ws_dev, n_ranks))) return st;
-    return mrs_launched(h, fn, launch(mrs_params(h, ws_dev, z_dev, n_ranks), h->stream));
+    if ((st = phase_rank(on, h, fn, n_ranks, rank)) || (st = check_phase_buffers(h, fn, {kKrylovSlot, ws_dev, with_z, z_dev, false, nullptr}, n_ranks, 0)))
+        return st;
+    return launched(h, fn, launch(shard_krylov_params(h, ws_dev, z_dev, n_ranks, kKrylovSlot), h->stream));
 }
 int32_t ctd_kkt_minres_shard_begin_dev_async(ctd_handle* h, double* ws_dev, int32_t n_ranks, int32_t rank) {
     return mrs_phase(h, "ctd_kkt_minres_shard_begin_dev_async", nullptr, false, ws_dev, n_ranks, rank, krylov_shard_begin);
@@ -2126,25 +2171,7 @@ int32_t ctd_kkt_minres_shard_update_dev_async(ctd_handle* h, double* z_dev, doub
 }
 
 int32_t ctd_kkt_minres_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info) {
-    const char* fn = "ctd_kkt_minres_shard_info";
-    if (!h) return CTD_EINVAL;
-    if (!info || info->struct_size != sizeof(ctd_minres_info))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
-                                       std::to_string(sizeof(ctd_minres_info)));
-    const OnDevice on(h, fn);
-    if (on.st) return on.st;
-    int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, 0, false)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
-    KrylovState s;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks).pend, sizeof(s), hipMemcpyDeviceToHost));
-    info->status = s.status;
-    info->iterations = s.itn;
-    info->phibar = s.phibar;
-    info->Anorm = s.Anorm;
-    info->ynorm = s.ynorm;
-    info->beta1 = s.beta1;
-    return CTD_OK;
+    return shard_info(h, "ctd_kkt_minres_shard_info", ws_dev, n_ranks, kKrylovSlot, info);
 }
 
 // ---- the shard form of the log-depth exact Schur preconditioner (plan: ctd_schur_plan.hpp; the kernels of the whole-grid form
@@ -2156,10 +2183,7 @@ static_assert(CTD_KKT_MINRES_SCHUR_SHARD_WORKSPACE(10, 3) == kKrylovVectors * 10
 // every handle is accepted; the plan's own refusals (CSR order, block_rows, the pattern -- walked once per handle)
 static int32_t schur_crs_plan(ctd_handle* h, const char* fn, bool ranges, SchurCrShardPlan& pl) {
     std::string err;
-    const int st = plan_kkt_schur_cr_shard(h->model, h->step_begin, h->step_end, !h->schur_verified, ranges, pl, err);
-    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
-    h->schur_verified = true;
-    return CTD_OK;
+    return schur_planned(h, fn, plan_kkt_schur_cr_shard(h->model, h->step_begin, h->step_end, !h->schur_verified, ranges, pl, err), err);
 }
 // the rank's blocks as the whole-grid problem of n_blocks blocks: the solve's arguments
 static SchurCrShardSolveParams schur_crs_solve_params(const SchurCrShardPlan& pl, int32_t mode, double* ws, const double* r, double* out,
@@ -2174,10 +2198,7 @@ static SchurCrShardSolveParams schur_crs_solve_params(const SchurCrShardPlan& pl
 
 int32_t ctd_kkt_schur_cr_shard_layout(ctd_handle* h, ctd_schur_cr_shard_layout* out) {
     const char* fn = "ctd_kkt_schur_cr_shard_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_schur_cr_shard_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_cr_shard_layout) = " +
-                                       std::to_string(sizeof(ctd_schur_cr_shard_layout)));
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_schur_cr_shard_layout, out)) return CTD_EINVAL;
     SchurCrShardPlan pl;
     if (const int32_t st = schur_crs_plan(h, fn, true, pl)) return st;
     out->reserved = 0;
@@ -2208,18 +2229,14 @@ int32_t ctd_kkt_schur_cr_shard_factor_dev_async(ctd_handle* h, const double* jva
     if (on.st) return on.st;
     SchurCrShardPlan pl;
     if (const int32_t st = schur_crs_plan(h, fn, false, pl)) return st;
-    if (!jvals_dev || !px_dev || !ws_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (jvals, px and ws are required)");
-    if (ws_dev == jvals_dev || ws_dev == px_dev || ws_dev == sc_dev)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (ws) must not be an input buffer");
+    if (const int32_t st = schur_check_factor_args(h, fn, jvals_dev, px_dev, sc_dev, ws_dev)) return st;
     if (const int32_t st = schur_upload_pattern(h, fn)) return st;
     SchurCrShardFactorParams fp{};
     static_cast<SchurCrFactorParams&>(fp) =
         SchurCrFactorParams{pl.n_blocks, pl.first_tail_col, (int32_t)pl.block_rows, (int32_t)pl.n_levels, h->d_schur_rowptr.p + pl.first_row,
                             h->d_schur_colind.p, jvals_dev, px_dev, sc_dev ? sc_dev + pl.first_row : nullptr, ws_dev};
     fp.first = pl.step_begin;
-    const hipError_t e = schur_cr_factor(fp, h->stream);
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, fn, schur_cr_factor(fp, h->stream));
 }
 
 int32_t ctd_kkt_schur_cr_shard_solve_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev) {
@@ -2228,12 +2245,8 @@ int32_t ctd_kkt_schur_cr_shard_solve_dev_async(ctd_handle* h, double* ws_dev, co
     if (on.st) return on.st;
     SchurCrShardPlan pl;
     if (const int32_t st = schur_crs_plan(h, fn, false, pl)) return st;
-    if (!ws_dev || !r_dev || !out_dev) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws, r and out are required)");
-    if (out_dev == r_dev || out_dev == ws_dev || r_dev == ws_dev)
-        return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) and the workspace must not be an input buffer");
-    const hipError_t e = schur_cr_solve(schur_crs_solve_params(pl, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr), h->stream);
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string(fn) + ": kernel launch: " + hipGetErrorString(e));
-    return CTD_OK;
+    if (const int32_t st = schur_check_solve_args(h, fn, ws_dev, r_dev, out_dev, true)) return st;
+    return launched(h, fn, schur_cr_solve(schur_crs_solve_params(pl, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr), h->stream));
 }
 
 int32_t ctd_kkt_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int64_t* first_bad_block) {
@@ -2242,68 +2255,34 @@ int32_t ctd_kkt_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int64_t
     if (on.st) return on.st;
     SchurCrShardPlan pl;
     if (const int32_t st = schur_crs_plan(h, fn, false, pl)) return st;
-    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    int64_t head[5];
-    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
-    if (head[0] != kSchurCrTag || head[1] != pl.n_blocks || head[2] != pl.block_rows || head[3] != pl.n_levels || head[4] != pl.step_begin)
+    std::vector<int64_t> status;       // one word per block of the rank
+    if (const int32_t st = schur_read_status(h, fn, ws_dev, first_bad_block, {kSchurCrTag, pl.n_blocks, pl.block_rows, pl.n_levels, pl.step_begin},
+                                             -1, pl.n_blocks, status))
+        return st;
+    if (status.empty())
         return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle's steps (ctd_kkt_schur_cr_shard_factor_dev_async)");
-    std::vector<int64_t> status((size_t)pl.n_blocks);
-    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
-    *first_bad_block = -1;
-    for (int64_t k = 0; k < pl.n_blocks; ++k)
-        if (status[(size_t)k] >= 0) {
-            *first_bad_block = pl.step_begin + k;
-            break;
-        }
+    const int64_t k = schur_first_set(status);
+    *first_bad_block = k < 0 ? -1 : pl.step_begin + k;
     return CTD_OK;
 }
 
 // The phases of ctd_kkt_minres_shard_* with slots of kKrylovSchurSlot doubles
 static KrylovSchurShardParams mrss_params(const ctd_handle* h, const SchurCrShardPlan& sc, double* ws, double* z, int32_t n_ranks) {
-    const KrylovShardPlan pl = mrs_plan(h);
-    const KrylovOwn own{pl.var_lo, pl.var_hi - pl.var_lo, pl.tail_lo, pl.tail_hi - pl.tail_lo, pl.row_lo, pl.last, n_ranks};
     KrylovSchurShardParams sp{};
-    static_cast<KrylovShardParams&>(sp) = krylov_shard_params(ws, pl.n, pl.n_own, own, z, kKrylovSchurSlot);
+    static_cast<KrylovShardParams&>(sp) = shard_krylov_params(h, ws, z, n_ranks, kKrylovSchurSlot);
     sp.s_lo = h->model.L.nvar + sc.first_row;
     sp.s_hi = sp.s_lo + sc.n_blocks * sc.block_rows;
     sp.s_nwg = schur_solve_grid(sc.n_blocks);
     return sp;
 }
-// z (n entries), the workspace and the factor's workspace as ranges: pairwise disjoint (z may be absent)
-static int32_t mrss_check_disjoint(ctd_handle* h, const char* fn, const double* z, const double* ws, const double* schur_ws, int32_t n_ranks,
-                                   const SchurCrShardPlan* pl) {
-    const int64_t n = h->model.L.nvar + h->model.L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurSlot);
-    if (mrs_overlap(z, n, ws, wlen)) return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
-    if (pl && (mrs_overlap(schur_ws, pl->workspace, ws, wlen) || mrs_overlap(schur_ws, pl->workspace, z, n)))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": schur_ws must not overlap z or the workspace");
-    return CTD_OK;
-}
 
 int32_t ctd_kkt_minres_schur_cr_shard_layout(ctd_handle* h, int32_t n_ranks, ctd_minres_shard_layout* out) {
     const char* fn = "ctd_kkt_minres_schur_cr_shard_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_minres_shard_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_minres_shard_layout) = " +
-                                       std::to_string(sizeof(ctd_minres_shard_layout)));
-    if (const int32_t st = mrs_check_rank(h, fn, n_ranks, 0, false)) return st;
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_minres_shard_layout, out)) return CTD_EINVAL;
+    if (const int32_t st = check_ranks(h, fn, n_ranks, 0, false)) return st;
     SchurCrShardPlan sp;
     if (const int32_t st = schur_crs_plan(h, fn, false, sp)) return st;
-    const KrylovShardPlan pl = mrs_plan(h);
-    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks, kKrylovSchurSlot);
-    out->reserved = 0;
-    out->n = pl.n; out->n_ranks = n_ranks;
-    out->var_begin = pl.var_lo; out->var_end = pl.var_hi;
-    out->tail_begin = pl.tail_lo; out->tail_end = pl.tail_hi;
-    out->row_begin = pl.row_lo; out->row_end = pl.row_hi;
-    out->n_own = pl.n_own; out->n_dot = pl.n_dot; out->nwg = pl.nwg; out->chunk = pl.chunk;
-    out->slot = kKrylovSchurSlot;
-    out->off_v = l.v; out->off_kv = l.kv;
-    out->off_send_a = l.send_a; out->off_send_b = l.send_b;
-    out->off_gathered_a = l.gathered_a; out->off_gathered_b = l.gathered_b;
-    out->off_state = l.pend;
-    out->workspace = krylov_shard_workspace(pl.n, n_ranks, kKrylovSchurSlot);
-    return CTD_OK;
+    return fill_shard_layout(h, n_ranks, kKrylovSchurSlot, out);
 }
 
 int32_t ctd_kkt_minres_schur_cr_shard_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
@@ -2313,102 +2292,67 @@ int32_t ctd_kkt_minres_schur_cr_shard_start_dev_async(ctd_handle* h, const ctd_k
     int32_t st;
     if (!mr_structs_ok(h, fn, sys, false, nullptr, &st)) return st;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
     SchurCrShardPlan pl;
-    if ((st = schur_crs_plan(h, fn, false, pl))) return st;
-    if ((st = mrs_check_ptr(h, fn, "rhs", rhs_dev)) || (st = mrs_check_ptr(h, fn, "z", z_dev)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev)) ||
-        (st = mrs_check_ptr(h, fn, "px", sys->px)) || (st = mrs_check_ptr(h, fn, "pc", sys->pc)) ||
-        (st = mrs_check_ptr(h, fn, "schur_ws", schur_ws_dev)))
+    if ((st = phase_rank(on, h, fn, n_ranks, rank)) || (st = schur_crs_plan(h, fn, false, pl))) return st;
+    if ((st = check_ptr(h, fn, "rhs", rhs_dev)) || (st = check_ptr(h, fn, "px", sys->px)) || (st = check_ptr(h, fn, "pc", sys->pc))) return st;
+    const PhaseBufs b{kKrylovSchurSlot, ws_dev, true, z_dev, true, schur_ws_dev};
+    if ((st = check_phase_buffers(h, fn, b, n_ranks, pl.workspace)) ||
+        (st = check_start_inputs(h, fn, sys, rhs_dev, b, n_ranks, pl.workspace)) || (st = check_start_scalars(h, fn, rtol, max_iter)))
         return st;
-    {   // the inputs as ranges against the output ranges, then the outputs against each other
-        const Layout& L = h->model.L;
-        const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurSlot);
-        const std::pair<const double*, int64_t> ins[] = {{rhs_dev, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
-        for (const auto& in : ins)
-            if (mrs_overlap(in.first, in.second, z_dev, n) || mrs_overlap(in.first, in.second, ws_dev, wlen) ||
-                mrs_overlap(in.first, in.second, schur_ws_dev, pl.workspace))
-                return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (z, ws and schur_ws) must not overlap an input buffer");
-    }
-    if ((st = mrss_check_disjoint(h, fn, z_dev, ws_dev, schur_ws_dev, n_ranks, &pl))) return st;
-    if (!(rtol >= 0.0)) return fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
-    if (max_iter < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": max_iter = " + std::to_string(max_iter) + ", must be at least 1");
     const KrylovSchurShardParams sp = mrss_params(h, pl, ws_dev, z_dev, n_ranks);
     const int64_t nvar = h->model.L.nvar;
     hipError_t e = krylov_schur_shard_start(sp, rhs_dev, sys->px, sys->pc, nvar, rtol, max_iter, h->stream);
     if (e == hipSuccess)
         e = schur_cr_solve(schur_crs_solve_params(pl, SCHUR_START, schur_ws_dev, sp.r2 + nvar, sp.y + nvar, sp.cur, sp.send_a + kSlotSchur),
                            h->stream);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 
-// the prologue of the phases: z, the factor's workspace may be absent
-static int32_t mrss_phase(ctd_handle* h, const char* fn, double* schur_ws, bool with_schur, double* z_dev, bool with_z, double* ws_dev,
-                          int32_t n_ranks, int32_t rank, SchurCrShardPlan& pl) {
-    if (!h) return CTD_EINVAL;
-    const OnDevice on(h, fn);
-    if (on.st) return on.st;
+// the prologue of the phases, with this family's plan
+static int32_t mrss_phase(const OnDevice& on, ctd_handle* h, const char* fn, const PhaseBufs& b, int32_t n_ranks, int32_t rank,
+                          SchurCrShardPlan& pl) {
     int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
-    if ((st = schur_crs_plan(h, fn, false, pl))) return st;
-    if (with_z && (st = mrs_check_ptr(h, fn, "z", z_dev))) return st;
-    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
-    if (with_schur && (st = mrs_check_ptr(h, fn, "schur_ws", schur_ws))) return st;
-    return mrss_check_disjoint(h, fn, with_z ? z_dev : nullptr, ws_dev, schur_ws, n_ranks, with_schur ? &pl : nullptr);
+    if ((st = phase_rank(on, h, fn, n_ranks, rank)) || (st = schur_crs_plan(h, fn, false, pl))) return st;
+    return check_phase_buffers(h, fn, b, n_ranks, pl.workspace);
 }
 int32_t ctd_kkt_minres_schur_cr_shard_begin_dev_async(ctd_handle* h, double* ws_dev, int32_t n_ranks, int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_shard_begin_dev_async";
+    const OnDevice on(h, fn);
     SchurCrShardPlan pl;
-    if (const int32_t st = mrss_phase(h, fn, nullptr, false, nullptr, false, ws_dev, n_ranks, rank, pl)) return st;
-    return mrs_launched(h, fn, krylov_schur_shard_begin(mrss_params(h, pl, ws_dev, nullptr, n_ranks), h->stream));
+    if (const int32_t st = mrss_phase(on, h, fn, {kKrylovSchurSlot, ws_dev, false, nullptr, false, nullptr}, n_ranks, rank, pl)) return st;
+    return launched(h, fn, krylov_schur_shard_begin(mrss_params(h, pl, ws_dev, nullptr, n_ranks), h->stream));
 }
 int32_t ctd_kkt_minres_schur_cr_shard_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_shard_alfa_dev_async";
+    const OnDevice on(h, fn);
     SchurCrShardPlan pl;
-    if (const int32_t st = mrss_phase(h, fn, nullptr, false, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
-    return mrs_launched(h, fn, krylov_shard_alfa(mrss_params(h, pl, ws_dev, z_dev, n_ranks), h->stream));
+    if (const int32_t st = mrss_phase(on, h, fn, {kKrylovSchurSlot, ws_dev, true, z_dev, false, nullptr}, n_ranks, rank, pl)) return st;
+    return launched(h, fn, krylov_shard_alfa(mrss_params(h, pl, ws_dev, z_dev, n_ranks), h->stream));
 }
 int32_t ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
                                                         int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_shard_lanczos_dev_async";
+    const OnDevice on(h, fn);
     SchurCrShardPlan pl;
-    if (const int32_t st = mrss_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    if (const int32_t st = mrss_phase(on, h, fn, {kKrylovSchurSlot, ws_dev, true, z_dev, true, schur_ws_dev}, n_ranks, rank, pl)) return st;
     const KrylovSchurShardParams sp = mrss_params(h, pl, ws_dev, z_dev, n_ranks);
     const int64_t nvar = h->model.L.nvar;
     hipError_t e = krylov_schur_shard_lanczos(sp, h->stream);
     if (e == hipSuccess)
         e = schur_cr_solve(schur_crs_solve_params(pl, SCHUR_ITER, schur_ws_dev, sp.r2 + nvar, sp.y + nvar, sp.cur, sp.send_b + kSlotSchur),
                            h->stream);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 int32_t ctd_kkt_minres_schur_cr_shard_update_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_shard_update_dev_async";
+    const OnDevice on(h, fn);
     SchurCrShardPlan pl;
-    if (const int32_t st = mrss_phase(h, fn, nullptr, false, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
-    return mrs_launched(h, fn, krylov_schur_shard_update(mrss_params(h, pl, ws_dev, z_dev, n_ranks), h->stream));
+    if (const int32_t st = mrss_phase(on, h, fn, {kKrylovSchurSlot, ws_dev, true, z_dev, false, nullptr}, n_ranks, rank, pl)) return st;
+    return launched(h, fn, krylov_schur_shard_update(mrss_params(h, pl, ws_dev, z_dev, n_ranks), h->stream));
 }
 
 int32_t ctd_kkt_minres_schur_cr_shard_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info) {
-    const char* fn = "ctd_kkt_minres_schur_cr_shard_info";
-    if (!h) return CTD_EINVAL;
-    if (!info || info->struct_size != sizeof(ctd_minres_info))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
-                                       std::to_string(sizeof(ctd_minres_info)));
-    const OnDevice on(h, fn);
-    if (on.st) return on.st;
-    int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, 0, false)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
-    KrylovState s;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks, kKrylovSchurSlot).pend, sizeof(s),
-                         hipMemcpyDeviceToHost));
-    info->status = s.status;
-    info->iterations = s.itn;
-    info->phibar = s.phibar;
-    info->Anorm = s.Anorm;
-    info->ynorm = s.ynorm;
-    info->beta1 = s.beta1;
-    return CTD_OK;
+    return shard_info(h, "ctd_kkt_minres_schur_cr_shard_info", ws_dev, n_ranks, kKrylovSchurSlot, info);
 }
 
 // ---- the joined form of the log-depth Schur preconditioner (plan: ctd_schur_plan.hpp; kernels: ctd_schur_cr_joint_kernels.hpp) ---------
@@ -2419,10 +2363,7 @@ static_assert(schur_cr_joint_factor_slot(9) == CTD_KKT_SCHUR_CR_JOINT_FACTOR_SLO
 // every handle is accepted; the plan's own refusals (CSR order, block_rows, the pattern -- walked once per handle --, the split)
 static int32_t schur_crj_plan(ctd_handle* h, const char* fn, int32_t n_ranks, int32_t rank, bool ranges, SchurCrJointPlan& pl) {
     std::string err;
-    const int st = plan_kkt_schur_cr_joint(h->model, n_ranks, rank, h->step_begin, h->step_end, !h->schur_verified, ranges, pl, err);
-    if (st) return fail(h, kPlanStatus[st], std::string(fn) + ": " + err);
-    h->schur_verified = true;
-    return CTD_OK;
+    return schur_planned(h, fn, plan_kkt_schur_cr_joint(h->model, n_ranks, rank, h->step_begin, h->step_end, !h->schur_verified, ranges, pl, err), err);
 }
 static SchurCrJointId schur_crj_id(const SchurCrJointPlan& pl) {
     return SchurCrJointId{pl.step_begin, pl.step_end, (int32_t)pl.n_ranks, (int32_t)pl.rank};
@@ -2461,16 +2402,13 @@ static SchurCrJointSolveParams schur_crj_solve_params(const SchurCrJointPlan& pl
 // [p, p + n) against the workspace
 static int32_t schur_crj_disjoint(ctd_handle* h, const char* fn, const char* name, const double* p, int64_t n, const double* ws,
                                   const SchurCrJointPlan& pl) {
-    if (mrs_overlap(p, n, ws, pl.workspace)) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " overlaps the workspace");
+    if (ranges_overlap(p, n, ws, pl.workspace)) return fail(h, CTD_EINVAL, std::string(fn) + ": " + name + " overlaps the workspace");
     return CTD_OK;
 }
 
 int32_t ctd_kkt_schur_cr_joint_layout(ctd_handle* h, int32_t n_ranks, int32_t rank, ctd_schur_cr_joint_layout* out) {
     const char* fn = "ctd_kkt_schur_cr_joint_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_schur_cr_joint_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_schur_cr_joint_layout) = " +
-                                       std::to_string(sizeof(ctd_schur_cr_joint_layout)));
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_schur_cr_joint_layout, out)) return CTD_EINVAL;
     SchurCrJointPlan pl;
     if (const int32_t st = schur_crj_plan(h, fn, n_ranks, rank, true, pl)) return st;
     out->reserved = 0;
@@ -2501,17 +2439,17 @@ int32_t ctd_kkt_schur_cr_joint_factor_local_dev_async(ctd_handle* h, const doubl
     SchurCrJointPlan pl;
     int32_t st;
     if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
-    if ((st = mrs_check_ptr(h, fn, "jvals", jvals_dev)) || (st = mrs_check_ptr(h, fn, "px", px_dev)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev)))
+    if ((st = check_ptr(h, fn, "jvals", jvals_dev)) || (st = check_ptr(h, fn, "px", px_dev)) || (st = check_ptr(h, fn, "ws", ws_dev)))
         return st;
-    if (sc_dev && (st = mrs_check_ptr(h, fn, "sc", sc_dev))) return st;
-    if (n_ranks > 1 && (st = mrs_check_ptr(h, fn, "send", send_dev))) return st;
+    if (sc_dev && (st = check_ptr(h, fn, "sc", sc_dev))) return st;
+    if (n_ranks > 1 && (st = check_ptr(h, fn, "send", send_dev))) return st;
     const Layout& L = h->model.L;
     if ((st = schur_crj_disjoint(h, fn, "jvals", jvals_dev, h->model.nnzj, ws_dev, pl)) || (st = schur_crj_disjoint(h, fn, "px", px_dev, L.nvar, ws_dev, pl)) ||
         (st = schur_crj_disjoint(h, fn, "sc", sc_dev, L.ncon, ws_dev, pl)) ||
         (n_ranks > 1 && (st = schur_crj_disjoint(h, fn, "send", send_dev, pl.factor_slot, ws_dev, pl))))
         return st;
-    if (n_ranks > 1 && (mrs_overlap(send_dev, pl.factor_slot, jvals_dev, h->model.nnzj) || mrs_overlap(send_dev, pl.factor_slot, px_dev, L.nvar) ||
-                        mrs_overlap(send_dev, pl.factor_slot, sc_dev, L.ncon)))
+    if (n_ranks > 1 && (ranges_overlap(send_dev, pl.factor_slot, jvals_dev, h->model.nnzj) || ranges_overlap(send_dev, pl.factor_slot, px_dev, L.nvar) ||
+                        ranges_overlap(send_dev, pl.factor_slot, sc_dev, L.ncon)))
         return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (ws and send) must not overlap an input buffer");
     if ((st = schur_upload_pattern(h, fn))) return st;
     SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
@@ -2529,7 +2467,7 @@ int32_t ctd_kkt_schur_cr_joint_factor_local_dev_async(ctd_handle* h, const doubl
     hipError_t e = n_ranks > 1 ? schur_cr_joint_interface(p, h->stream) : hipSuccess;      // (one rank: no interface, nothing behind the interior's part is read)
     if (e == hipSuccess) e = schur_cr_factor(fp, h->stream);
     if (e == hipSuccess && n_ranks > 1) e = schur_cr_joint_spikes(p, h->stream);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 
 int32_t ctd_kkt_schur_cr_joint_factor_join_dev_async(ctd_handle* h, double* ws_dev, const double* gathered_dev, int32_t n_ranks, int32_t rank) {
@@ -2539,14 +2477,14 @@ int32_t ctd_kkt_schur_cr_joint_factor_join_dev_async(ctd_handle* h, double* ws_d
     SchurCrJointPlan pl;
     int32_t st;
     if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
-    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
+    if ((st = check_ptr(h, fn, "ws", ws_dev))) return st;
     if (n_ranks == 1) return CTD_OK;
-    if ((st = mrs_check_ptr(h, fn, "gathered", gathered_dev))) return st;
+    if ((st = check_ptr(h, fn, "gathered", gathered_dev))) return st;
     if ((st = schur_crj_disjoint(h, fn, "gathered", gathered_dev, n_ranks * pl.factor_slot, ws_dev, pl))) return st;
     SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
     p.gathered = gathered_dev;
     p.slot = pl.factor_slot;
-    return mrs_launched(h, fn, schur_cr_joint_factor_join(p, h->stream));
+    return launched(h, fn, schur_cr_joint_factor_join(p, h->stream));
 }
 
 int32_t ctd_kkt_schur_cr_joint_solve_local_dev_async(ctd_handle* h, double* ws_dev, const double* r_dev, double* out_dev, double* send_dev,
@@ -2557,15 +2495,15 @@ int32_t ctd_kkt_schur_cr_joint_solve_local_dev_async(ctd_handle* h, double* ws_d
     SchurCrJointPlan pl;
     int32_t st;
     if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
-    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev)) || (st = mrs_check_ptr(h, fn, "r", r_dev)) || (st = mrs_check_ptr(h, fn, "out", out_dev)))
+    if ((st = check_ptr(h, fn, "ws", ws_dev)) || (st = check_ptr(h, fn, "r", r_dev)) || (st = check_ptr(h, fn, "out", out_dev)))
         return st;
-    if (n_ranks > 1 && (st = mrs_check_ptr(h, fn, "send", send_dev))) return st;
+    if (n_ranks > 1 && (st = check_ptr(h, fn, "send", send_dev))) return st;
     const int64_t ncon = h->model.L.ncon;
-    if (mrs_overlap(out_dev, ncon, r_dev, ncon)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not overlap r");
+    if (ranges_overlap(out_dev, ncon, r_dev, ncon)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not overlap r");
     if ((st = schur_crj_disjoint(h, fn, "r", r_dev, ncon, ws_dev, pl)) || (st = schur_crj_disjoint(h, fn, "out", out_dev, ncon, ws_dev, pl)))
         return st;
-    if (n_ranks > 1 && (mrs_overlap(send_dev, pl.solve_slot, r_dev, ncon) || mrs_overlap(send_dev, pl.solve_slot, out_dev, ncon) ||
-                        mrs_overlap(send_dev, pl.solve_slot, ws_dev, pl.workspace)))
+    if (n_ranks > 1 && (ranges_overlap(send_dev, pl.solve_slot, r_dev, ncon) || ranges_overlap(send_dev, pl.solve_slot, out_dev, ncon) ||
+                        ranges_overlap(send_dev, pl.solve_slot, ws_dev, pl.workspace)))
         return fail(h, CTD_EINVAL, std::string(fn) + ": send must not overlap r, out or the workspace");
     hipError_t e = schur_cr_solve(schur_crj_solve_params(pl, SCHUR_PLAIN, ws_dev, r_dev, out_dev, nullptr, nullptr), h->stream);
     if (e == hipSuccess && n_ranks > 1) {
@@ -2575,7 +2513,7 @@ int32_t ctd_kkt_schur_cr_joint_solve_local_dev_async(ctd_handle* h, double* ws_d
         p.send = send_dev;
         e = schur_cr_joint_solve_record(p, h->stream);
     }
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 
 int32_t ctd_kkt_schur_cr_joint_solve_join_dev_async(ctd_handle* h, double* ws_dev, const double* gathered_dev, double* out_dev, int32_t n_ranks,
@@ -2586,18 +2524,18 @@ int32_t ctd_kkt_schur_cr_joint_solve_join_dev_async(ctd_handle* h, double* ws_de
     SchurCrJointPlan pl;
     int32_t st;
     if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
-    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev)) || (st = mrs_check_ptr(h, fn, "out", out_dev))) return st;
+    if ((st = check_ptr(h, fn, "ws", ws_dev)) || (st = check_ptr(h, fn, "out", out_dev))) return st;
     if (n_ranks == 1) return CTD_OK;
-    if ((st = mrs_check_ptr(h, fn, "gathered", gathered_dev))) return st;
+    if ((st = check_ptr(h, fn, "gathered", gathered_dev))) return st;
     const int64_t ncon = h->model.L.ncon, glen = n_ranks * pl.solve_slot;
     if ((st = schur_crj_disjoint(h, fn, "gathered", gathered_dev, glen, ws_dev, pl)) || (st = schur_crj_disjoint(h, fn, "out", out_dev, ncon, ws_dev, pl)))
         return st;
-    if (mrs_overlap(gathered_dev, glen, out_dev, ncon)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not overlap gathered");
+    if (ranges_overlap(gathered_dev, glen, out_dev, ncon)) return fail(h, CTD_EINVAL, std::string(fn) + ": the output (out) must not overlap gathered");
     SchurCrJointParams p = schur_crj_params(h, pl, ws_dev);
     p.gathered = gathered_dev;
     p.slot = pl.solve_slot;
     p.out = out_dev;
-    return mrs_launched(h, fn, schur_cr_joint_solve_join(p, h->stream));
+    return launched(h, fn, schur_cr_joint_solve_join(p, h->stream));
 }
 
 int32_t ctd_kkt_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, int32_t rank, int64_t* first_bad_block) {
@@ -2606,20 +2544,19 @@ int32_t ctd_kkt_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t
     if (on.st) return on.st;
     SchurCrJointPlan pl;
     if (const int32_t st = schur_crj_plan(h, fn, n_ranks, rank, false, pl)) return st;
-    if (!ws_dev || !first_bad_block) return fail(h, CTD_EINVAL, std::string(fn) + ": null argument (ws and first_bad_block are required)");
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    int64_t head[9];
-    HIP_TRY(h, hipMemcpy(head, ws_dev, sizeof(head), hipMemcpyDeviceToHost));
-    if (head[0] != kSchurCrJointTag || head[1] != pl.n_int || head[2] != pl.block_rows || head[3] != pl.n_levels || head[4] != pl.int_begin ||
-        head[5] != pl.step_begin || head[6] != pl.step_end || head[7] != pl.n_ranks || head[8] != pl.rank)
+    std::vector<int64_t> status;       // one word per block of the interior
+    if (const int32_t st = schur_read_status(h, fn, ws_dev, first_bad_block,
+                                             {kSchurCrJointTag, pl.n_int, pl.block_rows, pl.n_levels, pl.int_begin, pl.step_begin, pl.step_end,
+                                              pl.n_ranks, pl.rank},
+                                             -1, pl.n_int, status))
+        return st;
+    if (status.empty())
         return fail(h, CTD_EINVAL, std::string(fn) + ": the workspace holds no factor of this handle's steps as rank " + std::to_string(rank) + " of " +
                                        std::to_string(n_ranks) + " (ctd_kkt_schur_cr_joint_factor_local_dev_async)");
-    std::vector<int64_t> status((size_t)pl.n_int), red((size_t)pl.n_sep);
-    HIP_TRY(h, hipMemcpy(status.data(), ws_dev + kSchurFixed, sizeof(int64_t) * status.size(), hipMemcpyDeviceToHost));
+    std::vector<int64_t> red((size_t)pl.n_sep);       // ... and per separator of the reduced factor
     HIP_TRY(h, hipMemcpy(red.data(), ws_dev + pl.off_reduced, sizeof(int64_t) * red.size(), hipMemcpyDeviceToHost));
-    int64_t bad = -1;
-    for (int64_t k = 0; k < pl.n_int && bad < 0; ++k)
-        if (status[(size_t)k] >= 0) bad = pl.int_begin + k;
+    int64_t bad = schur_first_set(status);
+    if (bad >= 0) bad += pl.int_begin;
     for (int64_t k = 0; k < pl.n_ranks - 1; ++k)
         if (red[(size_t)k] >= 0 && (bad < 0 || red[(size_t)k] < bad)) bad = red[(size_t)k];
     *first_bad_block = bad;
@@ -2632,30 +2569,20 @@ static_assert(kKrylovSchurJointSlot - kSlotJoint == kSchurJointSolveSlot, "the s
 static_assert(CTD_KKT_MINRES_SCHUR_JOINT_WORKSPACE(10, 3) == kKrylovVectors * 10 + 8 * kKrylovSchurJointSlot + 96, "the workspace of the header");
 
 static KrylovSchurJointParams mrsj_params(const ctd_handle* h, const SchurCrJointPlan& sc, double* ws, double* z, const double* schur_ws) {
-    const KrylovShardPlan pl = mrs_plan(h);
-    const KrylovOwn own{pl.var_lo, pl.var_hi - pl.var_lo, pl.tail_lo, pl.tail_hi - pl.tail_lo, pl.row_lo, pl.last, (int32_t)sc.n_ranks};
     KrylovSchurJointParams sp{};
-    static_cast<KrylovShardParams&>(sp) = krylov_shard_params(ws, pl.n, pl.n_own, own, z, kKrylovSchurJointSlot);
+    static_cast<KrylovShardParams&>(sp) = shard_krylov_params(h, ws, z, (int32_t)sc.n_ranks, kKrylovSchurJointSlot);
     sp.s_lo = h->model.L.nvar + sc.first_row;
     sp.s_hi = h->model.L.nvar + sc.step_end * sc.block_rows;
     sp.s_nwg = schur_solve_grid(sc.n_int);
     sp.sigma = schur_ws ? schur_ws + sc.off_sigma : nullptr;
     return sp;
 }
-// the prologue of every phase: rank, plan, pointers, disjoint ranges (z and the factor's workspace may be absent)
-static int32_t mrsj_phase(ctd_handle* h, const char* fn, const double* schur_ws, bool with_schur, const double* z_dev, bool with_z,
-                          const double* ws_dev, int32_t n_ranks, int32_t rank, SchurCrJointPlan& pl) {
+// the prologue of the phases, with this family's plan
+static int32_t mrsj_phase(const OnDevice& on, ctd_handle* h, const char* fn, const PhaseBufs& b, int32_t n_ranks, int32_t rank,
+                          SchurCrJointPlan& pl) {
     int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
-    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
-    if (with_z && (st = mrs_check_ptr(h, fn, "z", z_dev))) return st;
-    if ((st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
-    if (with_schur && (st = mrs_check_ptr(h, fn, "schur_ws", schur_ws))) return st;
-    const int64_t n = h->model.L.nvar + h->model.L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurJointSlot);
-    if (with_z && mrs_overlap(z_dev, n, ws_dev, wlen)) return fail(h, CTD_EINVAL, std::string(fn) + ": z and ws must be different buffers: z overlaps the workspace");
-    if (with_schur && (mrs_overlap(schur_ws, pl.workspace, ws_dev, wlen) || (with_z && mrs_overlap(schur_ws, pl.workspace, z_dev, n))))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": schur_ws must not overlap z or the workspace");
-    return CTD_OK;
+    if ((st = phase_rank(on, h, fn, n_ranks, rank)) || (st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    return check_phase_buffers(h, fn, b, n_ranks, pl.workspace);
 }
 // behind start's and (B)'s launch: the interior's solve with its partial sums into the send slot, then the solve record behind them
 static hipError_t mrsj_local(const ctd_handle* h, const SchurCrJointPlan& pl, const KrylovSchurJointParams& sp, int32_t mode, double* schur_ws,
@@ -2686,29 +2613,11 @@ static hipError_t mrsj_join(const ctd_handle* h, const SchurCrJointPlan& pl, con
 
 int32_t ctd_kkt_minres_schur_cr_joint_layout(ctd_handle* h, int32_t n_ranks, int32_t rank, ctd_minres_shard_layout* out) {
     const char* fn = "ctd_kkt_minres_schur_cr_joint_layout";
-    if (!h) return CTD_EINVAL;
-    if (!out || out->struct_size != sizeof(ctd_minres_shard_layout))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": layout is null or its struct_size is not sizeof(ctd_minres_shard_layout) = " +
-                                       std::to_string(sizeof(ctd_minres_shard_layout)));
+    if (!h || !STRUCT_OK(h, fn, "layout", ctd_minres_shard_layout, out)) return CTD_EINVAL;
     int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true))) return st;
     SchurCrJointPlan sp;
-    if ((st = schur_crj_plan(h, fn, n_ranks, rank, false, sp))) return st;
-    const KrylovShardPlan pl = mrs_plan(h);
-    const KrylovShardLayout l = krylov_shard_layout(pl.n, n_ranks, kKrylovSchurJointSlot);
-    out->reserved = 0;
-    out->n = pl.n; out->n_ranks = n_ranks;
-    out->var_begin = pl.var_lo; out->var_end = pl.var_hi;
-    out->tail_begin = pl.tail_lo; out->tail_end = pl.tail_hi;
-    out->row_begin = pl.row_lo; out->row_end = pl.row_hi;
-    out->n_own = pl.n_own; out->n_dot = pl.n_dot; out->nwg = pl.nwg; out->chunk = pl.chunk;
-    out->slot = kKrylovSchurJointSlot;
-    out->off_v = l.v; out->off_kv = l.kv;
-    out->off_send_a = l.send_a; out->off_send_b = l.send_b;
-    out->off_gathered_a = l.gathered_a; out->off_gathered_b = l.gathered_b;
-    out->off_state = l.pend;
-    out->workspace = krylov_shard_workspace(pl.n, n_ranks, kKrylovSchurJointSlot);
-    return CTD_OK;
+    if ((st = check_ranks(h, fn, n_ranks, rank, true)) || (st = schur_crj_plan(h, fn, n_ranks, rank, false, sp))) return st;
+    return fill_shard_layout(h, n_ranks, kKrylovSchurJointSlot, out);
 }
 
 int32_t ctd_kkt_minres_schur_cr_joint_start_dev_async(ctd_handle* h, const ctd_kkt_system* sys, double* schur_ws_dev, const double* rhs_dev,
@@ -2718,95 +2627,59 @@ int32_t ctd_kkt_minres_schur_cr_joint_start_dev_async(ctd_handle* h, const ctd_k
     int32_t st;
     if (!mr_structs_ok(h, fn, sys, false, nullptr, &st)) return st;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
     SchurCrJointPlan pl;
-    if ((st = mrs_check_rank(h, fn, n_ranks, rank, true)) || (st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
-    if ((st = mrs_check_ptr(h, fn, "rhs", rhs_dev)) || (st = mrs_check_ptr(h, fn, "px", sys->px)) || (st = mrs_check_ptr(h, fn, "pc", sys->pc))) return st;
-    if ((st = mrsj_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl))) return st;
-    {   // the inputs as ranges against the output ranges
-        const Layout& L = h->model.L;
-        const int64_t n = L.nvar + L.ncon, wlen = krylov_shard_workspace(n, n_ranks, kKrylovSchurJointSlot);
-        const std::pair<const double*, int64_t> ins[] = {{rhs_dev, n}, {sys->px, L.nvar}, {sys->pc, L.ncon}};
-        for (const auto& in : ins)
-            if (mrs_overlap(in.first, in.second, z_dev, n) || mrs_overlap(in.first, in.second, ws_dev, wlen) ||
-                mrs_overlap(in.first, in.second, schur_ws_dev, pl.workspace))
-                return fail(h, CTD_EINVAL, std::string(fn) + ": the outputs (z, ws and schur_ws) must not overlap an input buffer");
-    }
-    if (!(rtol >= 0.0)) return fail(h, CTD_EINVAL, std::string(fn) + ": rtol must not be negative (or NaN)");
-    if (max_iter < 1) return fail(h, CTD_EINVAL, std::string(fn) + ": max_iter = " + std::to_string(max_iter) + ", must be at least 1");
+    if ((st = phase_rank(on, h, fn, n_ranks, rank)) || (st = schur_crj_plan(h, fn, n_ranks, rank, false, pl))) return st;
+    if ((st = check_ptr(h, fn, "rhs", rhs_dev)) || (st = check_ptr(h, fn, "px", sys->px)) || (st = check_ptr(h, fn, "pc", sys->pc))) return st;
+    const PhaseBufs b{kKrylovSchurJointSlot, ws_dev, true, z_dev, true, schur_ws_dev};
+    if ((st = check_phase_buffers(h, fn, b, n_ranks, pl.workspace)) ||
+        (st = check_start_inputs(h, fn, sys, rhs_dev, b, n_ranks, pl.workspace)) || (st = check_start_scalars(h, fn, rtol, max_iter)))
+        return st;
     const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, z_dev, schur_ws_dev);
     hipError_t e = krylov_schur_joint_start(sp, rhs_dev, sys->px, sys->pc, h->model.L.nvar, rtol, max_iter, h->stream);
     if (e == hipSuccess) e = mrsj_local(h, pl, sp, SCHUR_START, schur_ws_dev, sp.send_a);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 int32_t ctd_kkt_minres_schur_cr_joint_begin_dev_async(ctd_handle* h, double* schur_ws_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_joint_begin_dev_async";
-    if (!h) return CTD_EINVAL;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
     SchurCrJointPlan pl;
-    if (const int32_t st = mrsj_phase(h, fn, schur_ws_dev, true, nullptr, false, ws_dev, n_ranks, rank, pl)) return st;
+    if (const int32_t st = mrsj_phase(on, h, fn, {kKrylovSchurJointSlot, ws_dev, false, nullptr, true, schur_ws_dev}, n_ranks, rank, pl)) return st;
     const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, nullptr, schur_ws_dev);
     hipError_t e = mrsj_join(h, pl, sp, SCHUR_START, schur_ws_dev, sp.gathered_a);
     if (e == hipSuccess) e = krylov_schur_joint_begin(sp, h->stream);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 int32_t ctd_kkt_minres_schur_cr_joint_alfa_dev_async(ctd_handle* h, double* z_dev, double* ws_dev, int32_t n_ranks, int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_joint_alfa_dev_async";
-    if (!h) return CTD_EINVAL;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
     SchurCrJointPlan pl;
-    if (const int32_t st = mrsj_phase(h, fn, nullptr, false, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
-    return mrs_launched(h, fn, krylov_shard_alfa(mrsj_params(h, pl, ws_dev, z_dev, nullptr), h->stream));
+    if (const int32_t st = mrsj_phase(on, h, fn, {kKrylovSchurJointSlot, ws_dev, true, z_dev, false, nullptr}, n_ranks, rank, pl)) return st;
+    return launched(h, fn, krylov_shard_alfa(mrsj_params(h, pl, ws_dev, z_dev, nullptr), h->stream));
 }
 int32_t ctd_kkt_minres_schur_cr_joint_lanczos_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
                                                         int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_joint_lanczos_dev_async";
-    if (!h) return CTD_EINVAL;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
     SchurCrJointPlan pl;
-    if (const int32_t st = mrsj_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    if (const int32_t st = mrsj_phase(on, h, fn, {kKrylovSchurJointSlot, ws_dev, true, z_dev, true, schur_ws_dev}, n_ranks, rank, pl)) return st;
     const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, z_dev, schur_ws_dev);
     hipError_t e = krylov_schur_joint_lanczos(sp, h->stream);
     if (e == hipSuccess) e = mrsj_local(h, pl, sp, SCHUR_ITER, schur_ws_dev, sp.send_b);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 int32_t ctd_kkt_minres_schur_cr_joint_update_dev_async(ctd_handle* h, double* schur_ws_dev, double* z_dev, double* ws_dev, int32_t n_ranks,
                                                        int32_t rank) {
     const char* fn = "ctd_kkt_minres_schur_cr_joint_update_dev_async";
-    if (!h) return CTD_EINVAL;
     const OnDevice on(h, fn);
-    if (on.st) return on.st;
     SchurCrJointPlan pl;
-    if (const int32_t st = mrsj_phase(h, fn, schur_ws_dev, true, z_dev, true, ws_dev, n_ranks, rank, pl)) return st;
+    if (const int32_t st = mrsj_phase(on, h, fn, {kKrylovSchurJointSlot, ws_dev, true, z_dev, true, schur_ws_dev}, n_ranks, rank, pl)) return st;
     const KrylovSchurJointParams sp = mrsj_params(h, pl, ws_dev, z_dev, schur_ws_dev);
     hipError_t e = mrsj_join(h, pl, sp, SCHUR_ITER, schur_ws_dev, sp.gathered_b);
     if (e == hipSuccess) e = krylov_schur_joint_update(sp, h->stream);
-    return mrs_launched(h, fn, e);
+    return launched(h, fn, e);
 }
 int32_t ctd_kkt_minres_schur_cr_joint_info(ctd_handle* h, const double* ws_dev, int32_t n_ranks, ctd_minres_info* info) {
-    const char* fn = "ctd_kkt_minres_schur_cr_joint_info";
-    if (!h) return CTD_EINVAL;
-    if (!info || info->struct_size != sizeof(ctd_minres_info))
-        return fail(h, CTD_EINVAL, std::string(fn) + ": info is null or its struct_size is not sizeof(ctd_minres_info) = " +
-                                       std::to_string(sizeof(ctd_minres_info)));
-    const OnDevice on(h, fn);
-    if (on.st) return on.st;
-    int32_t st;
-    if ((st = mrs_check_rank(h, fn, n_ranks, 0, false)) || (st = mrs_check_ptr(h, fn, "ws", ws_dev))) return st;
-    KrylovState s;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(&s, ws_dev + krylov_shard_layout(h->model.L.nvar + h->model.L.ncon, n_ranks, kKrylovSchurJointSlot).pend, sizeof(s),
-                         hipMemcpyDeviceToHost));
-    info->status = s.status;
-    info->iterations = s.itn;
-    info->phibar = s.phibar;
-    info->Anorm = s.Anorm;
-    info->ynorm = s.ynorm;
-    info->beta1 = s.beta1;
-    return CTD_OK;
+    return shard_info(h, "ctd_kkt_minres_schur_cr_joint_info", ws_dev, n_ranks, kKrylovSchurJointSlot, info);
 }
 
 int32_t ctd_obj(ctd_handle* h, const double* x, double* f) {
@@ -3063,8 +2936,7 @@ static int32_t enqueue_hess(ctd_handle* h, const double* x_dev, const double* y_
             e = launch_hess<P>(hp, x_dev, y_dev, h->hess_lds_bytes, h->stream, te0, te1, nb);
         }
     });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, nullptr, e);
 }
 
 int32_t ctd_hess_coord_dev_async(ctd_handle* h, const double* x_dev, const double* y_dev, double obj_weight, double* vals_dev) {
@@ -3210,8 +3082,7 @@ int32_t ctd_eval_all_dev_async(ctd_handle* h, const double* x_dev, const double*
         using P = typename decltype(tag)::type;
         e = launch_iter<P>(ip, x_dev, y_dev, lds, h->stream);
     });
-    if (e != hipSuccess) return fail(h, CTD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return CTD_OK;
+    return launched(h, nullptr, e);
 }
 
 // out[0..9]: grid (workgroups), block, LDS bytes, steps per tile, CSC period of the lower triangle, edge entries, eval lanes

@@ -38,7 +38,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .docp import SchurCrJointPrecond, SchurCrShardPrecond
+from .docp import _PHASE_FAMILIES, SchurCrJointPrecond, _phase_family
 
 # Rehearsal knob: run the collectives on a ONE-rank group too (they are no-ops for the data, but every RCCL call of the
 # multi-GPU path -- in-place / padded all-gather, halo all-gather, all-reduce, broadcast -- is issued exactly as on 8 GPUs),
@@ -189,31 +189,24 @@ class MinresPhases:
 
     def __init__(self, ranks, halo, gather):
         self.ranks, self.halo, self.gather = ranks, halo, gather
-        # a SchurCrShardPrecond per rank: the phase family ctd_kkt_minres_schur_cr_shard_* on workspaces with the larger slots --
-        # the same phases, the same gathers; on every rank or on none
-        self.schur = isinstance(ranks[0].precond, SchurCrShardPrecond)
-        if any(isinstance(r.precond, SchurCrShardPrecond) != self.schur for r in ranks):
-            raise ValueError("precond: a SchurCrShardPrecond on every shard or on none")
-        # ... or a SchurCrJointPrecond per rank (factored AND joined): the family ctd_kkt_minres_schur_cr_joint_*, whose slots also carry
-        # the solve records; begin and (C) take the factor's workspace
-        self.joint = isinstance(ranks[0].precond, SchurCrJointPrecond)
-        if any(isinstance(r.precond, SchurCrJointPrecond) != self.joint for r in ranks):
-            raise ValueError("precond: a SchurCrJointPrecond on every shard or on none")
+        # The phase family (docp._PHASE_FAMILIES), from the first rank's preconditioner: a SchurCrShardPrecond per rank is the family
+        # ctd_kkt_minres_schur_cr_shard_* on workspaces with the larger slots; a SchurCrJointPrecond per rank (factored AND joined)
+        # the family ctd_kkt_minres_schur_cr_joint_*, whose slots also carry the solve records and whose begin and (C) take the
+        # factor's workspace.  The same phases, the same gathers; either kind on every rank or on none
+        self.family = _phase_family(ranks[0].precond)
+        for fam in _PHASE_FAMILIES:
+            if fam.precond is not None and any(isinstance(r.precond, fam.precond) != (fam is self.family) for r in ranks):
+                raise ValueError(f"precond: a {fam.precond.__name__} on every shard or on none")
+
+    def _phase(self, phase):
+        for r in self.ranks:
+            r.docp._phase(self.family, phase, r.precond, r.z, r.w, r.rank)
 
     def start(self, rtol, max_iter):
         for r in self.ranks:
-            if self.joint:
-                r.docp.kkt_minres_schur_joint_start(r.precond, r.rhs, r.z, r.w, r.rank, rtol=rtol, max_iter=max_iter)
-            elif self.schur:
-                r.docp.kkt_minres_schur_shard_start(r.precond, r.rhs, r.z, r.w, r.rank, rtol=rtol, max_iter=max_iter)
-            else:
-                r.docp.kkt_minres_shard_start(r.rhs, r.z, r.w, r.rank, precond=r.precond, rtol=rtol, max_iter=max_iter)
+            r.docp._phase_start(self.family, r.precond, r.rhs, r.z, r.w, r.rank, rtol, max_iter)
         self.gather("a")
-        for r in self.ranks:
-            if self.joint:
-                r.docp.kkt_minres_schur_joint_begin(r.precond, r.w, r.rank)
-            else:
-                (r.docp.kkt_minres_schur_shard_begin if self.schur else r.docp.kkt_minres_shard_begin)(r.w, r.rank)
+        self._phase("begin")
 
     def iterate(self, k):
         """k iterations: per iteration the halo of v, K v (two launches per rank), (A), the gather of slot A, (B), the gather of
@@ -222,28 +215,15 @@ class MinresPhases:
             self.halo()
             for r in self.ranks:
                 r.docp.kktprod_shard(r.x, r.y, r.w.v_x, r.w.v_c, r.sigma, r.sx, r.sc, out=(r.w.kv_x, r.w.kv_c))
-                alfa = r.docp.kkt_minres_schur_joint_alfa if self.joint else (r.docp.kkt_minres_schur_shard_alfa if self.schur else r.docp.kkt_minres_shard_alfa)
-                alfa(r.z, r.w, r.rank)
+                r.docp._phase(self.family, "alfa", r.precond, r.z, r.w, r.rank)
             self.gather("a")
-            for r in self.ranks:
-                if self.joint:
-                    r.docp.kkt_minres_schur_joint_lanczos(r.precond, r.z, r.w, r.rank)
-                elif self.schur:
-                    r.docp.kkt_minres_schur_shard_lanczos(r.precond, r.z, r.w, r.rank)
-                else:
-                    r.docp.kkt_minres_shard_lanczos(r.z, r.w, r.rank)
+            self._phase("lanczos")
             self.gather("b")
-            for r in self.ranks:
-                if self.joint:
-                    r.docp.kkt_minres_schur_joint_update(r.precond, r.z, r.w, r.rank)
-                else:
-                    (r.docp.kkt_minres_schur_shard_update if self.schur else r.docp.kkt_minres_shard_update)(r.z, r.w, r.rank)
+            self._phase("update")
 
     def infos(self):
         """every rank's MinresInfo: the one host read per chunk"""
-        if self.joint:
-            return [r.docp.kkt_minres_schur_joint_info(r.w) for r in self.ranks]
-        return [(r.docp.kkt_minres_schur_shard_info if self.schur else r.docp.kkt_minres_shard_info)(r.w) for r in self.ranks]
+        return [r.docp._phase_info(self.family, r.w) for r in self.ranks]
 
     def solve(self, rtol, max_iter, check_every, on_chunk=None):
         """start, then chunks of check_every iterations with one read of the state between chunks.  Every rank's state has the
@@ -299,11 +279,7 @@ def minres_shards(handles, xs, y, rhs, obj_weight=1.0, sx=None, sc=None, precond
     for k, h in enumerate(handles):
         if h._stream_raw != cur:
             h.set_stream(cur)
-        if isinstance(pres[k], SchurCrJointPrecond):
-            new_ws = lambda G, h=h, k=k: h.kkt_minres_schur_joint_workspace(G, k)      # noqa: E731
-        else:
-            new_ws = h.kkt_minres_schur_shard_workspace if isinstance(pres[k], SchurCrShardPrecond) else h.kkt_minres_shard_workspace
-        w = workspaces[k] if workspaces is not None else new_ws(G)
+        w = workspaces[k] if workspaces is not None else h._phase_workspace(_phase_family(pres[k]), G, k)
         z = out[k] if out is not None else torch.empty(w.layout.n, dtype=torch.float64, device=dev)
         ranks.append(_MinresRank(h, k, w, z, xs[k], ys[k], obj_weight, sxs[k], scs[k], rhss[k], pres[k]))
     if G == 1:
@@ -414,9 +390,7 @@ class ShardedDOCP:
         self._phalo = {}                    # (layout, device) -> index sets and buffers of exchange_product_halo / _rows
         self._vv = None
         self._f = None
-        self._minres_ws = None              # the workspace of `kkt_minres`, kept between solves
-        self._minres_schur_ws = None        # ... and of its solves with a SchurCrShardPrecond (larger slots)
-        self._minres_joint_ws = None        # ... with a SchurCrJointPrecond (larger again)
+        self._minres_ws = {}                # the workspaces of `kkt_minres`, kept between solves: one per phase family
         self._peer = None                   # data_ptr of the x buffer the peer table is ACTIVE for (enable_peer_x), None: off
         self._peer_tables = {}              # x data_ptr -> (the tensor itself, mapped pointers of the other ranks' buffers): the
                                             # tensor is kept alive so the allocator cannot hand its address to another buffer
@@ -931,6 +905,12 @@ class ShardedDOCP:
         this rank's own Jacobian values on a CSR handle (`jvals`: full-length, this rank's rows valid; None: evaluated here),
         `kkt_diag_precond` and ONE halo exchange of px (`exchange_product_halo`: the next rank's first node); the factor needs no
         collective.  Returns the SchurCrShardPrecond for `kkt_minres(precond=P)`.  Inputs as `kkt_diag_precond`."""
+        px, pc, jvals = self._schur_cr_inputs(x, y, obj_weight, sx, sc, floor, jvals, x_halo_valid, y_halo_valid)
+        return self.docp.kkt_schur_cr_shard_factor(jvals, px, pc, sc)
+
+    def _schur_cr_inputs(self, x, y, obj_weight, sx, sc, floor, jvals, x_halo_valid, y_halo_valid):
+        """what both forms of the log-depth Schur preconditioner are factored from: the pair of `kkt_diag_precond`, px with its halo
+        (the next rank's first node), this rank's Jacobian values (evaluated here when None)"""
         d = self.docp
         px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc, floor, x_halo_valid, y_halo_valid)
         self.exchange_product_halo(px)
@@ -938,7 +918,7 @@ class ShardedDOCP:
             jvals = torch.empty(d.nnzj, dtype=torch.float64, device=x.device)
             c = torch.empty(d.dim_NLP_constraints, dtype=torch.float64, device=x.device)
             self.cons_jac(x, c, jvals, stitch=False)
-        return d.kkt_schur_cr_shard_factor(jvals, px, pc, sc)
+        return px, pc, jvals
 
     def exchange_jvals_block_halo(self, jvals):
         """The joined form of the Schur preconditioner: fills, inside this rank's full-length Jacobian values (CSR order), the values
@@ -970,12 +950,7 @@ class ShardedDOCP:
         (`exchange_jvals_block_halo`) and one all-gather of the factor records, after which every rank factors the same reduced
         system.  Returns the SchurCrJointPrecond for `kkt_minres(precond=P)`.  Inputs as `kkt_diag_precond`."""
         d = self.docp
-        px, pc = self.kkt_diag_precond(x, y, obj_weight, sx, sc, floor, x_halo_valid, y_halo_valid)
-        self.exchange_product_halo(px)
-        if jvals is None:
-            jvals = torch.empty(d.nnzj, dtype=torch.float64, device=x.device)
-            c = torch.empty(d.dim_NLP_constraints, dtype=torch.float64, device=x.device)
-            self.cons_jac(x, c, jvals, stitch=False)
+        px, pc, jvals = self._schur_cr_inputs(x, y, obj_weight, sx, sc, floor, jvals, x_halo_valid, y_halo_valid)
         self.exchange_jvals_block_halo(jvals)
         cur = torch.cuda.current_stream(x.device).cuda_stream
         if d._stream_raw != cur:
@@ -1020,20 +995,12 @@ class ShardedDOCP:
             build = {"diag": self.kkt_diag_precond, "schur_cr": self.kkt_schur_cr_precond, "schur_cr_joint": self.kkt_schur_cr_joint_precond}[precond]
             precond = build(x, y, obj_weight, sx, sc, x_halo_valid=True, y_halo_valid=True)
         collective = self.world > 1 or _FORCE
-        if isinstance(precond, SchurCrJointPrecond):      # (slots that also carry the solve records: a workspace of its own)
-            if (precond.layout.n_ranks, precond.layout.rank) != (self.world, self.rank):
-                raise ValueError(f"precond was factored as rank {precond.layout.rank} of {precond.layout.n_ranks}, this is rank {self.rank} of {self.world}")
-            w = self._minres_joint_ws
-            if w is None or w.ws.device != x.device:
-                w = self._minres_joint_ws = d.kkt_minres_schur_joint_workspace(self.world, self.rank)
-        elif isinstance(precond, SchurCrShardPrecond):
-            w = self._minres_schur_ws
-            if w is None or w.ws.device != x.device:
-                w = self._minres_schur_ws = d.kkt_minres_schur_shard_workspace(self.world)
-        else:
-            w = self._minres_ws
-            if w is None or w.ws.device != x.device:
-                w = self._minres_ws = d.kkt_minres_shard_workspace(self.world)
+        if isinstance(precond, SchurCrJointPrecond) and (precond.layout.n_ranks, precond.layout.rank) != (self.world, self.rank):
+            raise ValueError(f"precond was factored as rank {precond.layout.rank} of {precond.layout.n_ranks}, this is rank {self.rank} of {self.world}")
+        fam = _phase_family(precond)           # (every family cuts its own slots: a workspace per family)
+        w = self._minres_ws.get(fam)
+        if w is None or w.ws.device != x.device:
+            w = self._minres_ws[fam] = d._phase_workspace(fam, self.world, self.rank)
         z = torch.empty(n, dtype=torch.float64, device=x.device) if out is None else out
 
         def gather(which):

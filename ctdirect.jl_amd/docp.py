@@ -121,6 +121,22 @@ SchurCrShardPrecond = namedtuple("SchurCrShardPrecond", "px pc ws layout")
 # factor (layout: ctd_schur_cr_joint_layout); send, xsend: the rank's factor record and solve record
 SchurCrJointPrecond = namedtuple("SchurCrJointPrecond", "px pc ws layout send xsend")
 MinresShardWorkspace = namedtuple("MinresShardWorkspace", "ws layout n_ranks v_x v_c kv_x kv_c send_a send_b gathered_a gathered_b")
+# A family of sharded MINRES phases (layout, start, begin, alfa, lanczos, update, info): the prefix of its C entry points, the slot
+# length its workspaces are cut with, the class of the preconditioner it carries (None: none, or a pair (px, pc)), whether its
+# layout query takes the rank, and the phases that take the factor's workspace.  DOCP._phase_* are the one implementation behind the
+# public kkt_minres_*shard* / *joint* methods; dist.MinresPhases picks the family from the preconditioner (_phase_family).
+_PhaseFamily = namedtuple("_PhaseFamily", "prefix slot precond layout_rank schur")
+_PHASE_FAMILIES = (
+    _PhaseFamily("ctd_kkt_minres_shard_", _lib.KKT_MINRES_SHARD_SLOT, None, False, ()),
+    _PhaseFamily("ctd_kkt_minres_schur_cr_shard_", _lib.KKT_MINRES_SCHUR_SHARD_SLOT, SchurCrShardPrecond, False, ("start", "lanczos")),
+    _PhaseFamily("ctd_kkt_minres_schur_cr_joint_", _lib.KKT_MINRES_SCHUR_JOINT_SLOT, SchurCrJointPrecond, True,
+                ("start", "begin", "lanczos", "update")))
+_PLAIN, _SCHUR_SHARD, _SCHUR_JOINT = _PHASE_FAMILIES
+
+
+def _phase_family(precond):
+    """the phase family of a sharded solve with `precond`: that of its class, the diagonal form's otherwise"""
+    return next((f for f in _PHASE_FAMILIES if f.precond is not None and isinstance(precond, f.precond)), _PLAIN)
 
 
 def _mf_rows(L, nvar, ncon):
@@ -653,6 +669,27 @@ class DOCP:
                 raise ValueError(f"{fn}: {nm} must be a device tensor on the handle's GPU; NumPy inputs are not accepted (the Schur "
                                  "preconditioner has no host path)")
 
+    def _schur_solve(self, name, P, r, out, sync):
+        """the solve of a family with the factor P: `ctd_<name>_dev_async` on (P.ws, r, out), out zeros when None"""
+        self._tensors_only(name, r=r, out=out, ws=P.ws)
+        ncon = self.dim_NLP_constraints
+        if out is None:
+            import torch
+            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
+            torch.cuda.current_stream(r.device).synchronize()
+        self._ck(getattr(_lib.lib(), f"ctd_{name}_dev_async")(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), self._dev_ptr(r, ncon, "r"),
+                                                             self._dev_ptr(out, ncon, "out")))
+        if sync:
+            self.sync()
+        return out
+
+    def _schur_info(self, name, P, *split):
+        """the status query of a family: `ctd_<name>` on P.ws (split: n_ranks and rank where the entry point takes them)"""
+        self._tensors_only(name, ws=P.ws)
+        bad = C.c_int64(0)
+        self._ck(getattr(_lib.lib(), "ctd_" + name)(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), *split, C.byref(bad)))
+        return bad.value
+
     def kkt_schur_layout(self, chunk_steps=None):
         """`ctd_kkt_schur_layout`: N, block_rows (m), tail_rows, first_tail_row, tail_cols (nv), n_chunks, the effective chunk_steps
         and the workspace in doubles of the chunked block-tridiagonal Schur preconditioner; chunk_steps = None: one chunk.  Checks
@@ -696,25 +733,12 @@ class DOCP:
     def kkt_schur_solve(self, P, r, out=None, sync=True):
         """`ctd_kkt_schur_solve_dev_async`: out = blkdiag(T_c)^-1 r on the block rows (the first layout.first_tail_row entries); the
         tail rows of out are left untouched (zero in a tensor allocated here).  r, out: ncon entries, out must not be r."""
-        self._tensors_only("kkt_schur_solve", r=r, out=out, ws=P.ws)
-        ncon = self.dim_NLP_constraints
-        if out is None:
-            import torch
-            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
-            torch.cuda.current_stream(r.device).synchronize()
-        self._ck(_lib.lib().ctd_kkt_schur_solve_dev_async(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), self._dev_ptr(r, ncon, "r"),
-                                                         self._dev_ptr(out, ncon, "out")))
-        if sync:
-            self.sync()
-        return out
+        return self._schur_solve("kkt_schur_solve", P, r, out, sync)
 
     def kkt_schur_info(self, P):
         """`ctd_kkt_schur_info`: waits for the handle's stream; -1 when every pivot of the factor was positive, otherwise the first
         block (time step) whose pivot was not positive or not finite -- the preconditioner is then unusable (MINRES: "breakdown")."""
-        self._tensors_only("kkt_schur_info", ws=P.ws)
-        bad = C.c_int64(0)
-        self._ck(_lib.lib().ctd_kkt_schur_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
-        return bad.value
+        return self._schur_info("kkt_schur_info", P)
 
     # ---- log-depth exact block-tridiagonal Schur preconditioner (ctd_kkt_schur_cr*) --------------------------------------------------
     def kkt_schur_cr_layout(self):
@@ -758,25 +782,12 @@ class DOCP:
         """`ctd_kkt_schur_cr_solve_dev_async`: out = T^-1 r on the block rows (the first layout.first_tail_row entries); the tail
         rows of out are left untouched (zero in a tensor allocated here).  r, out: ncon entries, out must not be r; the scratch
         region of P.ws is written."""
-        self._tensors_only("kkt_schur_cr_solve", r=r, out=out, ws=P.ws)
-        ncon = self.dim_NLP_constraints
-        if out is None:
-            import torch
-            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
-            torch.cuda.current_stream(r.device).synchronize()
-        self._ck(_lib.lib().ctd_kkt_schur_cr_solve_dev_async(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"),
-                                                            self._dev_ptr(r, ncon, "r"), self._dev_ptr(out, ncon, "out")))
-        if sync:
-            self.sync()
-        return out
+        return self._schur_solve("kkt_schur_cr_solve", P, r, out, sync)
 
     def kkt_schur_cr_info(self, P):
         """`ctd_kkt_schur_cr_info`: waits for the handle's stream; -1 when every pivot of the factor was positive, otherwise the
         smallest block (time step) with a pivot that was not positive or not finite (MINRES: "breakdown")."""
-        self._tensors_only("kkt_schur_cr_info", ws=P.ws)
-        bad = C.c_int64(0)
-        self._ck(_lib.lib().ctd_kkt_schur_cr_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
-        return bad.value
+        return self._schur_info("kkt_schur_cr_info", P)
 
     # ---- the shard form of the log-depth Schur preconditioner (ctd_kkt_schur_cr_shard_*) ---------------------------------------------
     def kkt_schur_cr_shard_layout(self):
@@ -811,25 +822,12 @@ class DOCP:
     def kkt_schur_cr_shard_solve(self, P, r, out=None, sync=True):
         """`ctd_kkt_schur_cr_shard_solve_dev_async`: out = T_r^-1 r on the handle's block rows [first_row, first_row + n_blocks
         block_rows); nothing else of out is written (zero in a tensor allocated here).  r, out: ncon entries, out must not be r."""
-        self._tensors_only("kkt_schur_cr_shard_solve", r=r, out=out, ws=P.ws)
-        ncon = self.dim_NLP_constraints
-        if out is None:
-            import torch
-            out = torch.zeros(ncon, dtype=torch.float64, device=r.device)
-            torch.cuda.current_stream(r.device).synchronize()
-        self._ck(_lib.lib().ctd_kkt_schur_cr_shard_solve_dev_async(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"),
-                                                                  self._dev_ptr(r, ncon, "r"), self._dev_ptr(out, ncon, "out")))
-        if sync:
-            self.sync()
-        return out
+        return self._schur_solve("kkt_schur_cr_shard_solve", P, r, out, sync)
 
     def kkt_schur_cr_shard_info(self, P):
         """`ctd_kkt_schur_cr_shard_info`: waits for the handle's stream; -1 when every pivot of the factor was positive, otherwise
         the smallest GLOBAL block (time step) of the handle's range with a pivot that was not positive or not finite."""
-        self._tensors_only("kkt_schur_cr_shard_info", ws=P.ws)
-        bad = C.c_int64(0)
-        self._ck(_lib.lib().ctd_kkt_schur_cr_shard_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), C.byref(bad)))
-        return bad.value
+        return self._schur_info("kkt_schur_cr_shard_info", P)
 
     # ---- the joined form of the log-depth Schur preconditioner (ctd_kkt_schur_cr_joint_*): the couplings across the ranks restored ----
     def kkt_schur_cr_joint_layout(self, n_ranks, rank):
@@ -902,11 +900,7 @@ class DOCP:
     def kkt_schur_cr_joint_info(self, P):
         """`ctd_kkt_schur_cr_joint_info`: waits for the handle's stream; -1 when every pivot was positive, otherwise the smallest GLOBAL
         block with a recorded pivot among the rank's interior and the separators of the reduced factor."""
-        self._tensors_only("kkt_schur_cr_joint_info", ws=P.ws)
-        bad = C.c_int64(0)
-        self._ck(_lib.lib().ctd_kkt_schur_cr_joint_info(self._h, self._dev_ptr(P.ws, P.layout.workspace, "ws"), P.layout.n_ranks, P.layout.rank,
-                                                        C.byref(bad)))
-        return bad.value
+        return self._schur_info("kkt_schur_cr_joint_info", P, P.layout.n_ranks, P.layout.rank)
 
     # ---- device-resident preconditioned MINRES solve of K z = rhs (ctd_kkt_minres*) ---------------------------------------------
     def _kkt_system(self, fn, vecs, obj_weight, host_ok):
@@ -1043,25 +1037,17 @@ class DOCP:
         self._ck(_lib.lib().ctd_kkt_minres_info(self._h, C.byref(info)))
         return self._minres_info(info)
 
-    # ---- the solve on a shard of the grid (ctd_kkt_minres_shard_*): the phases between the caller's all-gathers --------------------
-    def kkt_minres_shard_layout(self, n_ranks):
-        """`ctd_kkt_minres_shard_layout`: what this handle's shard owns of a Krylov vector (var_*, tail_*, row_*: index ranges of an
-        (nvar + ncon)-vector; n_own, n_dot), the launch geometry (nwg, chunk) and the offsets of the workspace, for a split of the
-        grid into n_ranks blocks.  Needs no device."""
+    # ---- the solve on a shard of the grid: the phases between the caller's all-gathers.  One implementation (_phase_*) for the
+    # three families of _PHASE_FAMILIES; the public methods below name the family -------------------------------------------------
+    def _phase_layout(self, fam, n_ranks, rank=None):
         lay = _lib.ctd_minres_shard_layout(struct_size=C.sizeof(_lib.ctd_minres_shard_layout))
-        self._ck(_lib.lib().ctd_kkt_minres_shard_layout(self._h, int(n_ranks), C.byref(lay)))
+        split = (int(n_ranks), int(rank)) if fam.layout_rank else (int(n_ranks),)
+        self._ck(getattr(_lib.lib(), fam.prefix + "layout")(self._h, *split, C.byref(lay)))
         return lay
 
-    def kkt_minres_shard_workspace(self, n_ranks, ws=None):
-        """The caller-owned workspace of one sharded solve on this handle's GPU (`ws`: the caller's tensor of
-        kkt_minres_shard_layout(n_ranks).workspace doubles, allocated when None): a MinresShardWorkspace with the tensor `ws` and
-        named views of it -- v_x, v_c (the Lanczos vector the operator is applied to), kv_x, kv_c (where `kktprod_shard` puts K v),
-        send_a, send_b (this rank's slots) and gathered_a, gathered_b (n_ranks slots each, rank-major: what the all-gathers
-        fill; with one rank they are the send slots)."""
-        return self._shard_workspace(self.kkt_minres_shard_layout(n_ranks), n_ranks, ws)
-
-    def _shard_workspace(self, lay, n_ranks, ws):
+    def _phase_workspace(self, fam, n_ranks, rank=None, ws=None):
         import torch
+        lay = self._phase_layout(fam, n_ranks, rank)
         if ws is None:
             ws = torch.zeros(lay.workspace, dtype=torch.float64, device=torch.device("cuda", self.device))
         self._dev_ptr(ws, lay.workspace, "ws")
@@ -1071,19 +1057,22 @@ class DOCP:
                                     cut(lay.off_kv + nvar, n - nvar), cut(lay.off_send_a, slot), cut(lay.off_send_b, slot),
                                     cut(lay.off_gathered_a, G * slot), cut(lay.off_gathered_b, G * slot))
 
-    def _shard_ws_ptr(self, w, slot):
-        """the workspace's pointer, for the phase family whose slots have `slot` doubles: the C side lays the pointer out with its
-        own slot length and cannot know the tensor's, so a workspace cut for another family never reaches a kernel"""
-        if w.layout.slot != slot:
-            raise ValueError(f"the workspace was cut with slots of {w.layout.slot} doubles, this phase family needs {slot}: take it from "
+    def _phase_ws_ptr(self, fam, w):
+        """the workspace's pointer: the C side lays the pointer out with the family's slot length and cannot know the tensor's, so a
+        workspace cut for another family never reaches a kernel"""
+        if w.layout.slot != fam.slot:
+            raise ValueError(f"the workspace was cut with slots of {w.layout.slot} doubles, this phase family needs {fam.slot}: take it from "
                              "the family's own kkt_minres_*_workspace")
         return self._dev_ptr(w.ws, w.layout.workspace, "ws")
 
-    def kkt_minres_shard_start(self, rhs, z, w, rank, precond=None, rtol=1e-10, max_iter=None):
-        """`ctd_kkt_minres_shard_start_dev_async` on the workspace w: z = 0 and the vectors on the owned entries, the partial sums
-        of beta1^2 into w.send_a.  precond: None or a pair (px, pc), read now only.  max_iter: default 5 (nvar + ncon)."""
+    def _phase_schur(self, fam, phase, precond):
+        """the factor's workspace as the leading argument of the phases of the family that take it"""
+        return (self._dev_ptr(precond.ws, precond.layout.workspace, "schur_ws"),) if phase in fam.schur else ()
+
+    def _phase_start(self, fam, precond, rhs, z, w, rank, rtol=1e-10, max_iter=None):
+        """precond: the family's preconditioner; the diagonal form's: None or a pair (px, pc)"""
         nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        px, pc = (None, None) if precond is None else precond
+        px, pc = (None, None) if precond is None else ((precond.px, precond.pc) if fam.precond else precond)
         if (px is None) != (pc is None):
             raise ValueError("px and pc are given both (M = diag(1 / px, 1 / pc)) or neither")
         for nm, a in (("rhs", rhs), ("z", z)):
@@ -1092,139 +1081,133 @@ class DOCP:
         sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=1.0)
         if px is not None:
             sys.px, sys.pc = self._dev_ptr(px, nvar, "px").value, self._dev_ptr(pc, ncon, "pc").value
-        self._ck(_lib.lib().ctd_kkt_minres_shard_start_dev_async(
-            self._h, C.byref(sys), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SHARD_SLOT),
-            w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+        self._ck(getattr(_lib.lib(), fam.prefix + "start_dev_async")(
+            self._h, C.byref(sys), *self._phase_schur(fam, "start", precond), self._dev_ptr(rhs, nvar + ncon, "rhs"),
+            self._dev_ptr(z, nvar + ncon, "z"), self._phase_ws_ptr(fam, w), w.n_ranks, int(rank), float(rtol),
+            int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+
+    def _phase(self, fam, phase, precond, z, w, rank):
+        """begin (which has no z), alfa, lanczos, update"""
+        zp = () if phase == "begin" else (self._dev_ptr(z, w.layout.n, "z"),)
+        self._ck(getattr(_lib.lib(), f"{fam.prefix}{phase}_dev_async")(
+            self._h, *self._phase_schur(fam, phase, precond), *zp, self._phase_ws_ptr(fam, w), w.n_ranks, int(rank)))
+
+    def _phase_info(self, fam, w):
+        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
+        self._ck(getattr(_lib.lib(), fam.prefix + "info")(self._h, self._phase_ws_ptr(fam, w), w.n_ranks, C.byref(info)))
+        return self._minres_info(info)
+
+    # the diagonal form (ctd_kkt_minres_shard_*)
+    def kkt_minres_shard_layout(self, n_ranks):
+        """`ctd_kkt_minres_shard_layout`: what this handle's shard owns of a Krylov vector (var_*, tail_*, row_*: index ranges of an
+        (nvar + ncon)-vector; n_own, n_dot), the launch geometry (nwg, chunk) and the offsets of the workspace, for a split of the
+        grid into n_ranks blocks.  Needs no device."""
+        return self._phase_layout(_PLAIN, n_ranks)
+
+    def kkt_minres_shard_workspace(self, n_ranks, ws=None):
+        """The caller-owned workspace of one sharded solve on this handle's GPU (`ws`: the caller's tensor of
+        kkt_minres_shard_layout(n_ranks).workspace doubles, allocated when None): a MinresShardWorkspace with the tensor `ws` and
+        named views of it -- v_x, v_c (the Lanczos vector the operator is applied to), kv_x, kv_c (where `kktprod_shard` puts K v),
+        send_a, send_b (this rank's slots) and gathered_a, gathered_b (n_ranks slots each, rank-major: what the all-gathers
+        fill; with one rank they are the send slots)."""
+        return self._phase_workspace(_PLAIN, n_ranks, ws=ws)
+
+    def kkt_minres_shard_start(self, rhs, z, w, rank, precond=None, rtol=1e-10, max_iter=None):
+        """`ctd_kkt_minres_shard_start_dev_async` on the workspace w: z = 0 and the vectors on the owned entries, the partial sums
+        of beta1^2 into w.send_a.  precond: None or a pair (px, pc), read now only.  max_iter: default 5 (nvar + ncon)."""
+        self._phase_start(_PLAIN, precond, rhs, z, w, rank, rtol, max_iter)
 
     def kkt_minres_shard_begin(self, w, rank):
         """`ctd_kkt_minres_shard_begin_dev_async`: beta1 from w.gathered_a, the first Lanczos vector, the state."""
-        self._ck(_lib.lib().ctd_kkt_minres_shard_begin_dev_async(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SHARD_SLOT), w.n_ranks, int(rank)))
-
-    def _shard_phase(self, fn, z, w, rank):
-        name = fn.__name__          # (the phase family is in the entry point's name)
-        slot = _lib.KKT_MINRES_SCHUR_JOINT_SLOT if "schur_cr_joint" in name else (
-            _lib.KKT_MINRES_SCHUR_SHARD_SLOT if "schur_cr_shard" in name else _lib.KKT_MINRES_SHARD_SLOT)
-        self._ck(fn(self._h, self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, slot), w.n_ranks, int(rank)))
+        self._phase(_PLAIN, "begin", None, None, w, rank)
 
     def kkt_minres_shard_alfa(self, z, w, rank):
         """`ctd_kkt_minres_shard_alfa_dev_async`: phase (A), after `kktprod_shard` wrote K v into (w.kv_x, w.kv_c)."""
-        self._shard_phase(_lib.lib().ctd_kkt_minres_shard_alfa_dev_async, z, w, rank)
+        self._phase(_PLAIN, "alfa", None, z, w, rank)
 
     def kkt_minres_shard_lanczos(self, z, w, rank):
         """`ctd_kkt_minres_shard_lanczos_dev_async`: phase (B), after w.gathered_a was filled."""
-        self._shard_phase(_lib.lib().ctd_kkt_minres_shard_lanczos_dev_async, z, w, rank)
+        self._phase(_PLAIN, "lanczos", None, z, w, rank)
 
     def kkt_minres_shard_update(self, z, w, rank):
         """`ctd_kkt_minres_shard_update_dev_async`: phase (C), after w.gathered_b was filled."""
-        self._shard_phase(_lib.lib().ctd_kkt_minres_shard_update_dev_async, z, w, rank)
+        self._phase(_PLAIN, "update", None, z, w, rank)
 
     def kkt_minres_shard_info(self, w):
         """`ctd_kkt_minres_shard_info`: waits for the handle's stream and returns the MinresInfo in the workspace's state."""
-        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
-        self._ck(_lib.lib().ctd_kkt_minres_shard_info(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SHARD_SLOT), w.n_ranks, C.byref(info)))
-        return self._minres_info(info)
+        return self._phase_info(_PLAIN, w)
 
-    # ---- ... with the shard form of the log-depth Schur preconditioner (ctd_kkt_minres_schur_cr_shard_*): the same phases on
-    # larger slots; P is the SchurCrShardPrecond of this handle ------------------------------------------------------------------
+    # ... with the shard form of the log-depth Schur preconditioner (ctd_kkt_minres_schur_cr_shard_*): the same phases on larger
+    # slots; P is the SchurCrShardPrecond of this handle
     def kkt_minres_schur_shard_layout(self, n_ranks):
         """`ctd_kkt_minres_schur_cr_shard_layout`: `kkt_minres_shard_layout` with slots of CTD_KKT_MINRES_SCHUR_SHARD_SLOT doubles."""
-        lay = _lib.ctd_minres_shard_layout(struct_size=C.sizeof(_lib.ctd_minres_shard_layout))
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_layout(self._h, int(n_ranks), C.byref(lay)))
-        return lay
+        return self._phase_layout(_SCHUR_SHARD, n_ranks)
 
     def kkt_minres_schur_shard_workspace(self, n_ranks, ws=None):
         """`kkt_minres_shard_workspace` for the solve with a SchurCrShardPrecond: the same views, cut with the larger slots."""
-        return self._shard_workspace(self.kkt_minres_schur_shard_layout(n_ranks), n_ranks, ws)
-
-    def _schur_ws_ptr(self, P):
-        return self._dev_ptr(P.ws, P.layout.workspace, "schur_ws")
+        return self._phase_workspace(_SCHUR_SHARD, n_ranks, ws=ws)
 
     def kkt_minres_schur_shard_start(self, P, rhs, z, w, rank, rtol=1e-10, max_iter=None):
         """`ctd_kkt_minres_schur_cr_shard_start_dev_async`: the start of `kkt_minres_shard_start` with M of P; the partial sums of
         beta1^2 -- the solve's behind the init kernel's -- go into w.send_a."""
-        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        for nm, a in (("rhs", rhs), ("z", z)):
-            if a is None:
-                raise ValueError(f"{nm} is required")
-        sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=1.0)
-        sys.px, sys.pc = self._dev_ptr(P.px, nvar, "px").value, self._dev_ptr(P.pc, ncon, "pc").value
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_start_dev_async(
-            self._h, C.byref(sys), self._schur_ws_ptr(P), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"),
-            self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+        self._phase_start(_SCHUR_SHARD, P, rhs, z, w, rank, rtol, max_iter)
 
     def kkt_minres_schur_shard_begin(self, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_begin_dev_async`"""
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_begin_dev_async(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, int(rank)))
+        self._phase(_SCHUR_SHARD, "begin", None, None, w, rank)
 
     def kkt_minres_schur_shard_alfa(self, z, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_alfa_dev_async`: phase (A)"""
-        self._shard_phase(_lib.lib().ctd_kkt_minres_schur_cr_shard_alfa_dev_async, z, w, rank)
+        self._phase(_SCHUR_SHARD, "alfa", None, z, w, rank)
 
     def kkt_minres_schur_shard_lanczos(self, P, z, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_lanczos_dev_async`: phase (B), the solve with P's factor on the handle's block rows, and
         its partial sums into w.send_b"""
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_lanczos_dev_async(
-            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, int(rank)))
+        self._phase(_SCHUR_SHARD, "lanczos", P, z, w, rank)
 
     def kkt_minres_schur_shard_update(self, z, w, rank):
         """`ctd_kkt_minres_schur_cr_shard_update_dev_async`: phase (C)"""
-        self._shard_phase(_lib.lib().ctd_kkt_minres_schur_cr_shard_update_dev_async, z, w, rank)
+        self._phase(_SCHUR_SHARD, "update", None, z, w, rank)
 
     def kkt_minres_schur_shard_info(self, w):
         """`ctd_kkt_minres_schur_cr_shard_info`"""
-        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_shard_info(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_SHARD_SLOT), w.n_ranks, C.byref(info)))
-        return self._minres_info(info)
+        return self._phase_info(_SCHUR_SHARD, w)
 
-    # ---- ... with the joined form (ctd_kkt_minres_schur_cr_joint_*): the same phases on slots that also carry the solve records; P is
-    # the SchurCrJointPrecond of this handle, joined (kkt_schur_cr_joint_factor_join) ---------------------------------------------
+    # ... with the joined form (ctd_kkt_minres_schur_cr_joint_*): the same phases on slots that also carry the solve records; P is the
+    # SchurCrJointPrecond of this handle, joined (kkt_schur_cr_joint_factor_join)
     def kkt_minres_schur_joint_layout(self, n_ranks, rank):
         """`ctd_kkt_minres_schur_cr_joint_layout`: `kkt_minres_shard_layout` with slots of CTD_KKT_MINRES_SCHUR_JOINT_SLOT doubles."""
-        lay = _lib.ctd_minres_shard_layout(struct_size=C.sizeof(_lib.ctd_minres_shard_layout))
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_layout(self._h, int(n_ranks), int(rank), C.byref(lay)))
-        return lay
+        return self._phase_layout(_SCHUR_JOINT, n_ranks, rank)
 
     def kkt_minres_schur_joint_workspace(self, n_ranks, rank, ws=None):
         """`kkt_minres_shard_workspace` for the solve with a SchurCrJointPrecond: the same views, cut with the larger slots."""
-        return self._shard_workspace(self.kkt_minres_schur_joint_layout(n_ranks, rank), n_ranks, ws)
+        return self._phase_workspace(_SCHUR_JOINT, n_ranks, rank, ws)
 
     def kkt_minres_schur_joint_start(self, P, rhs, z, w, rank, rtol=1e-10, max_iter=None):
         """`ctd_kkt_minres_schur_cr_joint_start_dev_async`: the start with M of P; the partial sums of beta1^2 and the rank's solve
         record go into w.send_a."""
-        nvar, ncon = self.dim_NLP_variables, self.dim_NLP_constraints
-        for nm, a in (("rhs", rhs), ("z", z)):
-            if a is None:
-                raise ValueError(f"{nm} is required")
-        sys = _lib.ctd_kkt_system(struct_size=C.sizeof(_lib.ctd_kkt_system), obj_weight=1.0)
-        sys.px, sys.pc = self._dev_ptr(P.px, nvar, "px").value, self._dev_ptr(P.pc, ncon, "pc").value
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_start_dev_async(
-            self._h, C.byref(sys), self._schur_ws_ptr(P), self._dev_ptr(rhs, nvar + ncon, "rhs"), self._dev_ptr(z, nvar + ncon, "z"),
-            self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank), float(rtol), int(5 * (nvar + ncon) if max_iter is None else max_iter)))
+        self._phase_start(_SCHUR_JOINT, P, rhs, z, w, rank, rtol, max_iter)
 
     def kkt_minres_schur_joint_begin(self, P, w, rank):
         """`ctd_kkt_minres_schur_cr_joint_begin_dev_async`: the two join launches, then beta1 and the first Lanczos vector"""
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_begin_dev_async(self._h, self._schur_ws_ptr(P), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank)))
+        self._phase(_SCHUR_JOINT, "begin", P, None, w, rank)
 
     def kkt_minres_schur_joint_alfa(self, z, w, rank):
         """`ctd_kkt_minres_schur_cr_joint_alfa_dev_async`: phase (A)"""
-        self._shard_phase(_lib.lib().ctd_kkt_minres_schur_cr_joint_alfa_dev_async, z, w, rank)
+        self._phase(_SCHUR_JOINT, "alfa", None, z, w, rank)
 
     def kkt_minres_schur_joint_lanczos(self, P, z, w, rank):
         """`ctd_kkt_minres_schur_cr_joint_lanczos_dev_async`: phase (B), the interior's solve, its partial sums and the solve record
         into w.send_b"""
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_lanczos_dev_async(
-            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank)))
+        self._phase(_SCHUR_JOINT, "lanczos", P, z, w, rank)
 
     def kkt_minres_schur_joint_update(self, P, z, w, rank):
         """`ctd_kkt_minres_schur_cr_joint_update_dev_async`: the two join launches, then phase (C)"""
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_update_dev_async(
-            self._h, self._schur_ws_ptr(P), self._dev_ptr(z, w.layout.n, "z"), self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, int(rank)))
+        self._phase(_SCHUR_JOINT, "update", P, z, w, rank)
 
     def kkt_minres_schur_joint_info(self, w):
         """`ctd_kkt_minres_schur_cr_joint_info`"""
-        info = _lib.ctd_minres_info(struct_size=C.sizeof(_lib.ctd_minres_info))
-        self._ck(_lib.lib().ctd_kkt_minres_schur_cr_joint_info(self._h, self._shard_ws_ptr(w, _lib.KKT_MINRES_SCHUR_JOINT_SLOT), w.n_ranks, C.byref(info)))
-        return self._minres_info(info)
+        return self._phase_info(_SCHUR_JOINT, w)
 
     def grad_shard(self, x, g, sync=False):
         """`ctd_grad_shard_dev_async`: the gradient entries of THIS shard's own variables into the full-length device tensor g
